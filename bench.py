@@ -9,16 +9,33 @@ N = 1 workload: the north-star's headline shape, a 4 GiB random DNA string
 MI355X (the largest single-GPU configuration; BASELINE.json configs[2], 4 GiB
 random ASCII, is `--alphabet ascii128`; configs[1], 256 MiB DNA with uint32
 indices, is `--n 268435456 --index 32`).  The text is generated in HBM
-(psacx_synth_text_dev), the result of the last timed step is verified in HBM
-(psacx_check_dev_*), and the PCIe-inclusive construct() time on host pointers
-(SURVEY 8(d) Metric 1) is reported beside `value` as `construct_host`.
+(psacx_synth_text_dev); with --full the result of the last timed step is
+verified in HBM (psacx_check_dev_*), and the PCIe-inclusive construct() time on
+host pointers (SURVEY 8(d) Metric 1) is reported beside `value` as
+`construct_host`.
 
 Prints ONE JSON line (rank 0): metric MChars/s, plus
   roofline     -- the dominant kernel (the radix scatter pass of the rank-pair
                   sort): algorithmic bytes (6w per record per pass)
                   / HIP-event time of those launches inside the timed region
-  cpu_baseline -- the CPU oracle (a port of psac's algorithm, 1 thread) timed on
+  cpu_baseline -- (--full) the CPU oracle (a port of psac's algorithm) timed on
                   this box's host on a bounded sample of the same kind of text.
+
+A plain run sets up, warms up, times --steps constructions and prints the line
+(with the roofline, read from the timed steps themselves).  Everything else --
+the device check of the last result (`check`), the side workloads
+(`other_workloads`), the host-pointer path (`construct_host`,
+`value_metric1`), the CPU baselines (`cpu_baseline`) and, with more than one
+GPU, the one-GPU engine on the same block (`weak_scaling_efficiency`) -- runs
+only with --full; an explicit --side / --host-path / --cpu-sample still asks
+for its own leg.
+
+--dump-outputs DIR writes what the last timed step left in HBM as
+DIR/SA.npy, DIR/ISA.npy and DIR/LCP.npy (float64, exact below 2^53): whole
+arrays up to 2^21 entries, else a fixed sample of 512 windows of 4096
+consecutive entries (the first, the last and 510 drawn by a seeded generator,
+in increasing order of position).  With more than one GPU, rank r > 0 writes
+<name>_rank<r>.npy of its own block, the sample divided among the ranks.
 """
 import argparse
 import json
@@ -78,18 +95,31 @@ def parse():
     ap.add_argument("--index", type=int, default=None, choices=(32, 64), help="index width (default: 64 above 2^31 characters)")
     ap.add_argument("--alphabet", default="dna", choices=("dna", "ascii128", "tandem"))
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-sample", type=int, default=1 << 28, help="characters for the CPU baseline leg (0 = skip); the default is the whole workload, ~8 s on the GPU box's 256 host threads")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="characters for the CPU baseline leg (0 = skip); with --full the default is "
+                                                                   "2^28, the whole default workload, else 0")
     ap.add_argument("--no-lcp", action="store_true")
-    ap.add_argument("--host-path", default="auto", choices=("auto", "full", "off"),
+    ap.add_argument("--host-path", default=None, choices=("auto", "full", "off"),
                     help="also time psacx_construct_* with host pointers (H2D of the text, D2H of SA/ISA/LCP: SURVEY 8(d) "
                          "Metric 1); reported as the extra field construct_host, never as `value`.  auto: the full workload "
-                         "when the host has the memory for its results, else 2^28 characters")
-    ap.add_argument("--no-check", action="store_true", help="skip the device checker on the last result")
-    ap.add_argument("--side", default="auto", choices=("auto", "off"),
+                         "when the host has the memory for its results, else 2^28 characters.  Default: auto with --full, else off")
+    ap.add_argument("--no-check", action="store_true", help="skip the device checker on the last result (it runs only with --full)")
+    ap.add_argument("--side", default=None, choices=("auto", "off"),
                     help="after the timed region of the default workload also time BASELINE.json configs[2] (4 GiB ASCII, uint64), "
                          "configs[1] (256 MiB DNA, uint32) and the three-word (B1,B2,idx) form of the scatter pass; reported as "
-                         "the extra field other_workloads, never as `value`")
+                         "the extra field other_workloads, never as `value`.  Default: auto with --full, else off")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks and measurements the headline figure does not need: the device "
+                         "checker, the side workloads, the host-pointer path, the CPU baselines, and with more than one GPU the one-GPU "
+                         "engine on the same block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write SA / ISA / LCP of the last timed step (a fixed sample of large arrays) to DIR/<name>.npy as float64")
     a = ap.parse_args()
+    if a.cpu_sample is None:
+        a.cpu_sample = (1 << 28) if a.full else 0
+    if a.host_path is None:
+        a.host_path = "auto" if a.full else "off"
+    if a.side is None:
+        a.side = "auto" if a.full else "off"
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.n is None and world == 1 and a.gpus == 1 and not os.environ.get("PSACX_BENCH_FORCE_DIST"):
         a.n = 1 << 32
@@ -302,6 +332,12 @@ def main_distributed(a, rank, world, local_rank):
     t = torch.tensor([dt], dtype=torch.float64, device="cuda")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if a.dump_outputs:
+        def d2h(h, p):
+            rc = lib.psacx_copy_d2h(ctx, h.ctypes.data_as(C.c_void_p), C.c_void_p(p), h.nbytes)
+            if rc != 0:
+                raise RuntimeError("device-to-host copy failed rc=%d" % rc)
+        dump_outputs(a.dump_outputs, n, bits, d2h, [("SA", d_sa), ("ISA", d_isa)] + ([] if a.no_lcp else [("LCP", d_lcp)]), world, rank)
     s = psac_amd._lib.Stats()
     lib.psacx_get_stats(ctx, C.byref(s))
     # what every rank saw in its last step: the wire calls it issued, the time its exchanges held its second stream and the
@@ -331,23 +367,24 @@ def main_distributed(a, rank, world, local_rank):
                                    "engine_words_per_char_at_peak_per_rank": [p["engine_words_per_char_at_peak"] for p in per_rank],
                                    "result_arrays_words_per_char": round(3.0 * (n + slack) / n, 3)}
         # for a like-for-like scaling figure: the one-GPU engine on rank 0's block alone (same size, same index width, the same
-        # buffers), timed after the measured region; weak_scaling_efficiency = value / (N x that rate)
-        try:
-            lib.psacx_trim(ctx)              # the multi-GPU engine's cached blocks go back to the device first
-            one = psac_amd.Context(local_rank)
-            sa1 = psac_amd.SuffixArray(index_bits=bits, lcp=not a.no_lcp, ctx=one)
-            sa1.construct_device(d_text, n, d_sa, d_isa, None if a.no_lcp else d_lcp)
-            t1 = time.perf_counter()
-            for _ in range(3):
+        # buffers), timed after the measured region; weak_scaling_efficiency = value / (N x that rate) (--full)
+        if a.full:
+            try:
+                lib.psacx_trim(ctx)              # the multi-GPU engine's cached blocks go back to the device first
+                one = psac_amd.Context(local_rank)
+                sa1 = psac_amd.SuffixArray(index_bits=bits, lcp=not a.no_lcp, ctx=one)
                 sa1.construct_device(d_text, n, d_sa, d_isa, None if a.no_lcp else d_lcp)
-            t1 = (time.perf_counter() - t1) / 3
-            one_rate = n / t1 / 1e6
-            out["config"]["one_gpu_engine_same_block"] = {"ms": round(t1 * 1e3, 3), "MChars_per_s": round(one_rate, 1)}
-            out["weak_scaling_efficiency"] = round(out["value"] / (world * one_rate), 4)
-            one.close()
-        except Exception as e:          # never let the side measurement break the bench line
-            out["config"]["one_gpu_engine_same_block"] = {"error": str(e)[:200]}
-            out["weak_scaling_efficiency"] = None
+                t1 = time.perf_counter()
+                for _ in range(3):
+                    sa1.construct_device(d_text, n, d_sa, d_isa, None if a.no_lcp else d_lcp)
+                t1 = (time.perf_counter() - t1) / 3
+                one_rate = n / t1 / 1e6
+                out["config"]["one_gpu_engine_same_block"] = {"ms": round(t1 * 1e3, 3), "MChars_per_s": round(one_rate, 1)}
+                out["weak_scaling_efficiency"] = round(out["value"] / (world * one_rate), 4)
+                one.close()
+            except Exception as e:          # never let the side measurement break the bench line
+                out["config"]["one_gpu_engine_same_block"] = {"error": str(e)[:200]}
+                out["weak_scaling_efficiency"] = None
     for p in (d_text, d_sa, d_isa, d_lcp):
         lib.psacx_dev_free(ctx, C.c_void_p(p))
     mg.close()
@@ -557,6 +594,44 @@ def mem_available_bytes():
 
 KIND_ID = {"dna": 0, "ascii128": 1, "tandem": 2, "mutated": 3}
 
+DUMP_ENTRIES = 1 << 21          # per array and run: 3 arrays x 2^21 x 8 bytes = 48 MiB of float64
+DUMP_WINDOW = 4096
+DUMP_SEED = 20240611
+
+
+def dump_windows(n, entries):
+    """Start positions of the windows of DUMP_WINDOW entries that --dump-outputs copies from arrays of n entries (None: the whole
+    arrays): the first window, the last and windows on the grid of DUMP_WINDOW between them drawn by a fixed seed, sorted."""
+    import numpy as np
+    if n <= entries:
+        return None
+    slots = n // DUMP_WINDOW
+    k = max(entries // DUMP_WINDOW, 2)
+    rng = np.random.RandomState(DUMP_SEED)
+    inner = rng.choice(np.arange(1, slots - 1, dtype=np.int64), size=min(k - 2, max(slots - 2, 0)), replace=False) if slots > 2 else []
+    return sorted(set([0, n - DUMP_WINDOW] + [int(s) * DUMP_WINDOW for s in inner]))
+
+
+def dump_outputs(path, n, bits, d2h, arrays, world=1, rank=0):
+    """--dump-outputs: arrays = [(name, device pointer of n entries of bits / 8 bytes)]; d2h(host_array, device_pointer) copies
+    host_array.nbytes bytes.  Written as float64 (every index and LCP value is below 2^53)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    dt = np.uint32 if bits == 32 else np.uint64
+    w = bits // 8
+    starts = dump_windows(n, DUMP_ENTRIES // world)
+    for name, p in arrays:
+        if starts is None:
+            h = np.empty(n, dt)
+            if n:
+                d2h(h, p)
+        else:
+            h = np.empty((len(starts), DUMP_WINDOW), dt)
+            for i, s in enumerate(starts):
+                d2h(h[i], p + s * w)
+            h = h.reshape(-1)
+        np.save(os.path.join(path, name + (".npy" if rank == 0 else "_rank%d.npy" % rank)), h.astype(np.float64))
+
 
 def main():
     a = parse()
@@ -604,6 +679,8 @@ def main():
             scat_bytes[q] += s.scatter_bytes[q]; scat_launches[q] += s.scatter_launches[q]
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, n, bits, ctx.d2h, [("SA", d_sa), ("ISA", d_isa)] + ([] if a.no_lcp else [("LCP", d_lcp)]))
 
     phases = {"total": round(s.ms_total, 3), "alphabet": round(s.ms_alphabet, 3), "kmer": round(s.ms_kmer, 3),
               "sort_hist": round(s.ms_sort_hist, 3), "sort_scatter": round(s.ms_sort_scatter + s.ms_sort_scatter3 + s.ms_sort_scatter2, 3),
@@ -615,7 +692,7 @@ def main():
     out["config"]["workspace_GiB"] = round(s.workspace_bytes / 2.0 ** 30, 1)
     # the result of the last timed step, verified where it lies (psacx_check_dev_*: SA a permutation inverse to ISA,
     # suffix order, every LCP entry against a direct character comparison)
-    if not a.no_check:
+    if a.full and not a.no_check:
         t1 = time.perf_counter()
         if a.alphabet == "tandem" and not a.no_lcp:
             # psacx_check_dev_* compares characters (linear in sum(LCP): hours on a long tandem repeat); the multi-GPU

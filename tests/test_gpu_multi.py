@@ -317,7 +317,8 @@ def test_bench_and_cli_process_per_gpu_path(tmp_path):
     # at this size, a roofline entry quoted on the bucket passes (16 or 24 bytes per record) with every send matched by a receive
     env2 = dict(env, PSACX_MULTI_FORCE_WIRE="1", PSACX_MULTI_TWO_WORD="1", PSACX_MULTI_ONE_WORD="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", "29579", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", str(1 << 24), "--index", "64"],
+                        "--master-port", "29579", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", str(1 << 24), "--index", "64",
+                        "--full"],
                        capture_output=True, text=True, env=env2, cwd=root, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
