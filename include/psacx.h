@@ -207,7 +207,15 @@ int psacx_get_stats(const psacx_ctx* ctx, psacx_stats* out);
  * for buffers resident in HBM.  errors[0] = SA entries out of range or ISA[SA[i]] != i,
  * errors[1] = suffix-order violations, errors[2] = LCP entries that differ from a direct
  * character comparison (d_LCP may be NULL), errors[3] = LCP[0] != 0.  All zero = correct.
- * The LCP check costs sum(LCP) character reads: use it on texts without long repeats. */
+ * The LCP check costs sum(LCP) character reads: use it on texts without long repeats.
+ * How entries are counted (tests/checker_model.py states the same rules on the host):
+ *  - an entry i with SA[i] >= n or ISA[SA[i]] != i counts in errors[0] and is examined no further;
+ *  - entry 0 is only asked for LCP[0] == 0; an entry i > 0 is compared with its predecessor only if
+ *    SA[i-1] < n (a predecessor out of range is counted at its own entry);
+ *  - order, with a = SA[i-1], b = SA[i]: fine iff S[a] < S[b], or S[a] == S[b] and (a + 1 == n, or
+ *    b + 1 < n and ISA[a+1] < ISA[b+1]); ISA values are only compared, never used as indices;
+ *  - LCP[i] is compared with the characters the two suffixes share whether or not the order test
+ *    passed, so one wrong LCP entry counts once. */
 int psacx_check_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_SA,
                         const uint32_t* d_ISA, const uint32_t* d_LCP, uint64_t errors[4]);
 int psacx_check_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
@@ -323,7 +331,14 @@ int psacx_multi_construct_u64(psacx_multi* mg, const uint8_t* text, uint64_t n, 
  * ranks of the suffixes one further) through the engine's own exchanges, plus -- beyond the reference, whose
  * distributed checker leaves LCP out -- every LCP entry through the recurrence LCP[i] = 0 | 1 | 1 + min(LCP[ISA[SA[i-1]
  * +1]+1 .. ISA[SA[i]+1]]).  errors[0..3] as psacx_check_dev_*, summed over all ranks (every rank gets the totals).
- * d_LCP may be NULL. */
+ * d_LCP may be NULL.
+ * Counted as by psacx_check_dev_* (errors[0] ends the examination of an entry; predecessor only if in range; the same
+ * order test), with two differences: LCP is not examined at an entry that fails the order test, and errors[2] counts
+ * the entries that break the recurrence over the arrays as given -- 0 if the first characters differ, 1 if
+ * SA[i-1] + 1 == n, else 1 + the range minimum -- so one wrong LCP entry is usually counted at itself and at every
+ * entry whose range minimum it was, and an LCP array raised everywhere is caught only where the recurrence is
+ * anchored (the 0s and 1s).  An entry that passes the order test with ISA[SA[i]+1] >= n (two numbers that are no
+ * ranks compared) counts in errors[2]; no range minimum is asked for it, so an ISA holding anything is safe to pass. */
 int psacx_multi_check_dev_u32(psacx_multi* mg, const uint8_t* const* d_text, const uint64_t* m, const uint32_t* const* d_SA,
                               const uint32_t* const* d_ISA, const uint32_t* const* d_LCP, uint64_t errors[4]);
 int psacx_multi_check_dev_u64(psacx_multi* mg, const uint8_t* const* d_text, const uint64_t* m, const uint64_t* const* d_SA,

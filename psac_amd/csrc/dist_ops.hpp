@@ -44,12 +44,12 @@ __global__ void put_kernel(T* __restrict__ block, const T* __restrict__ g, uint6
 }
 template <typename T>
 __global__ void add_scalar_kernel(const T* __restrict__ in, uint64_t cnt, uint64_t s, uint64_t cap, T* __restrict__ out) {
-    // saturating: in + s is formed in 64 bits and clamped to cap (= n, "past the end"), so SA + h cannot wrap
-    // around a 32-bit index type and come back as a valid position
+    // saturating: min(in + s, cap) without forming a sum that could wrap (cap = n, "past the end"), so SA + h cannot
+    // come back as a valid position for any entry, an all-ones 64-bit one included
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += stride) {
-        const uint64_t v = (uint64_t)in[i] + s;
-        out[i] = (T)(v < cap ? v : cap);
+        const uint64_t x = (uint64_t)in[i];
+        out[i] = (T)((x < cap && s < cap - x) ? x + s : cap);
     }
 }
 template <typename T>

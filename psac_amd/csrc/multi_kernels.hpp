@@ -128,7 +128,9 @@ __global__ void ansv_finish_kernel(const T* __restrict__ first, const T* __restr
 // Distributed check, per block (see MultiRun::check).  For SA position p = off + i:
 //   back[i] = ISA[SA[p]] (must be p), ch[i] = S[SA[p]], nx[i] = ISA[SA[p] + 1] (undefined when SA[p] + 1 == n).
 // Queries of the LCP recurrence: LCP[p] = 0 if the first characters differ, 1 if the smaller suffix is one character
-// long, else 1 + min(LCP[ISA[SA[p-1]+1] + 1 .. ISA[SA[p]+1]]).
+// long, else 1 + min(LCP[ISA[SA[p-1]+1] + 1 .. ISA[SA[p]+1]]).  The two ranks are values fetched from the ISA under test: a
+// question is asked only when both are < n (na < nb < n), so no range leaves the LCP array whatever the ISA holds; an entry
+// whose ranks pass the order test with nb >= n has no recurrence to satisfy and is counted in err[2] by the verdict.
 template <typename T>
 __global__ void check_queries_kernel(const T* __restrict__ SA, const T* __restrict__ ch, const T* __restrict__ nx, uint64_t cnt, uint64_t n,
                                      int has_prev, T prev_sa, T prev_ch, T prev_nx, T* __restrict__ qlo, T* __restrict__ qhi) {
@@ -138,7 +140,7 @@ __global__ void check_queries_kernel(const T* __restrict__ SA, const T* __restri
         if (i > 0 || has_prev) {
             const uint64_t a = i ? (uint64_t)SA[i - 1] : (uint64_t)prev_sa, b = SA[i];
             const T ca = i ? ch[i - 1] : prev_ch, na = i ? nx[i - 1] : prev_nx;
-            if (a < n && b < n && ca == ch[i] && a + 1 < n && b + 1 < n && na < nx[i]) { lo = (T)(na + 1); hi = (T)(nx[i] + 1); }
+            if (a < n && b < n && ca == ch[i] && a + 1 < n && b + 1 < n && na < nx[i] && (uint64_t)nx[i] < n) { lo = (T)(na + 1); hi = (T)(nx[i] + 1); }
         }
         qlo[i] = lo; qhi[i] = hi;
     }
@@ -165,6 +167,7 @@ __global__ void check_verdict_kernel(const T* __restrict__ SA, const T* __restri
             uint64_t want;
             if (ca != cb) want = 0;
             else if (a + 1 == n) want = 1;
+            else if ((uint64_t)nb >= n) { ++e2; continue; }     // a rank that is none: no question was asked (check_queries_kernel)
             else want = 1 + (uint64_t)mins[i];
             if ((uint64_t)LCP[i] != want) ++e2;
         }
