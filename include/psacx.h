@@ -221,6 +221,31 @@ int psacx_check_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const
 int psacx_check_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
                         const uint64_t* d_ISA, const uint64_t* d_LCP, uint64_t errors[4]);
 
+/* The same for a generalized suffix array (psacx_construct_gsa_*): d_text holds the m strings back to back without separators,
+ * d_offsets (device memory) their m + 1 offsets as psacx_construct_gsa_dev_* takes them.  The reference's counterpart is
+ * gl_check_gsa (src/gsac.cpp:85-135), which gathers the arrays on rank 0, compares with libdivsufsort and tolerates swapped equal
+ * suffixes; this is the scalable form (check_suffix_array.hpp:207-267) for string sets, and it pins the order of equal suffixes
+ * as the engine builds them (text order).  Offsets that do not start at 0, do not end at n, hold an empty string or do not ascend
+ * return PSACX_EINVAL before anything else is read.  Beside the 4 KiB slab of the ctx the call allocates a bitmap of n + 1 bits
+ * ("a string starts here / end of text") for the time of the call; no array of n index words.
+ * The counting rules are those of psacx_check_dev_* with "end of text" replaced by "end of the suffix's string"; end(p) is the
+ * offset at which the string holding position p ends:
+ *  - errors[0]: SA[i] >= n or ISA[SA[i]] != i; such an entry is examined no further;
+ *  - errors[3]: LCP[0] != 0;
+ *  - an entry i > 0 that passed is compared with its predecessor only if SA[i-1] < n;
+ *  - errors[1], with a = SA[i-1], b = SA[i]: the entry is fine iff S[a] < S[b], or S[a] == S[b] and one of: a + 1 == end(a) and
+ *    b + 1 == end(b) and a < b (equal suffixes in text order); a + 1 == end(a) and b + 1 < end(b); neither suffix ends after one
+ *    character and ISA[a+1] < ISA[b+1].  (a + 1 < end(a) with b + 1 == end(b) is wrong.)  ISA values are only compared, never used
+ *    as indices;
+ *  - errors[2]: LCP[i] != the number of characters the two suffixes share before either string ends, counted whether or not the
+ *    order test passed (sum(LCP) character reads).
+ * With m = 1 the verdict on correct arrays equals psacx_check_dev_*'s; on corrupt arrays it may differ, because a one-character
+ * suffix that appears twice in a row now fails the a < b rule. */
+int psacx_check_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                            const uint32_t* d_SA, const uint32_t* d_ISA, const uint32_t* d_LCP, uint64_t errors[4]);
+int psacx_check_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                            const uint64_t* d_SA, const uint64_t* d_ISA, const uint64_t* d_LCP, uint64_t errors[4]);
+
 /* benchmark inputs ----------------------------------------------------------------
  * psacx_rand_dna: the reference's generator rand_dna(size, seed) (alphabet.hpp:32-45, used by psac -r,
  * src/psac.cpp:89-93): srand(1337 * seed), then "ACGT"[rand() % 4] per character (glibc rand; host memory).
@@ -343,6 +368,19 @@ int psacx_multi_check_dev_u32(psacx_multi* mg, const uint8_t* const* d_text, con
                               const uint32_t* const* d_ISA, const uint32_t* const* d_LCP, uint64_t errors[4]);
 int psacx_multi_check_dev_u64(psacx_multi* mg, const uint8_t* const* d_text, const uint64_t* m, const uint64_t* const* d_SA,
                               const uint64_t* const* d_ISA, const uint64_t* const* d_LCP, uint64_t errors[4]);
+/* The distributed checker for a generalized suffix array (psacx_multi_construct_gsa_dev_*: the strings back to back in the
+ * block-distributed text, offsets = the nstr + 1 global string offsets on the host of every process).  Same exchanges, pieces and
+ * range minima as psacx_multi_check_dev_*: the string ends travel in a spare bit of the text words.  Malformed offsets (not
+ * starting at 0, not ending at n, an empty string, not ascending) return PSACX_EINVAL.  errors[0], errors[1] and errors[3] as
+ * psacx_check_gsa_dev_* (src/gsac.cpp:85-135 is the reference's gathered counterpart, check_suffix_array.hpp:207-267 the scheme);
+ * errors[2] is examined only where the order test passed and expects, with a = SA[i-1], b = SA[i]: 0 if S[a] != S[b]; 1 if
+ * a + 1 == end(a) or b + 1 == end(b); otherwise 1 + min(LCP[ISA[a+1]+1 .. ISA[b+1]]) over the arrays as given.  An entry whose
+ * order test passed with ISA[b+1] >= n counts in errors[2] and no range minimum is asked for it.  With nstr = 1 the verdict on
+ * correct arrays equals psacx_multi_check_dev_*'s; on corrupt arrays it may differ (a repeated one-character suffix fails a < b). */
+int psacx_multi_check_gsa_dev_u32(psacx_multi* mg, const uint8_t* const* d_text, const uint64_t* m, const uint64_t* offsets, uint64_t nstr,
+                                  const uint32_t* const* d_SA, const uint32_t* const* d_ISA, const uint32_t* const* d_LCP, uint64_t errors[4]);
+int psacx_multi_check_gsa_dev_u64(psacx_multi* mg, const uint8_t* const* d_text, const uint64_t* m, const uint64_t* offsets, uint64_t nstr,
+                                  const uint64_t* const* d_SA, const uint64_t* const* d_ISA, const uint64_t* const* d_LCP, uint64_t errors[4]);
 /* Left-branching characters of block-distributed results (suffix_array<char_t, index_t, true, true>::local_Lc on p ranks,
  * suffix_array.hpp:211-212; filled by :1365-1383 and par_rmq.hpp:334-481 in the reference; by definition
  * Lc[i] = S[SA[i-1] + LCP[i]], desa.hpp:262-264, '\0' past the end and at i = 0): d_Lc[i] receives m[i] bytes for the

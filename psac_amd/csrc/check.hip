@@ -54,6 +54,110 @@ int check_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const T* sa, const 
     return PSACX_OK;
 }
 
+// ---- string sets: the generalized suffix array of psacx_construct_gsa_* (gl_check_gsa, src/gsac.cpp:85-135, gathers everything on one
+// rank and tolerates swapped equal suffixes; here the arrays stay in HBM and equal suffixes must stand in text order, as the engine
+// builds them).  The string ends are a bitmap of n + 1 bits, bit p = "a string starts at p, or p == n": the suffix at a ends after one
+// character iff bit a + 1 is set, and the characters two suffixes can share end at the first set bit past either position.
+//
+// One thread per offset whose word no smaller offset shares writes that word whole (the offsets ascend, so the others of the word
+// follow it directly): plain stores, no atomics.  The words without an offset were zeroed before.
+__global__ void string_ends_bitmap_kernel(const uint64_t* __restrict__ off, uint64_t m, uint32_t* __restrict__ bits) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t <= m; t += stride) {
+        const uint64_t w = off[t] >> 5;
+        if (t && (off[t - 1] >> 5) == w) continue;
+        uint32_t x = 0;
+        for (uint64_t u = t; u <= m && (off[u] >> 5) == w; ++u) x |= 1u << (off[u] & 31);
+        bits[w] = x;
+    }
+}
+
+__device__ __forceinline__ bool ends_at(const uint32_t* __restrict__ bits, uint64_t p) { return (bits[p >> 5] >> (p & 31)) & 1u; }
+
+// characters from p (< n) to the end of its string, or cap (1 <= cap <= n) if there are more: bit n is set, so the scan stays inside
+// the bitmap whatever cap is
+__device__ __forceinline__ uint64_t to_string_end(const uint32_t* __restrict__ bits, uint64_t n, uint64_t p, uint64_t cap) {
+    uint64_t w = (p + 1) >> 5;
+    const uint64_t last = min(p + cap, n) >> 5;
+    uint32_t x = bits[w] & (~0u << ((p + 1) & 31));
+    while (!x && w < last) x = bits[++w];
+    if (!x) return cap;
+    return min((w << 5) + (uint64_t)(__ffs((int)x) - 1) - p, cap);
+}
+
+// err as check_kernel; the rules are those of include/psacx.h (psacx_check_gsa_dev_*)
+template <typename T>
+__global__ void check_gsa_kernel(const uint8_t* __restrict__ text, uint64_t n, const uint32_t* __restrict__ bits, const T* __restrict__ SA,
+                                 const T* __restrict__ ISA, const T* __restrict__ LCP, unsigned long long* __restrict__ err) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned e0 = 0, e1 = 0, e2 = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t b = SA[i];
+        if (b >= n || (uint64_t)ISA[b] != i) { ++e0; continue; }
+        if (i == 0) { if (LCP && LCP[0] != 0) atomicAdd(&err[3], 1ull); continue; }
+        const uint64_t a = SA[i - 1];
+        if (a >= n) continue;                       // counted by the thread that owns i - 1
+        const uint8_t ca = text[a], cb = text[b];
+        bool ok = ca < cb;
+        if (ca == cb) {
+            const bool ea = ends_at(bits, a + 1), eb = ends_at(bits, b + 1);
+            ok = ea ? (!eb || a < b) : (!eb && ISA[a + 1] < ISA[b + 1]);        // (neither ends: a + 1 < n and b + 1 < n)
+        }
+        if (!ok) ++e1;
+        if (LCP) {
+            const uint64_t l = LCP[i], cap = l < n ? l + 1 : n;
+            const uint64_t room = min(to_string_end(bits, n, a, cap), to_string_end(bits, n, b, cap)), lim = min(l, room);
+            uint64_t h = 0;
+            while (h < lim && text[a + h] == text[b + h]) ++h;
+            const bool more = h == l && room > l && text[a + h] == text[b + h];
+            if (h != l || more) ++e2;
+        }
+    }
+    e0 = wave_reduce<uint32_t>(e0, OpSum()); e1 = wave_reduce<uint32_t>(e1, OpSum()); e2 = wave_reduce<uint32_t>(e2, OpSum());
+    if (lane_id() == 0) {
+        if (e0) atomicAdd(&err[0], (unsigned long long)e0);
+        if (e1) atomicAdd(&err[1], (unsigned long long)e1);
+        if (e2) atomicAdd(&err[2], (unsigned long long)e2);
+    }
+}
+
+template <typename T>
+int check_gsa_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* d_off, uint64_t m, const T* sa, const T* isa, const T* lcp,
+                  uint64_t* errors) {
+    if (!c || !text || !d_off || !sa || !isa || !errors || n == 0 || m == 0 || m > n) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    PSACX_TRY(ensure_slab(c, 4096));
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->slab);
+    // d[0..3]: the counters, d[4]: malformed offsets (a set that does not cover [0, n) with non-empty strings would send the
+    // bitmap's stores out of bounds)
+    PSACX_HIP(c, hipMemsetAsync(d, 0, 40, c->stream));
+    hipLaunchKernelGGL(check_offsets_kernel<0>, dim3(grid_for(c, m + 1, 256, 8)), dim3(256), 0, c->stream, d_off, m, n, d + 4);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long bad = 0;
+    PSACX_HIP(c, hipMemcpyAsync(&bad, d + 4, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (bad) return PSACX_EINVAL;
+    const uint64_t words = (n >> 5) + 1;
+    uint32_t* bits = nullptr;
+    hipError_t e = hipMalloc((void**)&bits, words * sizeof(uint32_t));
+    if (e != hipSuccess) { c->hip_err = std::string("hipMalloc(string ends): ") + hipGetErrorString(e); (void)hipGetLastError(); return PSACX_ENOMEM; }
+    int rc = PSACX_OK;
+    auto step = [&](hipError_t r) { if (rc == PSACX_OK && r != hipSuccess) { c->hip_err = hipGetErrorString(r); (void)hipGetLastError(); rc = PSACX_EHIP; } };
+    step(hipMemsetAsync(bits, 0, words * sizeof(uint32_t), c->stream));
+    if (rc == PSACX_OK) {
+        hipLaunchKernelGGL(string_ends_bitmap_kernel, dim3(grid_for(c, m + 1, 256, 8)), dim3(256), 0, c->stream, d_off, m, bits);
+        step(hipGetLastError());
+    }
+    if (rc == PSACX_OK) {
+        hipLaunchKernelGGL((check_gsa_kernel<T>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, text, n, (const uint32_t*)bits, sa, isa, lcp, d);
+        step(hipGetLastError());
+    }
+    if (rc == PSACX_OK) step(hipMemcpyAsync(errors, d, 32, hipMemcpyDeviceToHost, c->stream));
+    step(hipStreamSynchronize(c->stream));
+    (void)hipFree(bits);
+    return rc;
+}
+
 // Synthetic benchmark texts of SURVEY.md section 8(d), generated where they are used: character g of
 // DNA(n, seed) is "ACGT"[z & 3], of ASCII128(n, seed) z & 127, with z the g-th output (counting from 1) of
 // splitmix64 started at `seed`; TANDEM repeats the first `period` characters of DNA(period, seed); MUTATED is that repeat with one
@@ -111,5 +215,10 @@ int check_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa
 int check_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* isa, const uint64_t* lcp, uint64_t* e) {
     return check_dev<uint64_t>(c, t, n, sa, isa, lcp, e);
 }
+
+int check_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* isa,
+                      const uint32_t* lcp, uint64_t* e) { return check_gsa_dev<uint32_t>(c, t, n, off, m, sa, isa, lcp, e); }
+int check_gsa_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* isa,
+                      const uint64_t* lcp, uint64_t* e) { return check_gsa_dev<uint64_t>(c, t, n, off, m, sa, isa, lcp, e); }
 
 } // namespace psacx

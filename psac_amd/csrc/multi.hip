@@ -34,14 +34,14 @@ int run_dev(psacx_multi* g, const uint8_t* const* d_text, const uint64_t* m, uin
 
 template <typename T>
 int check_dev(psacx_multi* g, const uint8_t* const* d_text, const uint64_t* m, const T* const* sa, const T* const* isa, const T* const* lcp,
-              uint64_t errors[4]) {
+              uint64_t errors[4], const uint64_t* str_off = nullptr, uint64_t nstr = 0) {
     if (!g || !d_text || !m || !sa || !isa || !errors) return PSACX_EINVAL;
     g->err.clear();
     MultiRun<T> run(g);
     std::vector<const uint8_t*> t(g->nlocal); std::vector<uint64_t> mm(g->nlocal);
     std::vector<T*> a(g->nlocal), b(g->nlocal), c(g->nlocal, nullptr);
     for (int i = 0; i < g->nlocal; ++i) { t[i] = d_text[i]; mm[i] = m[i]; a[i] = const_cast<T*>(sa[i]); b[i] = const_cast<T*>(isa[i]); if (lcp) c[i] = const_cast<T*>(lcp[i]); }
-    return run.check(t, mm, a, b, c, lcp != nullptr, errors);
+    return run.check(t, mm, a, b, c, lcp != nullptr, errors, str_off, nstr);
 }
 
 template <typename T>
@@ -400,6 +400,15 @@ int psacx_multi_check_dev_u32(psacx_multi* g, const uint8_t* const* t, const uin
                               const uint32_t* const* lcp, uint64_t errors[4]) { return check_dev<uint32_t>(g, t, m, sa, isa, lcp, errors); }
 int psacx_multi_check_dev_u64(psacx_multi* g, const uint8_t* const* t, const uint64_t* m, const uint64_t* const* sa, const uint64_t* const* isa,
                               const uint64_t* const* lcp, uint64_t errors[4]) { return check_dev<uint64_t>(g, t, m, sa, isa, lcp, errors); }
+
+int psacx_multi_check_gsa_dev_u32(psacx_multi* g, const uint8_t* const* t, const uint64_t* m, const uint64_t* off, uint64_t nstr, const uint32_t* const* sa,
+                                  const uint32_t* const* isa, const uint32_t* const* lcp, uint64_t errors[4]) {
+    return off ? check_dev<uint32_t>(g, t, m, sa, isa, lcp, errors, off, nstr) : PSACX_EINVAL;
+}
+int psacx_multi_check_gsa_dev_u64(psacx_multi* g, const uint8_t* const* t, const uint64_t* m, const uint64_t* off, uint64_t nstr, const uint64_t* const* sa,
+                                  const uint64_t* const* isa, const uint64_t* const* lcp, uint64_t errors[4]) {
+    return off ? check_dev<uint64_t>(g, t, m, sa, isa, lcp, errors, off, nstr) : PSACX_EINVAL;
+}
 
 int psacx_multi_construct_lc_u32(psacx_multi* g, const uint8_t* text, uint64_t n, uint32_t k, uint32_t flags, uint32_t* SA, uint32_t* ISA,
                                  uint32_t* LCP, uint8_t* Lc) { return Lc ? run_host<uint32_t>(g, text, n, k, flags, SA, ISA, LCP, Lc) : PSACX_EINVAL; }

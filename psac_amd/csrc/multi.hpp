@@ -2116,7 +2116,8 @@ struct MultiRun {
     int ansv(const std::vector<const T*>& block, const std::vector<uint64_t>& m_local, int left_type, int right_type, uint64_t nonsv, const std::vector<uint64_t*>& out_left, const std::vector<uint64_t*>& out_right);
     int left_chars(const std::vector<const uint8_t*>& text, const std::vector<uint64_t>& m_local, const std::vector<T*>& d_sa, const std::vector<T*>& d_lcp, const std::vector<uint8_t*>& d_lc);
     int suffix_tree(const std::vector<const uint8_t*>& text, const std::vector<uint64_t>& m_local, const std::vector<T*>& d_sa, const std::vector<T*>& d_lcp, const std::vector<unsigned long long*>* d_nodes, uint32_t* sigma);
-    int check(const std::vector<const uint8_t*>& text, const std::vector<uint64_t>& m_local, const std::vector<T*>& d_sa, const std::vector<T*>& d_isa, const std::vector<T*>& d_lcp, bool with_lcp, uint64_t errors[4]);
+    int check(const std::vector<const uint8_t*>& text, const std::vector<uint64_t>& m_local, const std::vector<T*>& d_sa, const std::vector<T*>& d_isa, const std::vector<T*>& d_lcp, bool with_lcp, uint64_t errors[4],
+              const uint64_t* str_off = nullptr, uint64_t nstr = 0);
 
     // boundary bucket ids of every block, the list of positions that still share a bucket (suffix_array.hpp:925-965)
     // and the global counters.  ids == nullptr: first round (ids = Bsa, every position is a list entry).

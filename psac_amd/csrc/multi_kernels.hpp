@@ -131,7 +131,11 @@ __global__ void ansv_finish_kernel(const T* __restrict__ first, const T* __restr
 // long, else 1 + min(LCP[ISA[SA[p-1]+1] + 1 .. ISA[SA[p]+1]]).  The two ranks are values fetched from the ISA under test: a
 // question is asked only when both are < n (na < nb < n), so no range leaves the LCP array whatever the ISA holds; an entry
 // whose ranks pass the order test with nb >= n has no recurrence to satisfy and is counted in err[2] by the verdict.
-template <typename T>
+// GSA (string sets, psacx_multi_check_gsa_dev_*): a character word also carries bit 8 = "the suffix ends after this character" (the
+// next position starts a string or is n; set_string_ends_kernel), so S[SA[p]] arrives with what the order rule and the base case of the
+// recurrence ask about the string ends.  Equal one-character suffixes must stand in text order; the value is 1 where either suffix is
+// one character long.
+template <typename T, bool GSA = false>
 __global__ void check_queries_kernel(const T* __restrict__ SA, const T* __restrict__ ch, const T* __restrict__ nx, uint64_t cnt, uint64_t n,
                                      int has_prev, T prev_sa, T prev_ch, T prev_nx, T* __restrict__ qlo, T* __restrict__ qhi) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -140,12 +144,14 @@ __global__ void check_queries_kernel(const T* __restrict__ SA, const T* __restri
         if (i > 0 || has_prev) {
             const uint64_t a = i ? (uint64_t)SA[i - 1] : (uint64_t)prev_sa, b = SA[i];
             const T ca = i ? ch[i - 1] : prev_ch, na = i ? nx[i - 1] : prev_nx;
-            if (a < n && b < n && ca == ch[i] && a + 1 < n && b + 1 < n && na < nx[i] && (uint64_t)nx[i] < n) { lo = (T)(na + 1); hi = (T)(nx[i] + 1); }
+            if (GSA) {
+                if (a < n && b < n && ca == ch[i] && !(((unsigned)ca >> 8) & 1u) && na < nx[i] && (uint64_t)nx[i] < n) { lo = (T)(na + 1); hi = (T)(nx[i] + 1); }
+            } else if (a < n && b < n && ca == ch[i] && a + 1 < n && b + 1 < n && na < nx[i] && (uint64_t)nx[i] < n) { lo = (T)(na + 1); hi = (T)(nx[i] + 1); }
         }
         qlo[i] = lo; qhi[i] = hi;
     }
 }
-template <typename T>
+template <typename T, bool GSA = false>
 __global__ void check_verdict_kernel(const T* __restrict__ SA, const T* __restrict__ back, const T* __restrict__ ch, const T* __restrict__ nx,
                                      const T* __restrict__ LCP, const T* __restrict__ mins, uint64_t cnt, uint64_t off, uint64_t n,
                                      int has_prev, T prev_sa, T prev_ch, T prev_nx, unsigned long long* __restrict__ err) {
@@ -158,15 +164,17 @@ __global__ void check_verdict_kernel(const T* __restrict__ SA, const T* __restri
         if (i == 0 && !has_prev) continue;
         const uint64_t a = i ? (uint64_t)SA[i - 1] : (uint64_t)prev_sa;
         if (a >= n) continue;                               // counted where it lives
-        const T ca = i ? ch[i - 1] : prev_ch, cb = ch[i];
+        const T wa = i ? ch[i - 1] : prev_ch, wb = ch[i];
+        const T ca = GSA ? (T)(wa & 255) : wa, cb = GSA ? (T)(wb & 255) : wb;
+        const bool ea = GSA ? (((unsigned)wa >> 8) & 1u) != 0 : a + 1 == n, eb = GSA ? (((unsigned)wb >> 8) & 1u) != 0 : b + 1 >= n;
         const T na = i ? nx[i - 1] : prev_nx, nb = nx[i];
         bool ok = ca < cb;
-        if (ca == cb) ok = (a + 1 == n) || (b + 1 < n && na < nb);
+        if (ca == cb) ok = GSA ? (ea ? (!eb || a < b) : (!eb && na < nb)) : (ea || (!eb && na < nb));
         if (!ok) { ++e1; continue; }
         if (LCP) {
             uint64_t want;
             if (ca != cb) want = 0;
-            else if (a + 1 == n) want = 1;
+            else if (ea || (GSA && eb)) want = 1;
             else if ((uint64_t)nb >= n) { ++e2; continue; }     // a rank that is none: no question was asked (check_queries_kernel)
             else want = 1 + (uint64_t)mins[i];
             if ((uint64_t)LCP[i] != want) ++e2;
@@ -177,6 +185,16 @@ __global__ void check_verdict_kernel(const T* __restrict__ SA, const T* __restri
         if (e0) atomicAdd(&err[0], (unsigned long long)e0);
         if (e1) atomicAdd(&err[1], (unsigned long long)e1);
         if (e2) atomicAdd(&err[2], (unsigned long long)e2);
+    }
+}
+// ends[j]: the global offsets of the strings that end inside this block's positions (first .. first + m], each > first: the
+// character word of the position before gets bit 8.  Distinct offsets, distinct words: plain stores.
+template <typename T>
+__global__ void set_string_ends_kernel(const uint64_t* __restrict__ ends, uint64_t cnt, uint64_t first, T* __restrict__ wide) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < cnt; j += stride) {
+        const uint64_t q = ends[j] - 1 - first;
+        wide[q] = (T)(wide[q] | (T)256);
     }
 }
 

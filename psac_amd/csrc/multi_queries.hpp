@@ -483,9 +483,13 @@ int MultiRun<T>::suffix_tree(const std::vector<const uint8_t*>& text, const std:
 // ISA[SA[i]], S[SA[i]], ISA[SA[i]+1]), plus the LCP array through its recurrence
 //   LCP[i] = 0 | 1 | 1 + min(LCP[ISA[SA[i-1]+1]+1 .. ISA[SA[i]+1]])      (range minima: bulk_rmq_v2)
 // which has the true LCP array as its only solution.  errors[0..3] as psacx_check_dev_*, summed over all ranks.
+// str_off / nstr: the arrays are those of a string set (psacx_multi_check_gsa_dev_*; the nstr + 1 global offsets, on the host as the
+// construction takes them).  Suffixes end with their strings, equal suffixes stand in text order: the string ends ride in bit 8 of the
+// text words (multi_kernels.hpp), every exchange stays as it is.
 template <typename T>
 int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vector<uint64_t>& m_local, const std::vector<T*>& d_sa,
-          const std::vector<T*>& d_isa, const std::vector<T*>& d_lcp, bool with_lcp, uint64_t errors[4]) {
+          const std::vector<T*>& d_isa, const std::vector<T*>& d_lcp, bool with_lcp, uint64_t errors[4], const uint64_t* str_off, uint64_t nstr) {
+    const bool gsa = str_off != nullptr;
     want_lcp = with_lcp;
     S.resize(L);
     for (int i = 0; i < L; ++i) { (void)hipSetDevice(ctx(i)->device); pool_flush(ctx(i)); }     // the checker wants different sizes than the construction left cached
@@ -520,6 +524,10 @@ int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vecto
             if (sizes[r] != n / P + ((uint64_t)r < n % P ? 1 : 0)) { g->err = "The input string must be equally block decomposed accross all MPI processes."; return PSACX_EINVAL; }
         for (int i = 0; i < L; ++i) { S[i].off = offs[rank(i)]; ctx(i)->pool_cache_limit = 0; }
         if (n == 0) return PSACX_EINVAL;
+        if (gsa) {      // m non-empty strings covering [0, n), as the construction asks (stringset.hpp:53-72)
+            if (nstr == 0 || nstr > n || str_off[0] != 0 || str_off[nstr] != n) { g->err = "string set: the offsets do not cover the text"; return PSACX_EINVAL; }
+            for (uint64_t t = 0; t < nstr; ++t) if (str_off[t + 1] <= str_off[t]) { g->err = "string set: empty string or offsets not ascending"; return PSACX_EINVAL; }
+        }
     }
     // the text as index words, once (S[SA[i]] travels through the same exchanges as the indices)
     std::vector<DBuf<T>> wide(L);
@@ -528,6 +536,19 @@ int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vecto
         MG_OP(g, c, wide[i].alloc(c, S[i].m));
         OP_PROLOGUE(c);
         SIMPLE_LAUNCH(c, (widen_text_kernel<T>), S[i].m, text[i], S[i].m, wide[i].p);
+        if (gsa && S[i].m) {
+            // the strings that end at a position of this block: offsets in (off, off + m], a slice of the ascending array
+            const uint64_t* lo = std::upper_bound(str_off, str_off + nstr + 1, S[i].off);
+            const uint64_t* hi = std::upper_bound(lo, str_off + nstr + 1, S[i].off + S[i].m);
+            const uint64_t cnt = (uint64_t)(hi - lo);
+            if (cnt) {
+                DBuf<uint64_t> ends; MG_OP(g, c, ends.alloc(c, cnt));
+                MG_HIP(g, hipSetDevice(c->device));
+                MG_HIP(g, hipMemcpyAsync(ends.p, lo, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+                SIMPLE_LAUNCH(c, (set_string_ends_kernel<T>), cnt, (const uint64_t*)ends.p, cnt, S[i].off, wide[i].p);
+                MG_HIP(g, hipStreamSynchronize(c->stream));        // (the offsets leave with this scope)
+            }
+        }
         return PSACX_OK;
     }));
     // (SA, S[SA], ISA[SA + 1]) of a range of SA positions of every rank
@@ -590,8 +611,10 @@ int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vecto
                 psacx_ctx* c = ctx(i);
                 MG_OP(g, c, qlo[i].alloc(c, cnt[i])); MG_OP(g, c, qhi[i].alloc(c, cnt[i]));
                 OP_PROLOGUE(c);
-                SIMPLE_LAUNCH(c, (check_queries_kernel<T>), cnt[i], S[i].SA + from[i], ch[i].p, nx[i].p, cnt[i], n, bd[i].has_prev, (T)bd[i].prev[0],
-                              (T)bd[i].prev[1], (T)bd[i].prev[2], qlo[i].p, qhi[i].p);
+                if (gsa) SIMPLE_LAUNCH(c, (check_queries_kernel<T, true>), cnt[i], S[i].SA + from[i], ch[i].p, nx[i].p, cnt[i], n, bd[i].has_prev, (T)bd[i].prev[0],
+                                       (T)bd[i].prev[1], (T)bd[i].prev[2], qlo[i].p, qhi[i].p);
+                else SIMPLE_LAUNCH(c, (check_queries_kernel<T>), cnt[i], S[i].SA + from[i], ch[i].p, nx[i].p, cnt[i], n, bd[i].has_prev, (T)bd[i].prev[0],
+                                   (T)bd[i].prev[1], (T)bd[i].prev[2], qlo[i].p, qhi[i].p);
                 lo[i] = qlo[i].p; hi[i] = qhi[i].p;
                 return PSACX_OK;
             }));
@@ -603,9 +626,12 @@ int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vecto
             MG_HIP(g, hipSetDevice(c->device));
             MG_HIP(g, hipMemsetAsync(e.p, 0, 32, c->stream));
             OP_PROLOGUE(c);
-            SIMPLE_LAUNCH(c, (check_verdict_kernel<T>), cnt[i], S[i].SA + from[i], back[i].p, ch[i].p, nx[i].p, with_lcp ? (const T*)(S[i].LCP + from[i]) : (const T*)nullptr,
-                          with_lcp ? (const T*)mins[i].p : (const T*)nullptr, cnt[i], S[i].off + from[i], n, bd[i].has_prev, (T)bd[i].prev[0], (T)bd[i].prev[1],
-                          (T)bd[i].prev[2], e.p);
+            const T* lcp_i = with_lcp ? (const T*)(S[i].LCP + from[i]) : (const T*)nullptr;
+            const T* mins_i = with_lcp ? (const T*)mins[i].p : (const T*)nullptr;
+            if (gsa) SIMPLE_LAUNCH(c, (check_verdict_kernel<T, true>), cnt[i], S[i].SA + from[i], back[i].p, ch[i].p, nx[i].p, lcp_i, mins_i, cnt[i], S[i].off + from[i], n,
+                                   bd[i].has_prev, (T)bd[i].prev[0], (T)bd[i].prev[1], (T)bd[i].prev[2], e.p);
+            else SIMPLE_LAUNCH(c, (check_verdict_kernel<T>), cnt[i], S[i].SA + from[i], back[i].p, ch[i].p, nx[i].p, lcp_i, mins_i, cnt[i], S[i].off + from[i], n,
+                               bd[i].has_prev, (T)bd[i].prev[0], (T)bd[i].prev[1], (T)bd[i].prev[2], e.p);
             MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, e.p, 32, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
             const uint64_t* h = reinterpret_cast<const uint64_t*>(c->pinned + 32768);

@@ -18,6 +18,8 @@ int pair_sort_dev_u32(psacx_ctx*, uint32_t*, uint32_t*, uint32_t*, uint64_t, uin
 int pair_sort_dev_u64(psacx_ctx*, uint64_t*, uint64_t*, uint64_t*, uint64_t, uint32_t);
 int check_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*);
 int check_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*);
+int check_gsa_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*);
+int check_gsa_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*);
 int synth_text_dev(psacx_ctx*, uint8_t*, uint64_t, uint64_t, int, uint64_t, uint64_t);
 int suffix_tree_host_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, const uint32_t*, uint64_t*, uint32_t*);
 int suffix_tree_host_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t*, uint32_t*);
@@ -222,6 +224,11 @@ int psacx_check_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32
 int psacx_check_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* isa, const uint64_t* lcp, uint64_t* e) {
     return check_dev_u64(c, t, n, sa, isa, lcp, e);
 }
+
+int psacx_check_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* isa,
+                            const uint32_t* lcp, uint64_t* e) { return check_gsa_dev_u32(c, t, n, off, m, sa, isa, lcp, e); }
+int psacx_check_gsa_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* isa,
+                            const uint64_t* lcp, uint64_t* e) { return check_gsa_dev_u64(c, t, n, off, m, sa, isa, lcp, e); }
 
 int psacx_synth_text_dev(psacx_ctx* c, uint8_t* d_text, uint64_t n, uint64_t first, int kind, uint64_t seed, uint64_t period) {
     return synth_text_dev(c, d_text, n, first, kind, seed, period);

@@ -191,6 +191,20 @@ class MultiContext(object):
         self.check(fn(self.handle, vp(*d_text), mm, vp(*d_sa), vp(*d_isa), vp(*d_lcp) if d_lcp is not None else None, err))
         return list(err)
 
+    def check_gsa_device(self, d_text, m_local, offsets, d_sa, d_isa, d_lcp, index_bits):
+        """The distributed checker for a generalized suffix array (psacx_multi_check_gsa_dev_*): offsets are the global
+        string offsets (host, one more than there are strings), the blocks as check_device takes them."""
+        self._pre()
+        L = self.nlocal
+        vp = C.c_void_p * L
+        mm = (C.c_uint64 * L)(*[int(x) for x in m_local])
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        err = (C.c_uint64 * 4)()
+        fn = getattr(self._lib, "psacx_multi_check_gsa_dev_u%d" % index_bits)
+        self.check(fn(self.handle, vp(*d_text), mm, off.ctypes.data_as(C.c_void_p), int(off.size) - 1, vp(*d_sa), vp(*d_isa),
+                      vp(*d_lcp) if d_lcp is not None else None, err))
+        return list(err)
+
     def left_chars_device(self, d_text, m, d_sa, d_lcp, d_lc, index_bits):
         """Left-branching characters Lc[i] = S[SA[i-1] + LCP[i]] of block-distributed results resident in HBM
         (suffix_array.hpp:211-212); d_lc[i] receives m[i] bytes."""

@@ -265,6 +265,17 @@ def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
     return list(err)
 
 
+def check_gsa_device(ctx, d_text, n, d_off, m, d_sa, d_isa, d_lcp, index_bits):
+    """The same for a generalized suffix array resident in HBM (gl_check_gsa, src/gsac.cpp:85-135): d_off holds the
+    m + 1 string offsets on the device, as psacx_construct_gsa_dev_* takes them.  Returns the four error counters of
+    psacx_check_gsa_dev_*; all zero means correct, equal suffixes in text order included."""
+    err = (C.c_uint64 * 4)()
+    fn = getattr(ctx._lib, "psacx_check_gsa_dev_u%d" % index_bits)
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_off), int(m), C.c_void_p(d_sa), C.c_void_p(d_isa),
+                 C.c_void_p(d_lcp) if d_lcp else None, err))
+    return list(err)
+
+
 def ansv_device(ctx, d_in, n, d_left, d_right, index_bits, left_type=NEAREST_SM, right_type=NEAREST_SM, nonsv=0):
     """ansv<T, left_type, right_type> with the input (n index_t) and both results (n uint64 each) resident in
     HBM, e.g. over the LCP array construct_device left there (suffix_tree.hpp:62)."""

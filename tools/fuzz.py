@@ -81,7 +81,16 @@ while time.time() < t_end:
             raise
         ref = O.construct_ss(strings, bits=bits)
         ok = np.array_equal(got.local_SA, ref["SA"]) and np.array_equal(got.local_B, ref["ISA"]) and np.array_equal(got.local_LCP, ref["LCP"])
-        desc += " string set of %d" % len(strings)
+        # ... and the device checker must call the very arrays the oracle confirms correct (psacx_check_gsa_dev_*)
+        st, soff = psac_amd.parse_stringset(strings)
+        dbuf = [ctx.alloc(max(a.nbytes, 1)) for a in (st, soff, got.local_SA, got.local_B, got.local_LCP)]
+        for p, a in zip(dbuf, (st, soff, got.local_SA, got.local_B, got.local_LCP)):
+            ctx.h2d(p, a)
+        verdict = psac_amd.check_gsa_device(ctx, dbuf[0], st.size, dbuf[1], soff.size - 1, dbuf[2], dbuf[3], dbuf[4], bits)
+        for p in dbuf:
+            ctx.free(p)
+        ok = ok and not any(verdict)
+        desc += " string set of %d, device verdict %s" % (len(strings), verdict)
     elif n == 1:
         got = psac_amd.SuffixArray(index_bits=bits, lcp=True, ctx=ctx); got.construct(text)
         ok = got.local_SA.tolist() == [0] and got.local_LCP.tolist() == [0]
