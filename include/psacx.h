@@ -261,7 +261,11 @@ int psacx_synth_text_dev(psacx_ctx* ctx, uint8_t* d_text, uint64_t n, uint64_t f
  * Replaces idxsort_vectors(vec1, vec2, comm) (idxsort.hpp:23-83) at one rank:
  * sorts records (b1[i], b2[i], i) by (b1, b2); on return b1/b2 hold the sorted
  * keys and idx the permutation.  Device pointers, n entries each.  key_bits =
- * number of significant low bits in each key word (0 = all). */
+ * number of significant low bits in each key word (0, or more than the word has = all);
+ * the keys must be zero above them (a pass takes a whole 8-bit digit).  The sort is
+ * stable: equal pairs keep index order.
+ * psacx_get_stats then reports in rounds[0] the radix passes run (sort_passes) and the
+ * 8-bit digits of the key_bits found constant and skipped (sort_passes_skipped). */
 int psacx_pair_sort_dev_u32(psacx_ctx* ctx, uint32_t* d_b1, uint32_t* d_b2, uint32_t* d_idx,
                             uint64_t n, uint32_t key_bits);
 int psacx_pair_sort_dev_u64(psacx_ctx* ctx, uint64_t* d_b1, uint64_t* d_b2, uint64_t* d_idx,
@@ -271,7 +275,8 @@ int psacx_pair_sort_dev_u64(psacx_ctx* ctx, uint64_t* d_b1, uint64_t* d_b2, uint
  * Replaces ansv<T,left_type,right_type,global_indexing>(in, left, right, comm)
  * (ansv.hpp:2042-2051) at one rank.  type: 0 nearest_sm, 1 nearest_eq,
  * 2 furthest_eq (ansv_common.hpp:20-22).  Results are global indices, `nonsv`
- * where no such element exists.  Host pointers. */
+ * where no such element exists.  Any value of T is a legal input, its largest included,
+ * and any 64-bit word a legal nonsv.  Host pointers. */
 int psacx_ansv_u32(psacx_ctx* ctx, const uint32_t* in, uint64_t n, int left_type, int right_type,
                    uint64_t nonsv, uint64_t* left_nsv, uint64_t* right_nsv);
 int psacx_ansv_u64(psacx_ctx* ctx, const uint64_t* in, uint64_t n, int left_type, int right_type,

@@ -174,6 +174,44 @@ def test_ansv_definitions():
                 assert fe[i] == e_fe
 
 
+def ansv_by_definition(values, left, kind, nonsv):
+    # ansv_common.hpp:20-22 word for word, on Python integers: nearest j with v[j] < v[i] (kind 0) or v[j] <= v[i] (1, 2); furthest_eq (2) then
+    # walks on from j through the values equal to v[j] as long as nothing smaller lies between
+    v = [int(x) for x in values]
+    n = len(v)
+    out = [nonsv] * n
+    for i in range(n):
+        beyond = (lambda a: range(a - 1, -1, -1)) if left else (lambda a: range(a + 1, n))
+        j = next((k for k in beyond(i) if (v[k] < v[i] if kind == 0 else v[k] <= v[i])), None)
+        if j is None:
+            continue
+        if kind == 2:
+            for k in beyond(j):
+                if v[k] < v[j]:
+                    break
+                if v[k] == v[j]:
+                    j = k
+        out[i] = j
+    return np.array(out, dtype=np.uint64)
+
+
+@pytest.mark.parametrize("dtype", [np.uint32, np.uint64])
+def test_ansv_oracle_at_the_top_of_the_value_range(dtype):
+    # the oracle is the reference of tests/test_gpu_kernel_edges.py on values up to 2^bits - 1 (what the kernels pad with), values that differ in
+    # one 32-bit half only, and nonsv = 2^64 - 2: here against the definition, before the GPU tests lean on it
+    shapes = ["top3", "max", "falling", "rising"] + (list(inputs.ANSV_EDGE_SHAPES_64) if dtype == np.uint64 else [])
+    for shape in shapes:
+        for n in (1, 2, 17, 64, 300):
+            v = inputs.ansv_edge_values(shape, n, dtype, seed=3)
+            assert v.dtype == dtype and v.size == n
+            if shape in ("max", "falling", "rising"):
+                assert int(v.max()) == np.iinfo(dtype).max
+            for nonsv in (2**64 - 1, 2**64 - 2):
+                for left in (True, False):
+                    for kind in (0, 1, 2):
+                        assert np.array_equal(O.ansv(v, left, kind, nonsv), ansv_by_definition(v, left, kind, nonsv)), (shape, n, nonsv, left, kind)
+
+
 def test_suffix_tree_mississippi_table():
     # test/test_suffixtree.cpp:68-83
     m = KAT["mississippi"]
