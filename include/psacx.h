@@ -296,6 +296,42 @@ int psacx_suffix_tree_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const
                           const uint32_t* LCP, uint64_t* nodes, uint32_t* sigma);
 int psacx_suffix_tree_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* SA,
                           const uint64_t* LCP, uint64_t* nodes, uint32_t* sigma);
+/* The same with every array resident in HBM (the arrays psacx_construct_dev_* left there): d_nodes receives the
+ * n x (sigma + 1) table, which never visits the host; no input is written.  d_nodes == NULL: only *sigma is computed
+ * (d_SA / d_LCP may be NULL then).  The alphabet comes from a histogram taken on the device.  edges (may be NULL)
+ * receives the number of records written = nonzero cells = n + internal nodes, counted by the kernel that writes them.
+ * d_LCP[0] is expected to be 0, as psacx_construct_dev_* stores it.  Another value there never serves as an index or as a depth: a
+ * search that finds nothing, or finds entry 0, means parent 0 at depth 0; the table is that of LCP[0] = 0 provided the stored value
+ * equals no other entry. */
+int psacx_suffix_tree_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_SA,
+                              const uint32_t* d_LCP, uint64_t* d_nodes, uint32_t* sigma, uint64_t* edges);
+int psacx_suffix_tree_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
+                              const uint64_t* d_LCP, uint64_t* d_nodes, uint32_t* sigma, uint64_t* edges);
+
+/* Is d_nodes the node table of the text / SA / LCP as given?  (The reference's check_suffix_tree.hpp is a sequential
+ * host walk; this one runs in HBM.)  SA and LCP themselves are NOT verified here: that is psacx_check_dev_*'s job, and
+ * a table is "correct" relative to whatever arrays it is handed.  It shares no code and no intermediate array with the
+ * builder (no ANSV): the table is restated as follows.  L = LCP with L[0] read as 0 whatever is stored, row = sigma + 1,
+ * code() = alphabet code (1..sigma in byte order of the characters of d_text).
+ *   head(x)    = the smallest j <= x with L[j] == L[x] and min(L[j..x]) == L[x];
+ *   cell(s, d) = code(text[s + d]) if s < n and d < n - s, else 0 (no wrapping, no out-of-range read);
+ *   leaf record of every i in [0, n): x = i + 1 if i + 1 < n and L[i+1] > L[i], else x = i; id n + i in cell
+ *     (head(x), cell(SA[i], L[x]));
+ *   internal record of every i >= 1 with L[i] > 0 and head(i) == i: l / r = the nearest j < i / j > i with L[j] < L[i]
+ *     (r may not exist); (p, d) = (r, L[r]) if r exists and L[r] > L[l], else (head(l), L[l]); id i in cell
+ *     (p, cell(SA[i], d)).
+ * The correct table holds every record's id in its cell and 0 everywhere else.  Counting rules, total for any input:
+ *  - out[2] = records (leaf + internal) of the arrays as given; out[3] = nonzero cells of the table;
+ *  - a record is matched iff the cell it names holds its id (each record on its own, even if corrupt inputs send two
+ *    records to one cell);
+ *  - out[0] = records not matched; out[1] = out[3] - matched records = nonzero cells no record accounts for (never
+ *    negative: ids are distinct and nonzero);
+ *  - correct <=> out[0] == out[1] == 0.
+ * Table values are only compared, never used as indices.  Workspace: the ctx slab (a min-pyramid over LCP, n / 63 words). */
+int psacx_check_suffix_tree_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_SA,
+                                    const uint32_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
+int psacx_check_suffix_tree_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
+                                    const uint64_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

@@ -4,6 +4,7 @@
 // further) and d_check_sa's idea of a scalable checker (:207-267).  LCP entries are verified by
 // direct character comparison, which is linear in sum(LCP): meant for texts with short repeats.
 #include "engine.hpp"
+#include "nsv.hpp"      // nsv_pyramid_layout only: the suffix-tree checker below must not use the searches declared there
 
 namespace psacx {
 
@@ -158,6 +159,213 @@ int check_gsa_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t*
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Suffix-tree node table: is `nodes` the table of text / SA / LCP as given?  The rules are those of include/psacx.h
+// (psacx_check_suffix_tree_dev_*): head(), the leaf and the internal records are restated there without ANSV, and nothing
+// here is shared with the builder (ansv.hip) but the min-pyramid's shape.  L = LCP with L[0] read as 0: st_at() does that
+// on level 0, and entry 0 of every level above -- the minimum of a group that holds L[0] -- is set to 0 after the build.
+//
+// One wave takes 64 consecutive entries with one coalesced load.  Lane k learns which lanes hold a value < / <= its own
+// (64 broadcasts, two ballots each); every search that ends inside the group is then bit arithmetic on those two masks.  Only
+// a search that leaves the group walks the pyramid, and the whole wave walks with it: one coalesced load and one ballot per level
+// (st_walk; one thread on its own took a load per entry, and the checker spent most of its time waiting for those).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr uint64_t ST_NONE = ~0ull;
+
+template <typename T>
+__device__ __forceinline__ T st_at(const Pyramid<T>& P, int L, uint64_t idx) { return (L == 0 && idx == 0) ? (T)0 : P.lvl[L][idx]; }
+
+template <typename T>
+__global__ void st_first_is_zero_kernel(Pyramid<T> P) {
+    const int L = 1 + (int)threadIdx.x;
+    if (L < P.nlev) P.lvl[L][0] = 0;
+}
+
+// Deliberately NOT nsv_search_wave (nsv.hpp), which it resembles: the checker's verdict must not rest on the code the builder's
+// ANSV uses, so the walk is written a second time here (with L[0] read as 0, the direction a run-time argument and a way to skip the
+// group already searched).  Do not merge.
+// All 64 lanes work on ONE search, its arguments wave-uniform: nearest j < pos (left) or j > pos with L[j] < v (strict) or
+// L[j] <= v; ST_NONE if there is none.  One step looks at a whole 64-entry group with one coalesced load and one ballot.
+// skip: the caller has already looked through the level-0 group of pos.
+template <typename T>
+__device__ uint64_t st_walk_one(const Pyramid<T>& P, uint64_t pos, T v, bool strict, bool skip, bool left) {
+    const unsigned lane = lane_id();
+    uint64_t p = pos, j = 0;
+    int L = 0;
+    if (skip) {
+        if (P.nlev < 2) return ST_NONE;              // one group is the whole array
+        p >>= 6; L = 1;
+    }
+    for (;;) {                                      // upwards: the rest of p's group on every level
+        const uint64_t len = P.len[L], g0 = p & ~63ull, idx = g0 + lane;
+        const bool inr = idx < len && (left ? idx < p : idx > p);
+        const T x = inr ? st_at(P, L, idx) : (T)0;
+        const uint64_t m = __ballot(inr && (strict ? x < v : x <= v));
+        if (m) { j = g0 + (uint64_t)(left ? 63 - __builtin_clzll(m) : __builtin_ctzll(m)); break; }
+        if (left ? g0 == 0 : g0 + 64 >= len) return ST_NONE;       // (the top level is one group, so L stays below nlev)
+        p >>= 6; ++L;
+    }
+    while (L > 0) {                                 // downwards: the nearest qualifying child, which exists because its minimum qualified
+        --L;
+        const uint64_t lo = j << 6, idx = lo + lane;
+        const bool inr = idx < P.len[L];
+        const T x = inr ? st_at(P, L, idx) : (T)0;
+        const uint64_t m = __ballot(inr && (strict ? x < v : x <= v));
+        j = m ? lo + (uint64_t)(left ? 63 - __builtin_clzll(m) : __builtin_ctzll(m)) : lo;
+    }
+    return j;
+}
+
+// The searches of the lanes that `want` one, one after the other, each by the whole wave; the others get ST_NONE.  Every lane of the
+// wave must call this (the arguments of a lane that wants nothing are ignored).
+template <typename T>
+__device__ uint64_t st_walk(const Pyramid<T>& P, bool want, uint64_t pos, T v, bool strict, bool skip, bool left) {
+    uint64_t res = ST_NONE;
+    for (uint64_t pending = __ballot(want); pending; pending &= pending - 1) {
+        const int src = __builtin_ctzll(pending);
+        const uint64_t r = st_walk_one<T>(P, shfl<uint64_t>(pos, src), shfl<T>(v, src), strict, skip, left);
+        if ((int)lane_id() == src) res = r;
+    }
+    return res;
+}
+
+__device__ __forceinline__ uint64_t st_cell(const uint8_t* __restrict__ text, uint64_t n, const CodeTable& tab, uint64_t s, uint64_t d) {
+    return (s < n && d < n - s) ? (uint64_t)tab.c[text[s + d]] : 0;
+}
+
+// cnt[0]: records, cnt[1]: records whose cell holds their id
+template <typename T>
+__global__ __launch_bounds__(256) void st_check_kernel(Pyramid<T> P, uint64_t n, const T* __restrict__ SA, const uint8_t* __restrict__ text,
+                                                       CodeTable tab, uint64_t row, const unsigned long long* __restrict__ nodes,
+                                                       unsigned long long* __restrict__ cnt) {
+    const uint64_t wave_id = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) / WAVE;
+    const unsigned lane = lane_id();
+    const uint64_t ngroups = (n + 63) >> 6;
+    const uint64_t below = (1ull << lane) - 1ull;
+    unsigned rec = 0, hit = 0;
+    for (uint64_t g = wave_id; g < ngroups; g += nwaves) {
+        const uint64_t base = g << 6, i = base + lane;
+        const bool in = i < n;
+        const T v = in ? st_at(P, 0, i) : (T)0;
+        uint64_t lt = 0, le = 0;                     // the lanes of this group whose value is < / <= this lane's
+        for (int k = 0; k < WAVE; ++k) {
+            const T vk = shfl<T>(v, k);
+            const uint64_t a = __ballot(in && v < vk), b = __ballot(in && v <= vk);
+            if (lane == (unsigned)k) { lt = a; le = b; }
+        }
+        T nxt = shfl<T>(v, (int)((lane + 1) & 63u));  // L[i + 1]
+        if (lane == 63 && i + 1 < n) nxt = P.lvl[0][i + 1];
+        // l = the nearest smaller value on the left (v > 0: it exists, L[0] reads as 0), head = head(i): inside the group from the
+        // masks, else by the wave (every st_walk below is called by all 64 lanes)
+        uint64_t l = ST_NONE, head = 0;
+        int l_lane = -1;
+        const bool pos_v = in && v > 0;
+        const uint64_t ml = lt & below;
+        if (pos_v && ml) {
+            l_lane = 63 - __builtin_clzll(ml);
+            l = base + (uint64_t)l_lane;
+            head = base + (uint64_t)__builtin_ctzll(le & (~0ull << (l_lane + 1)));      // (never empty: this lane's own bit is in le)
+        }
+        const bool far_l = pos_v && !ml;
+        {
+            const uint64_t wl = st_walk<T>(P, far_l, i, v, true, true, true);
+            const uint64_t wh = st_walk<T>(P, far_l && wl != ST_NONE, wl, v, false, false, false);
+            if (far_l) { l = wl; head = wh == ST_NONE || wh > i ? i : wh; }
+        }
+        const uint64_t head_of_l = shfl<uint64_t>(head, l_lane < 0 ? 0 : l_lane);          // head(l) where l is in the group
+        // ---- the internal node i: r, and head(l) where l lies outside the group
+        const bool node = in && i != 0 && v > 0 && head == i && l != ST_NONE;
+        const T lv = node ? st_at(P, 0, l) : (T)0;
+        const uint64_t mr = lane == 63 ? 0ull : lt & (~0ull << (lane + 1));
+        uint64_t r = node && mr ? base + (uint64_t)__builtin_ctzll(mr) : ST_NONE;
+        {
+            const uint64_t wr = st_walk<T>(P, node && !mr, i, v, true, true, false);
+            if (node && !mr) r = wr;
+        }
+        const T rv = r != ST_NONE ? st_at(P, 0, r) : (T)0;
+        const bool by_r = node && r != ST_NONE && rv > lv;
+        uint64_t hl = l_lane >= 0 ? head_of_l : 0;                                          // head(l); 0 where L[l] == 0
+        {
+            const bool far_h = node && !by_r && l_lane < 0 && lv > 0;
+            const uint64_t s = st_walk<T>(P, far_h, l, lv, true, false, true);
+            const uint64_t h = st_walk<T>(P, far_h && s != ST_NONE, s, lv, false, false, false);
+            if (far_h) hl = s == ST_NONE ? 0 : (h == ST_NONE || h > l ? l : h);              // (l itself qualifies)
+        }
+        if (!in) continue;
+        const uint64_t sa = SA[i];
+        // ---- the leaf n + i
+        {
+            uint64_t p = head, d = v;
+            if (i + 1 < n && nxt > v) { p = i + 1; d = nxt; }
+            ++rec;
+            if (nodes[p * row + st_cell(text, n, tab, sa, d)] == n + i) ++hit;
+        }
+        if (!node) continue;
+        const uint64_t p = by_r ? r : hl, d = by_r ? (uint64_t)rv : (uint64_t)lv;
+        ++rec;
+        if (nodes[p * row + st_cell(text, n, tab, sa, d)] == i) ++hit;
+    }
+    rec = wave_reduce<uint32_t>(rec, OpSum()); hit = wave_reduce<uint32_t>(hit, OpSum());
+    if (lane == 0) {
+        if (rec) atomicAdd(&cnt[0], (unsigned long long)rec);
+        if (hit) atomicAdd(&cnt[1], (unsigned long long)hit);
+    }
+}
+
+// one streaming pass: how many of the m words are not zero (16 bytes per load where the table is aligned for it)
+__global__ void count_nonzero_kernel(const unsigned long long* __restrict__ a, uint64_t m, unsigned long long* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t pairs = (reinterpret_cast<uintptr_t>(a) & 15u) == 0 ? m / 2 : 0;
+    const ulonglong2* a2 = reinterpret_cast<const ulonglong2*>(a);
+    unsigned c = 0;
+    for (uint64_t i = t; i < pairs; i += stride) { const ulonglong2 w = a2[i]; c += (w.x != 0) + (w.y != 0); }
+    for (uint64_t i = pairs * 2 + t; i < m; i += stride) c += a[i] != 0;
+    c = wave_reduce<uint32_t>(c, OpSum());
+    if (lane_id() == 0 && c) atomicAdd(out, (unsigned long long)c);
+}
+
+template <typename T>
+int check_suffix_tree_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const T* sa, const T* lcp, const uint64_t* nodes, uint64_t* out) {
+    if (!c || !text || !sa || !lcp || !nodes || !out || n == 0) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    Pyramid<T> P;
+    unsigned long long* d = nullptr;                 // 256 character counts, then records / matched / nonzero cells
+    auto layout = [&](Arena& a) {
+        d = a.take<unsigned long long>(256 + 4);
+        nsv_pyramid_layout<T>(a, lcp, n, P);
+    };
+    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
+    Arena ar(c->slab);
+    layout(ar);
+    CodeTable tab;
+    uint32_t sigma = 0;
+    PSACX_TRY(tree_alphabet_dev(c, text, n, d, tab, sigma));
+    const uint64_t row = (uint64_t)sigma + 1;
+    unsigned long long* cnt = d + 256;
+    PSACX_HIP(c, hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+    for (int L = 1; L < P.nlev; ++L) {
+        hipLaunchKernelGGL((pyramid_level_kernel<T>), dim3(grid_for(c, P.len[L] * 64, 256, 8)), dim3(256), 0, c->stream,
+                           P.lvl[L - 1], P.len[L - 1], P.lvl[L], P.len[L]);
+        PSACX_HIP(c, hipGetLastError());
+    }
+    if (P.nlev > 1) {
+        hipLaunchKernelGGL((st_first_is_zero_kernel<T>), dim3(1), dim3(64), 0, c->stream, P);
+        PSACX_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL((st_check_kernel<T>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, P, n, sa, text, tab, row,
+                       reinterpret_cast<const unsigned long long*>(nodes), cnt);
+    PSACX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(count_nonzero_kernel, dim3(grid_for(c, n * row / 2 + 1, 256, 16)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const unsigned long long*>(nodes), n * row, cnt + 2);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    PSACX_HIP(c, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = h[0] - h[1]; out[1] = h[2] - h[1]; out[2] = h[0]; out[3] = h[2];
+    return PSACX_OK;
+}
+
 // Synthetic benchmark texts of SURVEY.md section 8(d), generated where they are used: character g of
 // DNA(n, seed) is "ACGT"[z & 3], of ASCII128(n, seed) z & 127, with z the g-th output (counting from 1) of
 // splitmix64 started at `seed`; TANDEM repeats the first `period` characters of DNA(period, seed); MUTATED is that repeat with one
@@ -214,6 +422,13 @@ int check_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa
 }
 int check_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* isa, const uint64_t* lcp, uint64_t* e) {
     return check_dev<uint64_t>(c, t, n, sa, isa, lcp, e);
+}
+
+int check_suffix_tree_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, const uint32_t* lcp, const uint64_t* nodes, uint64_t* o) {
+    return check_suffix_tree_dev<uint32_t>(c, t, n, sa, lcp, nodes, o);
+}
+int check_suffix_tree_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* lcp, const uint64_t* nodes, uint64_t* o) {
+    return check_suffix_tree_dev<uint64_t>(c, t, n, sa, lcp, nodes, o);
 }
 
 int check_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* isa,

@@ -138,22 +138,6 @@ inline int ensure_pinned(psacx_ctx* c, size_t bytes) {
     return PSACX_OK;
 }
 
-// alphabet.hpp:147-164 on the host from the device histogram
-// tab gets codes 0..sigma-1 in byte order (the packed sort key needs no end-marker code);
-// bits is psac's bits_per_char = ceil(log2(sigma + 1)), bits_packed = max(1, ceil(log2(sigma))).
-inline void build_alphabet(const unsigned long long* hist, CodeTable& tab, uint32_t& sigma, uint32_t& bits,
-                           uint32_t& bits_packed) {
-    uint16_t next = 0;
-    for (int ch = 0; ch < 256; ++ch) tab.c[ch] = hist[ch] ? next++ : (uint16_t)0;
-    sigma = next;
-    uint32_t b = 0;
-    while ((1u << b) < sigma + 1u) ++b;          // ceil(log2(sigma + 1))
-    bits = b;
-    b = 0;
-    while ((1u << b) < sigma) ++b;               // ceil(log2(sigma))
-    bits_packed = b ? b : 1;
-}
-
 // kmer.hpp:26-40 for a single rank
 inline uint32_t choose_k(uint32_t word_bits, uint32_t l, uint64_t n, uint32_t k) {
     const uint32_t max_k = word_bits / l;

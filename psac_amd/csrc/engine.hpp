@@ -555,6 +555,43 @@ inline int grid_for(const psacx_ctx* c, uint64_t work_items, int block, int per_
     return (int)std::min<uint64_t>(want, cap);
 }
 
+// alphabet.hpp:147-164 on the host from the device histogram
+// tab gets codes 0..sigma-1 in byte order (the packed sort key needs no end-marker code);
+// bits is psac's bits_per_char = ceil(log2(sigma + 1)), bits_packed = max(1, ceil(log2(sigma))).
+inline void build_alphabet(const unsigned long long* hist, CodeTable& tab, uint32_t& sigma, uint32_t& bits,
+                           uint32_t& bits_packed) {
+    uint16_t next = 0;
+    for (int ch = 0; ch < 256; ++ch) tab.c[ch] = hist[ch] ? next++ : (uint16_t)0;
+    sigma = next;
+    uint32_t b = 0;
+    while ((1u << b) < sigma + 1u) ++b;          // ceil(log2(sigma + 1))
+    bits = b;
+    b = 0;
+    while ((1u << b) < sigma) ++b;               // ceil(log2(sigma))
+    bits_packed = b ? b : 1;
+}
+
+// The suffix tree's code table from a 256-bin character histogram: build_alphabet's codes moved up by one, 1..sigma in byte order,
+// 0 = end of text (and every character that does not occur).
+inline void tree_code_table(const unsigned long long* hist, CodeTable& tab, uint32_t& sigma) {
+    uint32_t bits = 0, bits_packed = 0;
+    build_alphabet(hist, tab, sigma, bits, bits_packed);
+    for (int ch = 0; ch < 256; ++ch) if (hist[ch]) tab.c[ch] = (uint16_t)(tab.c[ch] + 1);
+}
+
+// The same for a text resident in HBM: the characters are counted on the device (char_hist_kernel into d_hist, 256 words); the host
+// only sees the 256 counts.
+inline int tree_alphabet_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, unsigned long long* d_hist, CodeTable& tab, uint32_t& sigma) {
+    PSACX_HIP(c, hipMemsetAsync(d_hist, 0, 256 * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL((char_hist_kernel<256>), dim3(grid_for(c, n / 16 + 1, 256, 8)), dim3(256), 0, c->stream, d_text, n, d_hist);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long h[256];
+    PSACX_HIP(c, hipMemcpyAsync(h, d_hist, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    tree_code_table(h, tab, sigma);
+    return PSACX_OK;
+}
+
 inline unsigned bits_for(uint64_t max_value) {      // bits needed to hold values 0..max_value
     unsigned b = 0;
     while (b < 64 && (max_value >> b) != 0) ++b;

@@ -255,6 +255,27 @@ def suffix_tree(text, SA, LCP, ctx=None):
     return nodes.reshape(t.size, sigma.value + 1)
 
 
+def suffix_tree_device(ctx, d_text, n, d_sa, d_lcp, d_nodes, index_bits):
+    """psacx_suffix_tree_dev_*: the node table of suffix_tree() with every array resident in HBM (raw device addresses), e.g.
+    the SA / LCP construct_device left there.  d_nodes receives n x (sigma + 1) uint64 cells; with d_nodes=None only sigma is
+    computed, to size it.  Returns (sigma, edges): edges = records written = nonzero cells (0 for the query)."""
+    fn = getattr(ctx._lib, "psacx_suffix_tree_dev_u%d" % index_bits)
+    sigma, edges = C.c_uint32(0), C.c_uint64(0)
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_sa) if d_sa else None, C.c_void_p(d_lcp) if d_lcp else None,
+                 C.c_void_p(d_nodes) if d_nodes else None, C.byref(sigma), C.byref(edges)))
+    return sigma.value, edges.value
+
+
+def check_suffix_tree_device(ctx, d_text, n, d_sa, d_lcp, d_nodes, index_bits):
+    """psacx_check_suffix_tree_dev_*: is the table at d_nodes the suffix tree of the text / SA / LCP as given (all in HBM)?
+    Returns [records not matched, nonzero cells no record accounts for, records, nonzero cells]; correct iff the first two
+    are zero.  SA and LCP themselves are check_device's business."""
+    out = (C.c_uint64 * 4)()
+    fn = getattr(ctx._lib, "psacx_check_suffix_tree_dev_u%d" % index_bits)
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_sa), C.c_void_p(d_lcp), C.c_void_p(d_nodes), out))
+    return list(out)
+
+
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
     """check_SA / check_lcp on buffers resident in HBM (check_suffix_array.hpp:56-126).  Returns the four
     error counters of psacx_check_dev_*; all zero means correct."""
