@@ -127,11 +127,14 @@ int psacx_trim(psacx_ctx* ctx);
  *   NO_WHOLE          no text-order rounds
  *   NO_LAZY_RANKS     the heavy runs of a split round always take the rank of their head and store it
  *   NO_EARLY_OUT      host-pointer calls: SA and LCP leave the device only when the construction has returned (default: from the moment the
- *                     first round has written them, under the SA -> ISA inversion; copied again if refinement rounds follow)             */
+ *                     first round has written them, under the SA -> ISA inversion; copied again if refinement rounds follow)
+ *   NO_SPREAD_CURSORS the partition levels of the SA -> ISA path run their tiles in order (default: striped over several destination classes,
+ *                     so that the workgroups running together do not all reserve and write inside one of them)                            */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
-    PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT, PSACX_OPT_COUNT
+    PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
+    PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
 /* Debug shim, the ONLY place where the library looks at the environment, and only when called: resets the options of ctx and sets those

@@ -65,6 +65,14 @@ constexpr uint64_t ONEW_PAD = 20480;            // places per bucket: 160 KiB
 template <typename T> inline uint64_t onew_pad_total(uint64_t n) { return (sizeof(T) == 8 && n >= (1ull << 28)) ? (uint64_t)RADIX * ONEW_PAD : 0; }
 
 constexpr int ISA_NARROW_WB = 14, ISA_NARROW_CB = 9;      // windows of 2^14 positions, 512-way partition levels (invert_permutation, IsaLevels, GatherLevels)
+// Tile order of the packed partition levels (sa_kernels.hpp: partition_packed_kernel): the workgroups that run at a time work in ISA_STRIPES
+// parent classes instead of one (8 and 16 stripes measured the same, 32 and 64 slower).  PSACX_OPT_NO_SPREAD_CURSORS: tiles in order (A/B runs).
+#ifndef ISA_STRIPES
+#define ISA_STRIPES 16
+#endif
+static_assert(ISA_STRIPES % 8 == 0, "the tiles of a stripe stay on one XCD");
+inline unsigned isa_stripes(const Knobs& kn) { return kn.no_spread_cursors ? 1u : (unsigned)ISA_STRIPES; }
+inline unsigned striped_grid(uint64_t ntiles, unsigned stripes) { return (unsigned)((ntiles + stripes - 1) / stripes * stripes); }
 template <typename T>
 size_t carve(Arena& a, Work<T>& w, uint64_t n, bool with_lcp, T* d_lcp, bool diet, uint64_t cap, T* d_sa, T* d_isa, const Knobs& kn) {
     w.diet = diet;
@@ -331,6 +339,7 @@ int invert_permutation(psacx_ctx* c, unsigned* d_cursors, const T* d_sa, const T
         constexpr int WB = ISA_NARROW_WB, CB = ISA_NARROW_CB;
         const uint64_t ntiles = (n + PB * PI - 1) / (PB * PI);
         const int lv9 = isa_narrow_levels<T>(n, kn);
+        const unsigned stripes = isa_stripes(kn);
         // packed pairs: one array of (position | rank << 32) entries per level (sa_kernels.hpp: partition_packed_kernel)
         uint64_t* pb[2] = {reinterpret_cast<uint64_t*>(t1.k1), reinterpret_cast<uint64_t*>(t2.k1)};
         const uint64_t* cur = fused_l1 ? pb[0] : nullptr;
@@ -339,11 +348,11 @@ int invert_permutation(psacx_ctx* c, unsigned* d_cursors, const T* d_sa, const T
             PSACX_HIP(c, hipMemsetAsync(d_cursors, 0, ((size_t)(n >> shift) + 1) * sizeof(unsigned), c->stream));
             uint64_t* o = pb[lv & 1];
             if (lv == 0)
-                hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 1, CB>), dim3((unsigned)ntiles), dim3(PB), 0, c->stream, d_sa, val,
-                                   (const uint64_t*)nullptr, o, n, shift, d_cursors, koff);
+                hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 1, CB>), dim3(striped_grid(ntiles, stripes)), dim3(PB), 0, c->stream, d_sa, val,
+                                   (const uint64_t*)nullptr, o, n, shift, d_cursors, koff, (const unsigned*)nullptr, 0u, (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, (const ulonglong2*)nullptr, 0u, stripes);
             else
-                hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3((unsigned)ntiles), dim3(PB), 0, c->stream, (const T*)nullptr,
-                                   (const T*)nullptr, cur, o, n, shift, d_cursors, (uint64_t)0);
+                hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3(striped_grid(ntiles, stripes)), dim3(PB), 0, c->stream, (const T*)nullptr,
+                                   (const T*)nullptr, cur, o, n, shift, d_cursors, (uint64_t)0, (const unsigned*)nullptr, 0u, (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, (const ulonglong2*)nullptr, 0u, stripes);
             PSACX_HIP(c, hipGetLastError());
             cur = o;
         }
@@ -379,12 +388,13 @@ int invert_permutation(psacx_ctx* c, unsigned* d_cursors, const T* d_sa, const T
 // (1024 + (n >> 14) + 1 entries).  One random 8-byte store per record instead: 217 ms per round of 2^32 records.
 template <typename T> struct IsaLevels {
     static constexpr int PB = 512, PI = 16, WB = ISA_NARROW_WB, CB = ISA_NARROW_CB;
-    psacx_ctx* c; unsigned* cursors; uint64_t n; int lv9; uint64_t* lvl_a; bool open;
+    psacx_ctx* c; unsigned* cursors; uint64_t n; int lv9; uint64_t* lvl_a; bool open; unsigned stripes;
     unsigned* c0() const { return cursors; }
     unsigned* c1() const { return cursors + 1024; }
     int begin(psacx_ctx* ctx, unsigned* d_cursors, uint64_t n_, uint64_t* a, const Knobs& kn) {
         c = ctx; cursors = d_cursors; n = n_; lvl_a = a; open = true;
         lv9 = isa_narrow_levels<T>(n, kn);
+        stripes = isa_stripes(kn);
         if (lv9 < 1 || lv9 > 2) { c->hip_err = "ISA update by levels: text size out of range"; return PSACX_EINVAL; }
         PSACX_HIP(c, hipMemsetAsync(cursors, 0, (1024 + (size_t)(n >> WB) + 1) * sizeof(unsigned), c->stream));
         return PSACX_OK;
@@ -392,9 +402,9 @@ template <typename T> struct IsaLevels {
     // skip (split rounds, heavy_keys.hpp): per scan tile of the list whether it lies inside a heavy run that keeps its rank -- tiles of such entries are left out
     int add(const uint64_t* pairs, uint64_t cnt, const ulonglong2* skip = nullptr) {
         static_assert((PB * PI) % ScanCfg<T>::TILE == 0 || sizeof(T) != 8, "a tile of pairs covers whole scan tiles");
-        hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3((unsigned)((cnt + PB * PI - 1) / (PB * PI))), dim3(PB), 0, c->stream, (const T*)nullptr,
+        hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3(striped_grid((cnt + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, (const T*)nullptr,
                            (const T*)nullptr, pairs, lvl_a, cnt, isa_narrow_shift(lv9, 0), lv9 == 1 ? c1() : c0(), (uint64_t)0, (const unsigned*)nullptr, 0u,
-                           (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, skip, skip ? (unsigned)((PB * PI) / ScanCfg<T>::TILE) : 0u);
+                           (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, skip, skip ? (unsigned)((PB * PI) / ScanCfg<T>::TILE) : 0u, stripes);
         PSACX_HIP(c, hipGetLastError());
         return PSACX_OK;
     }
@@ -402,8 +412,9 @@ template <typename T> struct IsaLevels {
         open = false;
         const uint64_t* last = lvl_a;
         if (lv9 == 2) {
-            hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3((unsigned)((n + PB * PI - 1) / (PB * PI))), dim3(PB), 0, c->stream, (const T*)nullptr,
-                               (const T*)nullptr, (const uint64_t*)lvl_a, lvl_b, n, (unsigned)WB, c1(), (uint64_t)0, (const unsigned*)c0(), isa_narrow_shift(lv9, 0));
+            hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3(striped_grid((n + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, (const T*)nullptr,
+                               (const T*)nullptr, (const uint64_t*)lvl_a, lvl_b, n, (unsigned)WB, c1(), (uint64_t)0, (const unsigned*)c0(), isa_narrow_shift(lv9, 0),
+                               (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, (const ulonglong2*)nullptr, 0u, stripes);
             PSACX_HIP(c, hipGetLastError());
             last = lvl_b;
         }
@@ -427,12 +438,15 @@ int gather_by_levels(psacx_ctx* c, Work<T>& w, uint64_t n, uint64_t h, const T* 
     constexpr int PB = 512, PI = 16, WB = ISA_NARROW_WB, CB = ISA_NARROW_CB;
     if (isa_narrow_levels<T>(n, kn) != 2) { c->hip_err = "B2 fetch by levels: text size out of range"; return PSACX_EINVAL; }
     unsigned* const c0 = w.d_gcursors; unsigned* const c1 = w.d_gcursors + 1024;
+    const unsigned stripes = isa_stripes(kn);
     const uint64_t nwin = (n + (1ull << WB) - 1) >> WB;
     PSACX_HIP(c, hipMemsetAsync(c0, 0, (1024 + (size_t)nwin + 1) * sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 2, CB>), dim3((unsigned)((cnt + PB * PI - 1) / (PB * PI))), dim3(PB), 0, c->stream, d_sa, plist,
-                       (const uint64_t*)nullptr, lvl_a, cnt, isa_narrow_shift(2, 0), c0, (uint64_t)0, (const unsigned*)nullptr, 0u, ord, h, n);
-    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3((unsigned)((n + PB * PI - 1) / (PB * PI))), dim3(PB), 0, c->stream, (const T*)nullptr,
-                       (const T*)nullptr, (const uint64_t*)lvl_a, lvl_b, n, (unsigned)WB, c1, (uint64_t)0, (const unsigned*)c0, isa_narrow_shift(2, 0));
+    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 2, CB>), dim3(striped_grid((cnt + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, d_sa, plist,
+                       (const uint64_t*)nullptr, lvl_a, cnt, isa_narrow_shift(2, 0), c0, (uint64_t)0, (const unsigned*)nullptr, 0u, ord, h, n,
+                       (const ulonglong2*)nullptr, 0u, stripes);
+    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3(striped_grid((n + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, (const T*)nullptr,
+                       (const T*)nullptr, (const uint64_t*)lvl_a, lvl_b, n, (unsigned)WB, c1, (uint64_t)0, (const unsigned*)c0, isa_narrow_shift(2, 0),
+                       (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, (const ulonglong2*)nullptr, 0u, stripes);
     hipLaunchKernelGGL(window_offsets_kernel<1024>, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)c1, nwin, w.d_gwin);
     hipLaunchKernelGGL((window_gather_kernel<T, 1024, WB>), dim3((unsigned)nwin), dim3(1024), 0, c->stream, (const uint64_t*)lvl_b, (const unsigned*)c1,
                        (const uint64_t*)w.d_gwin, n, h, d_isa, kb2, keys, v32, w.sc.d_partials);
@@ -464,13 +478,16 @@ int gather_heavy_by_levels(psacx_ctx* c, Work<T>& w, uint64_t n, uint64_t h, con
     const HeavyTabs ht = heavy_tabs(w.d_heavy, nb);
     *tabs = ht;
     unsigned* const c0 = w.d_gcursors; unsigned* const c1 = w.d_gcursors + 1024;
+    const unsigned stripes = isa_stripes(kn);
     const uint64_t nwin = (n + (1ull << WB) - 1) >> WB;
     hipLaunchKernelGGL((heavy_probe_kernel<T>), dim3((nb + 1 + 255) / 256), dim3(256), 0, c->stream, ord, cnt, (uint32_t)nb, plist, d_sa, d_isa, n, h, ht);
     PSACX_HIP(c, hipMemsetAsync(c0, 0, (1024 + (size_t)nwin + 1) * sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 2, CB>), dim3((unsigned)((cnt + PB * PI - 1) / (PB * PI))), dim3(PB), 0, c->stream, d_sa, plist,
-                       (const uint64_t*)nullptr, lvl_a, cnt, isa_narrow_shift(2, 0), c0, (uint64_t)0, (const unsigned*)nullptr, 0u, ord, h, n);
-    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3((unsigned)((n + PB * PI - 1) / (PB * PI))), dim3(PB), 0, c->stream, (const T*)nullptr,
-                       (const T*)nullptr, (const uint64_t*)lvl_a, lvl_b, n, (unsigned)WB, c1, (uint64_t)0, (const unsigned*)c0, isa_narrow_shift(2, 0));
+    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 2, CB>), dim3(striped_grid((cnt + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, d_sa, plist,
+                       (const uint64_t*)nullptr, lvl_a, cnt, isa_narrow_shift(2, 0), c0, (uint64_t)0, (const unsigned*)nullptr, 0u, ord, h, n,
+                       (const ulonglong2*)nullptr, 0u, stripes);
+    hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3(striped_grid((n + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, (const T*)nullptr,
+                       (const T*)nullptr, (const uint64_t*)lvl_a, lvl_b, n, (unsigned)WB, c1, (uint64_t)0, (const unsigned*)c0, isa_narrow_shift(2, 0),
+                       (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, (const ulonglong2*)nullptr, 0u, stripes);
     hipLaunchKernelGGL((window_gather_heavy_kernel<T, 1024, WB>), dim3((unsigned)nwin), dim3(1024), (size_t)nb * 2 * sizeof(uint32_t), c->stream, (const uint64_t*)lvl_b,
                        (const unsigned*)c1, n, h, d_isa, kb2, (uint32_t)nb, ht, LK, LV, HB, w.sc.d_partials);
     uint64_t* const h_light = reinterpret_cast<uint64_t*>(c->pinned + 112);

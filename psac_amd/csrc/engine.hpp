@@ -60,6 +60,8 @@ struct Knobs {
     bool no_whole = false;        // PSACX_OPT_NO_WHOLE: rounds in which nearly every suffix is unresolved take the list of positions too (A/B runs)
     bool widen_last = false;      // PSACX_OPT_WIDEN_LAST: the last pass of the one-word prefix sort writes word 1 and the suffixes as two arrays (the form the
                                   // tie stage's radix path and the multi-GPU engine read) although the kernels after the sort could read one-word records
+    bool no_spread_cursors = false; // PSACX_OPT_NO_SPREAD_CURSORS: the packed partition levels of the SA -> ISA path run their tiles in order, every resident workgroup
+                                  // in one parent class (construct.hpp: isa_stripes; A/B runs)
 };
 
 } // namespace psacx

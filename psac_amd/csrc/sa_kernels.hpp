@@ -1266,7 +1266,15 @@ __global__ __launch_bounds__(BLOCK) void partition_packed_kernel(const TI* __res
                                                                  unsigned shift, unsigned* __restrict__ cursors, uint64_t koff,
                                                                  const unsigned* __restrict__ in_counts = nullptr, unsigned in_shift = 0,
                                                                  const uint32_t* __restrict__ req_ord = nullptr, uint64_t req_h = 0, uint64_t n_text = 0,
-                                                                 const ulonglong2* __restrict__ skip_tiles = nullptr, unsigned skip_per_tile = 0) {
+                                                                 const ulonglong2* __restrict__ skip_tiles = nullptr, unsigned skip_per_tile = 0,
+                                                                 unsigned stripes = 1) {
+    // stripes (a multiple of 8, grid = striped_grid(tiles, stripes); 1: workgroup b takes tile b): workgroup b takes tile
+    // (b % stripes) * ceil(tiles / stripes) + b / stripes.  The tiles of a level after the first lie in their parent classes one after the
+    // other, so in tile order every workgroup that runs at a time reserves at the 2^CB cursors of ONE parent class and writes into its 2^CB
+    // regions; striped, the workgroups work in `stripes` parent classes at a time: level 2 of 2^32 pairs and the window scatter 29.8 -> 24.4 ms
+    // with 8 or 16 stripes, 25.1 with 32, 27.1 with 64 (profiles/isa_cursors_ab.txt).  The reservations alone do not explain it
+    // (tools/ubench_reserve.hip: 1.2 ms in tile order); the level took 19.0 ms where its write pattern copies in 13.4.  Workgroups b and b + 8 run on one XCD, so the runs a class receives
+    // still meet in one L2.  Tiles do not depend on each other: the class regions receive the same records in another order.
     // skip_tiles (the ISA entries of a split round, heavy_keys.hpp): this tile covers skip_per_tile scan tiles of the list; when all of them
     // lie inside heavy runs that keep their ranks (HeavyView::tile_b) there is nothing in it to store
     // in_counts (levels after the first, pairs of a SUBSET of the positions: the ISA update of a refinement round): the class regions of
@@ -1280,7 +1288,15 @@ __global__ __launch_bounds__(BLOCK) void partition_packed_kernel(const TI* __res
     __shared__ uint64_t gbase[NCLS];
     __shared__ unsigned scan_tmp[BLOCK / WAVE + 1];
     const unsigned tid = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * TILE;
+    const uint64_t ntiles = (n + TILE - 1) / TILE;
+    uint64_t tile = blockIdx.x;
+    if (stripes > 1) {
+        const uint64_t per = (ntiles + stripes - 1) / stripes, k = blockIdx.x / stripes;
+        if (k >= per) return;                        // (the same for every thread of the workgroup)
+        tile = (uint64_t)(blockIdx.x % stripes) * per + k;
+    }
+    if (tile >= ntiles) return;
+    const uint64_t base = tile * TILE;
     uint64_t remain = n - base;
     if (in_counts) {
         const uint64_t filled = in_counts[base >> in_shift], into = base & ((1ull << in_shift) - 1);
@@ -1291,7 +1307,7 @@ __global__ __launch_bounds__(BLOCK) void partition_packed_kernel(const TI* __res
     if (skip_tiles) {
         bool all = true;
         for (unsigned q = 0; q < skip_per_tile; ++q) {
-            const uint64_t st = (uint64_t)blockIdx.x * skip_per_tile + q;
+            const uint64_t st = tile * skip_per_tile + q;
             if (st * (TILE / skip_per_tile) >= n) break;
             const ulonglong2 tb = skip_tiles[st];
             all = all && tb.y != ~0ull && (tb.y & HEAVY_VIEW_KEEP) != 0;
