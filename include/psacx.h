@@ -336,6 +336,57 @@ int psacx_check_suffix_tree_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint6
 int psacx_check_suffix_tree_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
                                     const uint64_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
 
+/* The suffix tree of a string set (construct_gst with gst_edgechars, suffix_tree.hpp:501-608, one rank) from the arrays
+ * psacx_construct_gsa_* leaves: text[0..n) holds the m strings back to back, offsets[0..m] ascend with offsets[0] = 0,
+ * offsets[m] = n and no empty string (anything else: PSACX_EINVAL before any other array is read).  One row of sigma + 2 cells per
+ * LCP index: cells 0 and 1 hold the first and the last $-leaf (a suffix whose string ends at the node's depth), cell c + 1 the
+ * child through the character with alphabet code c; leaves are numbered n + i, 0 = none.  Two things differ from the reference,
+ * whose code for this is never called: the root's edges are stored (it collects them and drops them), and a suffix that starts a
+ * string hangs under the root by its first character (its test for "string begins here" would take it for an ended one).
+ * Defined as the one-string table above is: L = LCP with L[0] read as 0 whatever is stored, head(), l, r and code() as there,
+ * row = sigma + 2, start[p] = a string starts at p, or p == n.
+ *   gcell(s, d) = 0 (the $) if s >= n, or d >= n - s, or (d > 0 and start[s + d]); else code(text[s + d]) (no out-of-range read);
+ *   leaf record of every i in [0, n): x = i + 1 if i + 1 < n and L[i+1] > L[i], else x = i; id n + i, row head(x),
+ *     c = gcell(SA[i], L[x]);
+ *   internal record of every i >= 1 with L[i] > 0 and head(i) == i: (p, d) = (r, L[r]) if r exists and L[r] > L[l], else
+ *     (head(l), L[l]); id i, row p, c = gcell(SA[i], d);
+ *   a record with c >= 1 puts its id in cell (row, 1 + c); the records of a row with c == 0 put their smallest id in cell (row, 0)
+ *   and their largest in cell (row, 1); every other cell is 0.
+ * On a correct generalized suffix array the c == 0 records of a row are leaves only, neighbours in SA (the equal suffixes, first in
+ * the node's interval), and row 0 has none; with m = 1, columns 2.. are columns 1.. of the one-string table and columns 0 and 1
+ * both its column 0.
+ * psacx_suffix_tree_gsa_dev_*: everything resident in HBM, no input written; d_nodes == NULL only computes *sigma (d_offsets, d_SA
+ * and d_LCP may be NULL then); edges (may be NULL) receives the number of records written, leaf + internal, counted by the kernel
+ * that writes them.  The $ cells are written without atomics: a $-leaf i at depth d writes cell 0 iff i == 0 or not (L[i] == d
+ * and the suffix at SA[i-1] ends d characters on), and cell 1 iff i == n - 1 or not (L[i+1] == d and the suffix at SA[i+1] ends
+ * d characters on).  On arrays that are no generalized suffix array nothing is read or written out of range (SA >= n and
+ * SA + d >= n are turned away before the bitmap and the text are touched; parents are LCP indices), and the $ cells of a row hold
+ * ids of $ records of that row, not necessarily the extremes.  The stored LCP[0] is never used as a value: where it is not 0
+ * the call works on a copy of LCP.  Workspace: the ctx slab (the ANSV of LCP, 16 n bytes, and the bitmap of n + 1 bits).
+ * psacx_suffix_tree_gsa_*: the host-pointer form, nodes[n x (sigma + 2)]; nodes == NULL only computes *sigma. */
+int psacx_suffix_tree_gsa_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m,
+                              const uint32_t* SA, const uint32_t* LCP, uint64_t* nodes, uint32_t* sigma);
+int psacx_suffix_tree_gsa_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m,
+                              const uint64_t* SA, const uint64_t* LCP, uint64_t* nodes, uint32_t* sigma);
+int psacx_suffix_tree_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                                  const uint32_t* d_SA, const uint32_t* d_LCP, uint64_t* d_nodes, uint32_t* sigma, uint64_t* edges);
+int psacx_suffix_tree_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                                  const uint64_t* d_SA, const uint64_t* d_LCP, uint64_t* d_nodes, uint32_t* sigma, uint64_t* edges);
+/* Is d_nodes that table for the text / offsets / SA / LCP as given?  As psacx_check_suffix_tree_dev_*: the same searches, no ANSV,
+ * no code of the builder's; malformed offsets return PSACX_EINVAL.  Counting rules, total for any SA, LCP and table:
+ *  - out[2] = records of the arrays as given; out[3] = nonzero cells of the table;
+ *  - a record with c >= 1 is matched iff cell (row, 1 + c) holds its id;
+ *  - a record with c == 0 and id v is matched iff lo != 0 and lo <= v <= hi, lo and hi being cells (row, 0) and (row, 1); it is then
+ *    also a witness of lo if v == lo and of hi if v == hi (a single $-leaf witnesses both);
+ *  - out[0] = records not matched; out[1] = out[3] - matched records with c >= 1 - witnesses (never negative: ids are distinct
+ *    and a record witnesses only its own row);
+ *  - correct <=> out[0] == out[1] == 0.
+ * Table values are only compared, never used as indices. */
+int psacx_check_suffix_tree_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                                        const uint32_t* d_SA, const uint32_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
+int psacx_check_suffix_tree_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                                        const uint64_t* d_SA, const uint64_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
+
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP
  * (suffix_array.hpp:183-194, :217-228; src/psac.cpp:85-93 block-decomposes the input).  A psacx_multi stands for the

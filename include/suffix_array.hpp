@@ -532,4 +532,38 @@ std::vector<std::size_t> construct_suffix_tree(suffix_array<char, index_t, true>
     return nodes;
 }
 
+// construct_gst(sa, ss, comm) of the reference (include/suffix_tree.hpp:521-608): the (sigma + 2) * n node table of the
+// string set `sa.construct_ss(ss, ...)` was built from (row i = internal node of LCP index i, cells 0 and 1 = first and last
+// $-leaf, cell c + 1 = child through the character with alphabet code c, leaves are n + i, 0 = none; psacx_suffix_tree_gsa_* in
+// psacx.h defines it and names the two points where the reference's code, which nothing calls, would differ).  One rank only:
+// there is no distributed form, and none is emulated by gathering.
+template <typename index_t>
+std::vector<std::size_t> construct_gst(suffix_array<char, index_t, true>& sa, simple_dstringset& ss, const psacx::comm& = psacx::comm(0)) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    if (sa.multi_context()) throw std::runtime_error("psacx: construct_gst needs a single-rank communicator (the tree of a string set is built on one GPU)");
+    if (ss.sum_sizes != sa.n) throw std::runtime_error("construct_gst: string set does not match the suffix array");
+    std::vector<uint8_t> text; text.reserve(sa.n);
+    std::vector<uint64_t> off(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) {
+        text.insert(text.end(), reinterpret_cast<const uint8_t*>(ss.str_begins[s]), reinterpret_cast<const uint8_t*>(ss.str_begins[s]) + ss.sizes[s]);
+        off.push_back(text.size());
+    }
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* f, uint64_t m, const uint32_t* a, const uint32_t* l, uint64_t* o, uint32_t* s) {
+            return psacx_suffix_tree_gsa_u32(c, t, n, f, m, a, l, o, s);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* f, uint64_t m, const uint64_t* a, const uint64_t* l, uint64_t* o, uint32_t* s) {
+            return psacx_suffix_tree_gsa_u64(c, t, n, f, m, a, l, o, s);
+        }
+    };
+    uint32_t sigma = 0;
+    const uint64_t m = (uint64_t)ss.sizes.size();
+    psacx::check(sa.context(), Call::run(sa.context(), text.data(), sa.n, off.data(), m, (const W*)nullptr, (const W*)nullptr, nullptr, &sigma));
+    std::vector<std::size_t> nodes((std::size_t)(sigma + 2) * sa.n, 0);
+    psacx::check(sa.context(), Call::run(sa.context(), text.data(), sa.n, off.data(), m, reinterpret_cast<const W*>(sa.local_SA.data()),
+                                         reinterpret_cast<const W*>(sa.local_LCP.data()), reinterpret_cast<uint64_t*>(nodes.data()), &sigma));
+    return nodes;
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

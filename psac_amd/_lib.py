@@ -37,7 +37,9 @@ EXPORTS = [
     "psacx_construct_lc_u32", "psacx_construct_lc_u64", "psacx_construct_lc_dev_u32", "psacx_construct_lc_dev_u64",
     "psacx_get_stats", "psacx_profile", "psacx_check_dev_u32", "psacx_check_dev_u64", "psacx_check_gsa_dev_u32", "psacx_check_gsa_dev_u64", "psacx_pair_sort_dev_u32", "psacx_pair_sort_dev_u64", "psacx_ansv_u32",
     "psacx_ansv_u64", "psacx_ansv_dev_u32", "psacx_ansv_dev_u64", "psacx_suffix_tree_u32", "psacx_suffix_tree_u64", "psacx_suffix_tree_dev_u32", "psacx_suffix_tree_dev_u64",
-    "psacx_check_suffix_tree_dev_u32", "psacx_check_suffix_tree_dev_u64", "psacx_dev_alloc", "psacx_dev_free", "psacx_copy_h2d", "psacx_copy_d2h", "psacx_sync",
+    "psacx_check_suffix_tree_dev_u32", "psacx_check_suffix_tree_dev_u64",
+    "psacx_suffix_tree_gsa_u32", "psacx_suffix_tree_gsa_u64", "psacx_suffix_tree_gsa_dev_u32", "psacx_suffix_tree_gsa_dev_u64",
+    "psacx_check_suffix_tree_gsa_dev_u32", "psacx_check_suffix_tree_gsa_dev_u64", "psacx_dev_alloc", "psacx_dev_free", "psacx_copy_h2d", "psacx_copy_d2h", "psacx_sync",
     "psacx_rand_dna", "psacx_synth_text_dev",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
@@ -122,6 +124,9 @@ def load():
     for suf in ("u32", "u64"):
         getattr(lib, "psacx_suffix_tree_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_check_suffix_tree_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_suffix_tree_gsa_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint32)]
+        getattr(lib, "psacx_suffix_tree_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_check_suffix_tree_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_gsa_dev_u32.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

@@ -74,10 +74,24 @@ int ansv_run(psacx_ctx* c, const T* in, uint64_t n, int lt, int rt, uint64_t non
 // text).  Leaves are numbered n + i.  Parents come from the ANSV of LCP: left = furthest_eq,
 // right = nearest_sm (suffix_tree.hpp:62).
 // ---------------------------------------------------------------------------------------------
-template <typename T>
+//
+// GSA = true: the table of a string set (include/psacx.h, psacx_suffix_tree_gsa_dev_*).  The parents are the same function of LCP; a
+// row has sigma + 2 cells, the character with code c leads to cell 1 + c, and a suffix whose string has ended at the parent's depth
+// (bits: bit p = "a string starts at p, or p == n") is a $-leaf.  The $-leaves of a node are equal suffixes, neighbours in SA: the
+// one whose left neighbour is no $-leaf of the node writes cell 0, the one whose right neighbour is none writes cell 1.
+
+// has the string of the suffix at s ended d characters on?  Nothing is read unless s < n and s + d < n.
+__device__ __forceinline__ bool gst_ended(const uint32_t* __restrict__ bits, uint64_t n, uint64_t s, uint64_t d) {
+    if (s >= n || d >= n - s) return true;
+    const uint64_t p = s + d;
+    return d > 0 && ((bits[p >> 5] >> (p & 31)) & 1u);
+}
+
+template <typename T, bool GSA>
 __global__ void st_nodes_kernel(const T* __restrict__ LCP, uint64_t n, const T* __restrict__ SA, const uint8_t* __restrict__ text,
                                 CodeTable tab, uint64_t row, const uint64_t* __restrict__ lnsv, const uint64_t* __restrict__ rnsv,
-                                unsigned long long* __restrict__ nodes, unsigned long long* __restrict__ edges) {
+                                unsigned long long* __restrict__ nodes, unsigned long long* __restrict__ edges,
+                                const uint32_t* __restrict__ bits) {
     // lnsv / rnsv: ANSV of LCP with left = furthest_eq, right = nearest_sm (suffix_tree.hpp:62), NSV_NONE where none.
     // The stored LCP[0] is expected to be 0.  Where it is not, it still never serves as an index or as a depth: a left result of "none"
     // (only possible then) stands for parent 0 at depth 0, a left result of 0 is read as depth 0, and a parent at depth 0 is row 0
@@ -105,7 +119,17 @@ __global__ void st_nodes_kernel(const T* __restrict__ LCP, uint64_t n, const T* 
             parent = i + 1; lcp_val = LCP[i + 1];
         }
         uint64_t ci = sa + lcp_val;
-        nodes[parent * row + (ci < n ? tab.c[text[ci]] : 0)] = n + i;
+        if (!GSA) {
+            nodes[parent * row + (ci < n ? tab.c[text[ci]] : 0)] = n + i;
+        } else if (!gst_ended(bits, n, sa, lcp_val)) {
+            nodes[parent * row + 1 + tab.c[text[ci]]] = n + i;
+        } else {
+            // a $-leaf at depth lcp_val: its neighbour is one of the same node iff they share exactly lcp_val characters and it ends there too
+            const bool first = i == 0 || !(li == lcp_val && gst_ended(bits, n, SA[i - 1], lcp_val));
+            const bool last = i == n - 1 || !((uint64_t)LCP[i + 1] == lcp_val && gst_ended(bits, n, SA[i + 1], lcp_val));
+            if (first) nodes[parent * row] = n + i;
+            if (last) nodes[parent * row + 1] = n + i;
+        }
         ++written;
         // ---- the internal node i (suffix_tree.hpp:146-222)
         if (i == 0 || li == 0) continue;
@@ -118,7 +142,14 @@ __global__ void st_nodes_kernel(const T* __restrict__ LCP, uint64_t n, const T* 
             else { parent = rn; lcp_val = rv; }
         }
         ci = sa + lcp_val;
-        nodes[parent * row + (ci < n ? tab.c[text[ci]] : 0)] = i;
+        if (!GSA) {
+            nodes[parent * row + (ci < n ? tab.c[text[ci]] : 0)] = i;
+        } else if (!gst_ended(bits, n, sa, lcp_val)) {
+            nodes[parent * row + 1 + tab.c[text[ci]]] = i;
+        } else {
+            // (no generalized suffix array has such a node: the arrays are wrong, and so will this row be)
+            nodes[parent * row] = i; nodes[parent * row + 1] = i;
+        }
         ++written;
     }
     if (edges) {
@@ -163,8 +194,8 @@ int suffix_tree_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const T* sa,
     }
     launch_ansv_tiles<T>(c, P, n, 2, 0, NSV_NONE, d_ln, d_rn);
     PSACX_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL((st_nodes_kernel<T>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, d_lcp, n, d_sa, d_text, tab, row,
-                       d_ln, d_rn, d_nodes, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL((st_nodes_kernel<T, false>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, d_lcp, n, d_sa, d_text, tab, row,
+                       d_ln, d_rn, d_nodes, (unsigned long long*)nullptr, (const uint32_t*)nullptr);
     PSACX_HIP(c, hipGetLastError());
     PSACX_HIP(c, hipMemcpyAsync(nodes, d_nodes, n * row * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -204,8 +235,8 @@ int suffix_tree_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_
     }
     launch_ansv_tiles<T>(c, P, n, 2, 0, NSV_NONE, d_ln, d_rn);
     PSACX_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL((st_nodes_kernel<T>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, d_lcp, n, d_sa, d_text, tab, row,
-                       d_ln, d_rn, reinterpret_cast<unsigned long long*>(d_nodes), d_edges);
+    hipLaunchKernelGGL((st_nodes_kernel<T, false>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, d_lcp, n, d_sa, d_text, tab, row,
+                       d_ln, d_rn, reinterpret_cast<unsigned long long*>(d_nodes), d_edges, (const uint32_t*)nullptr);
     PSACX_HIP(c, hipGetLastError());
     unsigned long long cnt = 0;
     PSACX_HIP(c, hipMemcpyAsync(&cnt, d_edges, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
@@ -213,6 +244,119 @@ int suffix_tree_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_
     if (edges) *edges = cnt;
     return PSACX_OK;
 }
+
+// check.hip: PSACX_EINVAL unless the m + 1 offsets on the device start at 0, end at n and ascend strictly (uses the first bytes of the
+// slab and waits); and the bitmap of the string ends into bits[(n >> 5) + 1], queued on the ctx stream
+int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n);
+int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits);
+
+template <typename T>
+__global__ void gst_clear_first_kernel(T* lcp) { lcp[0] = 0; }
+
+// The table of a string set (psacx_suffix_tree_gsa_dev_*): suffix_tree_dev with the bitmap of the string ends beside the ANSV results
+// in the slab.  The ANSV takes the stored LCP[0] for a value, so where it is not 0 -- psacx_construct_gsa_* always stores 0 -- the
+// call works on a copy of LCP whose entry 0 is.
+template <typename T>
+int suffix_tree_gsa_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint64_t* d_off, uint64_t m, const T* d_sa, const T* d_lcp,
+                        uint64_t* d_nodes, uint32_t* sigma, uint64_t* edges) {
+    if (!c || !d_text || !sigma || n == 0) return PSACX_EINVAL;
+    if (d_nodes && (!d_sa || !d_lcp || !d_off)) return PSACX_EINVAL;
+    if (d_off && (m == 0 || m > n)) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    if (d_off) PSACX_TRY(string_offsets_valid_dev(c, d_off, m, n));
+    T lcp0 = 0;
+    if (d_nodes) {
+        PSACX_HIP(c, hipMemcpyAsync(&lcp0, d_lcp, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+        PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    Pyramid<T> P;
+    unsigned long long* d_hist = nullptr; uint64_t *d_ln = nullptr, *d_rn = nullptr; uint32_t* bits = nullptr; T* lcp_copy = nullptr;
+    auto layout = [&](Arena& a) {
+        d_hist = a.take<unsigned long long>(256 + 1);          // the character counts, then the edge counter
+        if (!d_nodes) return;
+        bits = a.take<uint32_t>((n >> 5) + 1);
+        d_ln = a.take<uint64_t>(n); d_rn = a.take<uint64_t>(n);
+        if (lcp0 != 0) lcp_copy = a.take<T>(n);
+        nsv_pyramid_layout<T>(a, lcp_copy ? lcp_copy : d_lcp, n, P);
+    };
+    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
+    Arena ar(c->slab);
+    layout(ar);
+    CodeTable tab;
+    PSACX_TRY(tree_alphabet_dev(c, d_text, n, d_hist, tab, *sigma));
+    if (!d_nodes) return PSACX_OK;                    // size query
+    const uint64_t row = (uint64_t)*sigma + 2;
+    unsigned long long* d_edges = d_hist + 256;
+    PSACX_HIP(c, hipMemsetAsync(d_edges, 0, sizeof(unsigned long long), c->stream));
+    PSACX_HIP(c, hipMemsetAsync(d_nodes, 0, n * row * sizeof(unsigned long long), c->stream));
+    PSACX_TRY(string_ends_bitmap_dev(c, d_off, m, n, bits));
+    if (lcp_copy) {
+        PSACX_HIP(c, hipMemcpyAsync(lcp_copy, d_lcp, n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL((gst_clear_first_kernel<T>), dim3(1), dim3(1), 0, c->stream, lcp_copy);
+        PSACX_HIP(c, hipGetLastError());
+    }
+    for (int L = 1; L < P.nlev; ++L) {
+        hipLaunchKernelGGL((pyramid_level_kernel<T>), dim3(grid_for(c, P.len[L] * 64, 256, 8)), dim3(256), 0, c->stream,
+                           P.lvl[L - 1], P.len[L - 1], P.lvl[L], P.len[L]);
+        PSACX_HIP(c, hipGetLastError());
+    }
+    launch_ansv_tiles<T>(c, P, n, 2, 0, NSV_NONE, d_ln, d_rn);
+    PSACX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL((st_nodes_kernel<T, true>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, (const T*)P.lvl[0], n, d_sa, d_text, tab,
+                       row, d_ln, d_rn, reinterpret_cast<unsigned long long*>(d_nodes), d_edges, (const uint32_t*)bits);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long cnt = 0;
+    PSACX_HIP(c, hipMemcpyAsync(&cnt, d_edges, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (edges) *edges = cnt;
+    return PSACX_OK;
+}
+
+// The host-pointer form: the arrays are staged in device memory of their own (the slab belongs to the call above) and the table comes back.
+template <typename T>
+int suffix_tree_gsa_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* off, uint64_t m, const T* sa, const T* lcp,
+                         uint64_t* nodes, uint32_t* sigma) {
+    if (!c || !text || !sigma || n == 0) return PSACX_EINVAL;
+    if (nodes && (!sa || !lcp || !off)) return PSACX_EINVAL;
+    if (off) {
+        if (m == 0 || m > n || off[0] != 0 || off[m] != n) return PSACX_EINVAL;
+        for (uint64_t t = 1; t <= m; ++t) if (off[t] <= off[t - 1]) return PSACX_EINVAL;
+    }
+    PSACX_HIP(c, hipSetDevice(c->device));
+    unsigned long long hist[256] = {0};
+    for (uint64_t i = 0; i < n; ++i) ++hist[text[i]];
+    CodeTable tab;
+    tree_code_table(hist, tab, *sigma);
+    if (!nodes) return PSACX_OK;                      // size query
+    const uint64_t row = (uint64_t)*sigma + 2;
+    const size_t sizes[5] = {n, (m + 1) * sizeof(uint64_t), n * sizeof(T), n * sizeof(T), n * row * sizeof(uint64_t)};
+    const void* src[4] = {text, off, sa, lcp};
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int rc = PSACX_OK;
+    for (int k = 0; k < 5 && rc == PSACX_OK; ++k) {
+        const hipError_t e = hipMalloc(&d[k], sizes[k]);
+        if (e != hipSuccess) { c->hip_err = std::string("hipMalloc(string set): ") + hipGetErrorString(e); (void)hipGetLastError(); rc = PSACX_ENOMEM; }
+    }
+    auto step = [&](hipError_t r) { if (rc == PSACX_OK && r != hipSuccess) { c->hip_err = hipGetErrorString(r); (void)hipGetLastError(); rc = PSACX_EHIP; } };
+    for (int k = 0; k < 4 && rc == PSACX_OK; ++k) step(hipMemcpyAsync(d[k], src[k], sizes[k], hipMemcpyHostToDevice, c->stream));
+    if (rc == PSACX_OK) {
+        uint32_t sg = 0;
+        rc = suffix_tree_gsa_dev<T>(c, (const uint8_t*)d[0], n, (const uint64_t*)d[1], m, (const T*)d[2], (const T*)d[3], (uint64_t*)d[4], &sg, nullptr);
+    }
+    if (rc == PSACX_OK) step(hipMemcpyAsync(nodes, d[4], sizes[4], hipMemcpyDeviceToHost, c->stream));
+    step(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 5; ++k) if (d[k]) (void)hipFree(d[k]);
+    return rc;
+}
+
+int suffix_tree_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* lcp,
+                            uint64_t* nodes, uint32_t* sg, uint64_t* e) { return suffix_tree_gsa_dev<uint32_t>(c, t, n, off, m, sa, lcp, nodes, sg, e); }
+int suffix_tree_gsa_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* lcp,
+                            uint64_t* nodes, uint32_t* sg, uint64_t* e) { return suffix_tree_gsa_dev<uint64_t>(c, t, n, off, m, sa, lcp, nodes, sg, e); }
+int suffix_tree_gsa_host_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* lcp,
+                             uint64_t* nodes, uint32_t* sg) { return suffix_tree_gsa_host<uint32_t>(c, t, n, off, m, sa, lcp, nodes, sg); }
+int suffix_tree_gsa_host_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* lcp,
+                             uint64_t* nodes, uint32_t* sg) { return suffix_tree_gsa_host<uint64_t>(c, t, n, off, m, sa, lcp, nodes, sg); }
 
 int suffix_tree_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, const uint32_t* lcp, uint64_t* nodes, uint32_t* sg, uint64_t* e) {
     return suffix_tree_dev<uint32_t>(c, t, n, sa, lcp, nodes, sg, e);

@@ -159,6 +159,28 @@ int check_gsa_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t*
     return rc;
 }
 
+// The two steps of check_gsa_dev for the callers that keep the bitmap in their own workspace (the suffix tree of a string set, here and
+// in ansv.hip).  PSACX_EINVAL unless the m + 1 offsets start at 0, end at n and ascend strictly; uses the first bytes of the slab and waits.
+int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n) {
+    PSACX_TRY(ensure_slab(c, 4096));
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->slab);
+    PSACX_HIP(c, hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(check_offsets_kernel<0>, dim3(grid_for(c, m + 1, 256, 8)), dim3(256), 0, c->stream, d_off, m, n, d);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long bad = 0;
+    PSACX_HIP(c, hipMemcpyAsync(&bad, d, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    return bad ? PSACX_EINVAL : PSACX_OK;
+}
+
+// bits[(n >> 5) + 1] = the bitmap of the string ends of VALID offsets, queued on the ctx stream
+int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits) {
+    PSACX_HIP(c, hipMemsetAsync(bits, 0, ((n >> 5) + 1) * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(string_ends_bitmap_kernel, dim3(grid_for(c, m + 1, 256, 8)), dim3(256), 0, c->stream, d_off, m, bits);
+    PSACX_HIP(c, hipGetLastError());
+    return PSACX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Suffix-tree node table: is `nodes` the table of text / SA / LCP as given?  The rules are those of include/psacx.h
 // (psacx_check_suffix_tree_dev_*): head(), the leaf and the internal records are restated there without ANSV, and nothing
@@ -233,17 +255,35 @@ __device__ __forceinline__ uint64_t st_cell(const uint8_t* __restrict__ text, ui
     return (s < n && d < n - s) ? (uint64_t)tab.c[text[s + d]] : 0;
 }
 
-// cnt[0]: records, cnt[1]: records whose cell holds their id
-template <typename T>
+// The table of a string set (psacx_check_suffix_tree_gsa_dev_*): 0 where the string of the suffix at s has ended d characters on
+// (bits as above), and nothing is read unless s < n and s + d < n
+__device__ __forceinline__ uint64_t gst_cell(const uint8_t* __restrict__ text, uint64_t n, const uint32_t* __restrict__ bits, const CodeTable& tab,
+                                             uint64_t s, uint64_t d) {
+    if (s >= n || d >= n - s || (d > 0 && ends_at(bits, s + d))) return 0;
+    return (uint64_t)tab.c[text[s + d]];
+}
+
+// One record of a string set's table (a row of sigma + 2 cells) against the table: through a character it is matched iff cell 1 + c
+// holds its id; through the $ iff cells 0 and 1 hold a range lo <= id <= hi with lo != 0, and it then accounts for either cell that
+// holds its very id.  acc: the nonzero cells the matched records account for.
+__device__ __forceinline__ void gst_match(const unsigned long long* __restrict__ cells, uint64_t c, uint64_t id, unsigned& hit, unsigned& acc) {
+    if (c) { if (cells[1 + c] == id) { ++hit; ++acc; } return; }
+    const uint64_t lo = cells[0], hi = cells[1];
+    if (lo != 0 && lo <= id && id <= hi) { ++hit; acc += (unsigned)(id == lo) + (unsigned)(id == hi); }
+}
+
+// cnt[0]: records, cnt[1]: records whose cell holds their id; GSA (the table of a string set, bits = its string ends): cnt[1] the
+// matched records, cnt[3] the cells they account for
+template <typename T, bool GSA>
 __global__ __launch_bounds__(256) void st_check_kernel(Pyramid<T> P, uint64_t n, const T* __restrict__ SA, const uint8_t* __restrict__ text,
                                                        CodeTable tab, uint64_t row, const unsigned long long* __restrict__ nodes,
-                                                       unsigned long long* __restrict__ cnt) {
+                                                       unsigned long long* __restrict__ cnt, const uint32_t* __restrict__ bits) {
     const uint64_t wave_id = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) / WAVE;
     const unsigned lane = lane_id();
     const uint64_t ngroups = (n + 63) >> 6;
     const uint64_t below = (1ull << lane) - 1ull;
-    unsigned rec = 0, hit = 0;
+    unsigned rec = 0, hit = 0, acc = 0;
     for (uint64_t g = wave_id; g < ngroups; g += nwaves) {
         const uint64_t base = g << 6, i = base + lane;
         const bool in = i < n;
@@ -299,17 +339,21 @@ __global__ __launch_bounds__(256) void st_check_kernel(Pyramid<T> P, uint64_t n,
             uint64_t p = head, d = v;
             if (i + 1 < n && nxt > v) { p = i + 1; d = nxt; }
             ++rec;
-            if (nodes[p * row + st_cell(text, n, tab, sa, d)] == n + i) ++hit;
+            if (GSA) gst_match(nodes + p * row, gst_cell(text, n, bits, tab, sa, d), n + i, hit, acc);
+            else if (nodes[p * row + st_cell(text, n, tab, sa, d)] == n + i) ++hit;
         }
         if (!node) continue;
         const uint64_t p = by_r ? r : hl, d = by_r ? (uint64_t)rv : (uint64_t)lv;
         ++rec;
-        if (nodes[p * row + st_cell(text, n, tab, sa, d)] == i) ++hit;
+        if (GSA) gst_match(nodes + p * row, gst_cell(text, n, bits, tab, sa, d), i, hit, acc);
+        else if (nodes[p * row + st_cell(text, n, tab, sa, d)] == i) ++hit;
     }
     rec = wave_reduce<uint32_t>(rec, OpSum()); hit = wave_reduce<uint32_t>(hit, OpSum());
+    if (GSA) acc = wave_reduce<uint32_t>(acc, OpSum());
     if (lane == 0) {
         if (rec) atomicAdd(&cnt[0], (unsigned long long)rec);
         if (hit) atomicAdd(&cnt[1], (unsigned long long)hit);
+        if (GSA && acc) atomicAdd(&cnt[3], (unsigned long long)acc);
     }
 }
 
@@ -353,8 +397,8 @@ int check_suffix_tree_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const T
         hipLaunchKernelGGL((st_first_is_zero_kernel<T>), dim3(1), dim3(64), 0, c->stream, P);
         PSACX_HIP(c, hipGetLastError());
     }
-    hipLaunchKernelGGL((st_check_kernel<T>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, P, n, sa, text, tab, row,
-                       reinterpret_cast<const unsigned long long*>(nodes), cnt);
+    hipLaunchKernelGGL((st_check_kernel<T, false>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, P, n, sa, text, tab, row,
+                       reinterpret_cast<const unsigned long long*>(nodes), cnt, (const uint32_t*)nullptr);
     PSACX_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(count_nonzero_kernel, dim3(grid_for(c, n * row / 2 + 1, 256, 16)), dim3(256), 0, c->stream,
                        reinterpret_cast<const unsigned long long*>(nodes), n * row, cnt + 2);
@@ -363,6 +407,53 @@ int check_suffix_tree_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const T
     PSACX_HIP(c, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
     out[0] = h[0] - h[1]; out[1] = h[2] - h[1]; out[2] = h[0]; out[3] = h[2];
+    return PSACX_OK;
+}
+
+// The same for the table of a string set: check_suffix_tree_dev with the bitmap of the string ends beside the pyramid in the slab.
+template <typename T>
+int check_suffix_tree_gsa_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* d_off, uint64_t m, const T* sa, const T* lcp,
+                              const uint64_t* nodes, uint64_t* out) {
+    if (!c || !text || !d_off || !sa || !lcp || !nodes || !out || n == 0 || m == 0 || m > n) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    PSACX_TRY(string_offsets_valid_dev(c, d_off, m, n));
+    Pyramid<T> P;
+    unsigned long long* d = nullptr;                 // 256 character counts, then records / matched / nonzero cells / cells accounted for
+    uint32_t* bits = nullptr;
+    auto layout = [&](Arena& a) {
+        d = a.take<unsigned long long>(256 + 4);
+        bits = a.take<uint32_t>((n >> 5) + 1);
+        nsv_pyramid_layout<T>(a, lcp, n, P);
+    };
+    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
+    Arena ar(c->slab);
+    layout(ar);
+    CodeTable tab;
+    uint32_t sigma = 0;
+    PSACX_TRY(tree_alphabet_dev(c, text, n, d, tab, sigma));
+    const uint64_t row = (uint64_t)sigma + 2;
+    unsigned long long* cnt = d + 256;
+    PSACX_HIP(c, hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+    PSACX_TRY(string_ends_bitmap_dev(c, d_off, m, n, bits));
+    for (int L = 1; L < P.nlev; ++L) {
+        hipLaunchKernelGGL((pyramid_level_kernel<T>), dim3(grid_for(c, P.len[L] * 64, 256, 8)), dim3(256), 0, c->stream,
+                           P.lvl[L - 1], P.len[L - 1], P.lvl[L], P.len[L]);
+        PSACX_HIP(c, hipGetLastError());
+    }
+    if (P.nlev > 1) {
+        hipLaunchKernelGGL((st_first_is_zero_kernel<T>), dim3(1), dim3(64), 0, c->stream, P);
+        PSACX_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL((st_check_kernel<T, true>), dim3(grid_for(c, n, 256, 16)), dim3(256), 0, c->stream, P, n, sa, text, tab, row,
+                       reinterpret_cast<const unsigned long long*>(nodes), cnt, (const uint32_t*)bits);
+    PSACX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(count_nonzero_kernel, dim3(grid_for(c, n * row / 2 + 1, 256, 16)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const unsigned long long*>(nodes), n * row, cnt + 2);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long h[4] = {0, 0, 0, 0};
+    PSACX_HIP(c, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = h[0] - h[1]; out[1] = h[2] - h[3]; out[2] = h[0]; out[3] = h[2];
     return PSACX_OK;
 }
 
@@ -430,6 +521,11 @@ int check_suffix_tree_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const 
 int check_suffix_tree_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* lcp, const uint64_t* nodes, uint64_t* o) {
     return check_suffix_tree_dev<uint64_t>(c, t, n, sa, lcp, nodes, o);
 }
+
+int check_suffix_tree_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* lcp,
+                                  const uint64_t* nodes, uint64_t* o) { return check_suffix_tree_gsa_dev<uint32_t>(c, t, n, off, m, sa, lcp, nodes, o); }
+int check_suffix_tree_gsa_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* lcp,
+                                  const uint64_t* nodes, uint64_t* o) { return check_suffix_tree_gsa_dev<uint64_t>(c, t, n, off, m, sa, lcp, nodes, o); }
 
 int check_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* isa,
                       const uint32_t* lcp, uint64_t* e) { return check_gsa_dev<uint32_t>(c, t, n, off, m, sa, isa, lcp, e); }

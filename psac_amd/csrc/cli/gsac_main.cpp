@@ -1,5 +1,5 @@
 // gsac -- generalized suffix array of the lines of a file, the command line of
-// /root/reference/src/gsac.cpp:139-204:  gsac -f <file> [-l] [-c] [--check-device] [-o <basename>] [--device N]
+// /root/reference/src/gsac.cpp:139-204:  gsac -f <file> [-l] [-t] [-c] [--check-device] [-o <basename>] [--device N]
 // Strings are the runs between '\n' (src/gsac.cpp:170); positions count the characters with the
 // separators left out.  -o (extra) writes <basename>.sa64 / .lcp64 as psac does.
 //
@@ -9,6 +9,9 @@
 // --check-device (extra): the arrays go back to HBM and the device checker gives the verdict (psacx_check_gsa_dev_u64; with
 // --gpus / --gpus-on-device the distributed one, psacx_multi_check_gsa_dev_u64, on the ranks that built them): the same rules at sizes
 // the walk below does not reach.
+// -t (extra; implies -l): the generalized suffix tree's node table is built in HBM from the arrays (psacx_suffix_tree_gsa_dev_u64) and
+// its edge count and time are printed as psac -t prints them; with --check-device psacx_check_suffix_tree_gsa_dev_u64 gives a verdict on
+// the table too.  One GPU: with --gpus / --gpus-on-device it is an error.
 #include <cstring>
 #include <vector>
 
@@ -121,6 +124,44 @@ static bool check_gsa_on_device(suffix_array<char, index_t, LCP>& sa, const simp
     return true;
 }
 
+// gsac -t: text, offsets, SA and LCP go (back) to HBM, the table is built and stays there
+static bool tree_on_device(suffix_array<char, index_t, true>& sa, const simple_dstringset& ss, bool check_device) {
+    static_assert(sizeof(index_t) == 8, "the 64-bit entry points are called");
+    const uint64_t n = sa.n, m = ss.sizes.size();
+    std::vector<uint8_t> cat; cat.reserve(n);
+    std::vector<uint64_t> off(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) {
+        cat.insert(cat.end(), reinterpret_cast<const uint8_t*>(ss.str_begins[s]), reinterpret_cast<const uint8_t*>(ss.str_begins[s]) + ss.sizes[s]);
+        off.push_back(cat.size());
+    }
+    psacx_ctx* cx = sa.context();
+    DevBufs d(cx);
+    const uint8_t* t = (const uint8_t*)d.get(cat.data(), n);
+    const uint64_t* o = (const uint64_t*)d.get(off.data(), off.size() * 8);
+    const uint64_t* a = (const uint64_t*)d.get(sa.local_SA.data(), n * 8);
+    const uint64_t* l = (const uint64_t*)d.get(sa.local_LCP.data(), n * 8);
+    bench_cli::Clock clk;
+    uint32_t sigma = 0;
+    uint64_t edges = 0;
+    psacx::check(cx, psacx_suffix_tree_gsa_dev_u64(cx, t, n, o, m, nullptr, nullptr, nullptr, &sigma, nullptr));
+    void* p = nullptr;
+    psacx::check(cx, psacx_dev_alloc(cx, &p, n * ((uint64_t)sigma + 2) * sizeof(uint64_t)));
+    d.held.push_back(p);
+    psacx::check(cx, psacx_suffix_tree_gsa_dev_u64(cx, t, n, o, m, a, l, (uint64_t*)p, &sigma, &edges));
+    std::cerr << "ST time: " << clk.elapsed() << " ms" << std::endl;
+    std::cerr << "ST edges: " << edges << std::endl;
+    if (!check_device) return true;
+    uint64_t out[4] = {0, 0, 0, 0};
+    psacx::check(cx, psacx_check_suffix_tree_gsa_dev_u64(cx, t, n, o, m, a, l, (const uint64_t*)p, out));
+    if (out[0] | out[1] | (out[2] != edges)) {
+        std::cerr << "[ERROR] Suffix Tree is wrong: " << out[0] << " records not in their cell, " << out[1] << " cells without a record" << std::endl;
+        return false;
+    }
+    std::cout << "[SUCCESS] Suffix Tree is correct" << std::endl;
+    return true;
+}
+static bool tree_on_device(suffix_array<char, index_t, false>&, const simple_dstringset&, bool) { return true; }
+
 template <typename V> static void write_u64(const std::string& fn, const std::vector<V>& v) {
     std::ofstream f(fn.c_str(), std::ios::binary | std::ios::trunc);
     for (std::size_t i = 0; i < v.size(); ++i) { const uint64_t x = (uint64_t)v[i]; f.write(reinterpret_cast<const char*>(&x), 8); }
@@ -128,7 +169,7 @@ template <typename V> static void write_u64(const std::string& fn, const std::ve
 }
 
 template <bool LCP>
-static int run(const std::string& str, bool check, bool check_device, const std::string& out, int device, const std::vector<int>& devices) {
+static int run(const std::string& str, bool check, bool check_device, bool tree, const std::string& out, int device, const std::vector<int>& devices) {
     simple_dstringset ss(str.begin(), str.end(), psacx::comm(device), '\n');
     if (ss.sum_sizes == 0) { std::cerr << "error: no strings in the input" << std::endl; return EXIT_FAILURE; }
     psacx::alphabet<char> alpha = psacx::alphabet<char>::from_stringset(ss, psacx::comm(device));
@@ -139,6 +180,7 @@ static int run(const std::string& str, bool check, bool check_device, const std:
     std::cerr << "PSAC time: " << t.elapsed() << " ms" << std::endl;
     if (check && !check_gsa<LCP>(sa, ss)) return 1;
     if (check_device && !check_gsa_on_device<LCP>(sa, ss)) return 1;
+    if (tree && !tree_on_device(sa, ss, check_device)) return 1;
     if (!out.empty()) {
         write_u64(out + ".sa64", sa.local_SA);
         if (LCP) write_u64(out + ".lcp64", sa.local_LCP);
@@ -154,9 +196,9 @@ int main(int argc, char** argv) {
         for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
         --argc;
     }
-    bench_cli::Args a(argc, argv, "fo", "lc");
+    bench_cli::Args a(argc, argv, "fo", "lct");
     if (!a.ok || !a.has("-f")) {
-        std::cerr << "USAGE: gsac -f <filename> [-l] [-c] [--check-device] [-o <basename>] [--device N] [--gpus N] [--gpus-on-device D,N]\n"
+        std::cerr << "USAGE: gsac -f <filename> [-l] [-t] [-c] [--check-device] [-o <basename>] [--device N] [--gpus N] [--gpus-on-device D,N]\n"
                      "Parallel distributed generalized suffix array and LCP construction (MI355X engine)." << std::endl;
         return EXIT_FAILURE;
     }
@@ -172,9 +214,11 @@ int main(int argc, char** argv) {
             devices.assign((std::size_t)std::max(c == std::string::npos ? 1 : atoi(v.substr(c + 1).c_str()), 1), atoi(v.substr(0, c).c_str()));
         }
     }
+    const bool tree = a.has("-t");
+    if (tree && !devices.empty()) { std::cerr << "error: -t builds the tree on one GPU; it does not go with --gpus / --gpus-on-device" << std::endl; return EXIT_FAILURE; }
     try {
-        return a.has("-l") ? run<true>(str, a.has("-c"), check_device, a.str("-o"), device, devices)
-                           : run<false>(str, a.has("-c"), check_device, a.str("-o"), device, devices);
+        return a.has("-l") || tree ? run<true>(str, a.has("-c"), check_device, tree, a.str("-o"), device, devices)
+                                   : run<false>(str, a.has("-c"), check_device, false, a.str("-o"), device, devices);
     } catch (const std::exception& e) {
         std::cerr << "error: " << e.what() << std::endl;
         return EXIT_FAILURE;

@@ -27,6 +27,12 @@ int suffix_tree_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, c
 int suffix_tree_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t*, uint32_t*, uint64_t*);
 int check_suffix_tree_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, const uint32_t*, const uint64_t*, uint64_t*);
 int check_suffix_tree_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*);
+int suffix_tree_gsa_host_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint32_t*, const uint32_t*, uint64_t*, uint32_t*);
+int suffix_tree_gsa_host_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t*, uint32_t*);
+int suffix_tree_gsa_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint32_t*, const uint32_t*, uint64_t*, uint32_t*, uint64_t*);
+int suffix_tree_gsa_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t*, uint32_t*, uint64_t*);
+int check_suffix_tree_gsa_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint32_t*, const uint32_t*, const uint64_t*, uint64_t*);
+int check_suffix_tree_gsa_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*);
 int ansv_host_u32(psacx_ctx*, const uint32_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
 int ansv_host_u64(psacx_ctx*, const uint64_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
 int ansv_dev_u32(psacx_ctx*, const uint32_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
@@ -277,6 +283,19 @@ int psacx_check_suffix_tree_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, 
 int psacx_check_suffix_tree_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* lcp, const uint64_t* nodes, uint64_t* o) {
     return check_suffix_tree_dev_u64(c, t, n, sa, lcp, nodes, o);
 }
+
+int psacx_suffix_tree_gsa_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* lcp,
+                              uint64_t* nodes, uint32_t* sg) { return suffix_tree_gsa_host_u32(c, t, n, off, m, sa, lcp, nodes, sg); }
+int psacx_suffix_tree_gsa_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* lcp,
+                              uint64_t* nodes, uint32_t* sg) { return suffix_tree_gsa_host_u64(c, t, n, off, m, sa, lcp, nodes, sg); }
+int psacx_suffix_tree_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* lcp,
+                                  uint64_t* nodes, uint32_t* sg, uint64_t* e) { return suffix_tree_gsa_dev_u32(c, t, n, off, m, sa, lcp, nodes, sg, e); }
+int psacx_suffix_tree_gsa_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* lcp,
+                                  uint64_t* nodes, uint32_t* sg, uint64_t* e) { return suffix_tree_gsa_dev_u64(c, t, n, off, m, sa, lcp, nodes, sg, e); }
+int psacx_check_suffix_tree_gsa_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa,
+                                        const uint32_t* lcp, const uint64_t* nodes, uint64_t* o) { return check_suffix_tree_gsa_dev_u32(c, t, n, off, m, sa, lcp, nodes, o); }
+int psacx_check_suffix_tree_gsa_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa,
+                                        const uint64_t* lcp, const uint64_t* nodes, uint64_t* o) { return check_suffix_tree_gsa_dev_u64(c, t, n, off, m, sa, lcp, nodes, o); }
 
 int psacx_dev_alloc(psacx_ctx* c, void** out, uint64_t bytes) {
     if (!c || !out) return PSACX_EINVAL;

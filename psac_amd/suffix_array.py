@@ -276,6 +276,46 @@ def check_suffix_tree_device(ctx, d_text, n, d_sa, d_lcp, d_nodes, index_bits):
     return list(out)
 
 
+def suffix_tree_gsa(text, offsets, SA, LCP, ctx=None):
+    """construct_gst with gst_edgechars (suffix_tree.hpp:501-608) at one rank: the n x (sigma + 2) node table of a string set
+    (psacx_suffix_tree_gsa_* in include/psacx.h) from the characters of the strings back to back, their m + 1 offsets and the
+    SA / LCP construct_ss leaves (SuffixArray.string_offsets, local_SA, local_LCP)."""
+    if isinstance(text, str):
+        text = text.encode("latin-1")
+    t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    sa, lcp = np.ascontiguousarray(SA), np.ascontiguousarray(LCP)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_suffix_tree_gsa_u%d" % (sa.dtype.itemsize * 8))
+    sigma = C.c_uint32(0)
+    ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(off), off.size - 1, None, None, None, C.byref(sigma)))
+    nodes = np.zeros(t.size * (sigma.value + 2), np.uint64)
+    ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(off), off.size - 1, _ptr(sa), _ptr(lcp), _ptr(nodes), C.byref(sigma)))
+    return nodes.reshape(t.size, sigma.value + 2)
+
+
+def suffix_tree_gsa_device(ctx, d_text, n, d_off, m, d_sa, d_lcp, d_nodes, index_bits):
+    """psacx_suffix_tree_gsa_dev_*: the node table of suffix_tree_gsa() with every array resident in HBM (raw device addresses),
+    e.g. what psacx_construct_gsa_dev_* left there; d_off holds the m + 1 string offsets as uint64.  d_nodes receives
+    n x (sigma + 2) uint64 cells; with d_nodes=None only sigma is computed, to size it.  Returns (sigma, edges): edges = records
+    written, leaf + internal (0 for the query)."""
+    fn = getattr(ctx._lib, "psacx_suffix_tree_gsa_dev_u%d" % index_bits)
+    sigma, edges = C.c_uint32(0), C.c_uint64(0)
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_off) if d_off else None, int(m), C.c_void_p(d_sa) if d_sa else None,
+                 C.c_void_p(d_lcp) if d_lcp else None, C.c_void_p(d_nodes) if d_nodes else None, C.byref(sigma), C.byref(edges)))
+    return sigma.value, edges.value
+
+
+def check_suffix_tree_gsa_device(ctx, d_text, n, d_off, m, d_sa, d_lcp, d_nodes, index_bits):
+    """psacx_check_suffix_tree_gsa_dev_*: is the table at d_nodes the suffix tree of the string set / SA / LCP as given (all in
+    HBM)?  Returns [records not matched, nonzero cells no record accounts for, records, nonzero cells]; correct iff the first
+    two are zero.  SA and LCP themselves are check_gsa_device's business."""
+    out = (C.c_uint64 * 4)()
+    fn = getattr(ctx._lib, "psacx_check_suffix_tree_gsa_dev_u%d" % index_bits)
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_off), int(m), C.c_void_p(d_sa), C.c_void_p(d_lcp), C.c_void_p(d_nodes), out))
+    return list(out)
+
+
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
     """check_SA / check_lcp on buffers resident in HBM (check_suffix_array.hpp:56-126).  Returns the four
     error counters of psacx_check_dev_*; all zero means correct."""
