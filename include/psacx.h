@@ -89,6 +89,9 @@ typedef struct psacx_stats {
        leave early) into the caller's arrays, [4] Lc, [5] the call; SA and LCP leaving early (from the end of the first round):
        [6] when that began, [7] = [8] when both were through, since the call began */
     double ms_host[9];
+    /* psacx_locate_dev_* with PSACX_OPT_LOCATE_COUNT set, last call: [0] SA entries fetched, [1] text words fetched (8 bytes or less each, counted per load in either kernel shape);
+       a bisection step is one of the first and at least one of the second, each waiting for the one before it.  0 without the option. */
+    uint64_t locate_fetches[2];
 } psacx_stats;
 
 /* life cycle ------------------------------------------------------------- */
@@ -129,12 +132,14 @@ int psacx_trim(psacx_ctx* ctx);
  *   NO_EARLY_OUT      host-pointer calls: SA and LCP leave the device only when the construction has returned (default: from the moment the
  *                     first round has written them, under the SA -> ISA inversion; copied again if refinement rounds follow)
  *   NO_SPREAD_CURSORS the partition levels of the SA -> ISA path run their tiles in order (default: striped over several destination classes,
- *                     so that the workgroups running together do not all reserve and write inside one of them)                            */
+ *                     so that the workgroups running together do not all reserve and write inside one of them)
+ *   LOCATE_SHAPE      psacx_locate_*: 1 = one pattern per lane (the default), 2 = eight lanes per pattern, 64 characters per step (A/B runs)
+ *   LOCATE_COUNT      psacx_locate_*: the kernel counts its fetches into psacx_stats.locate_fetches (slower; tools/locate_time.py)          */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
-    PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_COUNT
+    PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
 /* Debug shim, the ONLY place where the library looks at the environment, and only when called: resets the options of ctx and sets those
@@ -386,6 +391,74 @@ int psacx_check_suffix_tree_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, u
                                         const uint32_t* d_SA, const uint32_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
 int psacx_check_suffix_tree_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_offsets, uint64_t m,
                                         const uint64_t* d_SA, const uint64_t* d_LCP, const uint64_t* d_nodes, uint64_t out[4]);
+
+/* pattern search ------------------------------------------------------------------
+ * Replaces sa_index::locate (seq_query.hpp:246-251) and the top-level lookup table lookup_index (lookup_table.hpp:36-149) for a
+ * text and its suffix array resident in HBM; desa-main -f ... -c -q ... (src/desa_main.cpp) is the reference's tool on top of them.
+ * One GPU.  The Lc-guided search of desa.hpp exists to avoid remote text reads and belongs with a distributed index.
+ *
+ * Definitions.  Text S[0..n), bytes compared as unsigned values.  Suffix i is S[i..n).  A pattern P has m >= 0 bytes.  Order is
+ * lexicographic, and a proper prefix is smaller.
+ *
+ *     lb(P) = #{ i : S[i..n) < P }
+ *     ub(P) = lb(P) + #{ i : P is a prefix of S[i..n) }
+ *
+ *  - For a correct SA, SA[lb..ub) are the occurrences of P.
+ *  - For the found cases this is what the reference's sa_index::locate returns (seq_query.hpp:246-251).
+ *  - If P does not occur, lb == ub == the insertion point.  The reference's faster indexes only promise first == second there.
+ *    This project pins the value, as it pins everything else.
+ *  - m == 0 gives [0, n).
+ *
+ * Lookup table.  code() is the alphabet code: 1..sigma in byte order of the bytes that occur in the text, and 0 for an absent byte
+ * and for positions past the end.  B = sigma + 1.
+ *
+ *     key_k(i) = sum over j < k of code(S[i+j]) * B^(k-1-j).
+ *
+ * The table has B^k + 1 entries of the index type.  table[v] = #{ i : key_k(i) < v }, so table[0] = 0, table[B^k] = n, and bucket
+ * v is SA[table[v] .. table[v+1]).
+ *  - This is lookup_index::table (lookup_table.hpp:36-149) with two changes.  The keys are dense: the reference packs bits_per_char
+ *    bits, which wastes 5/8 of a DNA table.  The sum is exclusive, with one entry more.
+ *  - k >= 1.  B^k > 2^30 returns PSACX_EINVAL.
+ *
+ * Use of the table by a pattern.  Let j = min(m, k).
+ *  - If any of P[0..j) has code 0, the table is not used for that pattern.  It is searched over [0, n).
+ *  - Otherwise v is the key of P[0..j) padded with zeros, and w = v + B^(k-j).
+ *     - For m <= k the answer is [table[v], table[w]) with no search.
+ *     - For m > k both bounds are searched inside [table[v], table[v+1]).  Comparisons may start at character k, because every
+ *       suffix in that bucket has at least k characters and shares them with P.
+ *
+ * Totality.
+ *  - Whatever SA and table hold, nothing is read out of range.  An SA entry >= n is compared as the empty suffix.  Table entries are
+ *    clamped to n, and a bucket with lo > hi is treated as empty.
+ *  - Every search terminates.
+ *  - On arrays that are no suffix array or table of the text, the answers are unspecified except lb <= ub <= n.
+ *
+ * psacx_lookup_table_dev_*: code[256] (host memory) receives code(), *sigma the alphabet size, *entries = B^k + 1; d_table == NULL
+ * only computes these three (the size query, as psacx_suffix_tree_dev_* has one; d_SA may be NULL then).  The alphabet comes from a
+ * histogram taken on the device.  The table is counted from the text -- a histogram of key_k over all positions and an exclusive
+ * scan, as lookup_table.hpp:60-140 -- so d_SA is not consulted and a wrong SA cannot leak into it.
+ * psacx_locate_dev_*: d_pat holds the q patterns back to back, d_poff (device memory) their q + 1 offsets; d_lb / d_ub receive q
+ * entries each.  d_table == NULL with k == 0 and code == NULL is the form without a table; any other mix of the three is
+ * PSACX_EINVAL.  poff[0] != 0 or a descending pair returns PSACX_EINVAL, checked on the device before any result is written; equal
+ * neighbours are empty patterns and legal.  q == 0 returns PSACX_OK.  Nothing is allocated per call beyond the 4 KiB of the ctx slab.
+ * psacx_locate_*: the host-pointer form; k == 0 means no table.  It stages text, SA and patterns, builds the table when k > 0,
+ * and copies the two result arrays back. */
+int psacx_lookup_table_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_SA, uint32_t k,
+                               uint32_t* d_table, uint16_t code[256], uint32_t* sigma, uint64_t* entries);
+int psacx_lookup_table_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA, uint32_t k,
+                               uint64_t* d_table, uint16_t code[256], uint32_t* sigma, uint64_t* entries);
+int psacx_locate_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_SA,
+                         const uint32_t* d_table, uint32_t k, const uint16_t code[256],
+                         const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                         uint32_t* d_lb, uint32_t* d_ub);
+int psacx_locate_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
+                         const uint64_t* d_table, uint32_t k, const uint16_t code[256],
+                         const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                         uint64_t* d_lb, uint64_t* d_ub);
+int psacx_locate_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint32_t* SA, const uint8_t* pat, const uint64_t* poff,
+                     uint64_t q, uint32_t k, uint32_t* lb, uint32_t* ub);
+int psacx_locate_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* SA, const uint8_t* pat, const uint64_t* poff,
+                     uint64_t q, uint32_t k, uint64_t* lb, uint64_t* ub);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

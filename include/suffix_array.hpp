@@ -22,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "psacx.h"
@@ -564,6 +565,39 @@ std::vector<std::size_t> construct_gst(suffix_array<char, index_t, true>& sa, si
     psacx::check(sa.context(), Call::run(sa.context(), text.data(), sa.n, off.data(), m, reinterpret_cast<const W*>(sa.local_SA.data()),
                                          reinterpret_cast<const W*>(sa.local_LCP.data()), reinterpret_cast<uint64_t*>(nodes.data()), &sigma));
     return nodes;
+}
+
+// sa_index::locate (seq_query.hpp:246-251 of the reference) for a batch of patterns: element i = [lb, ub) of patterns[i] in
+// sa.local_SA -- it occurs at local_SA[lb .. ub); where it does not occur, lb == ub is its insertion point (psacx.h: "pattern
+// search").  The text [begin, end) must be the bytes `sa` was constructed from.  k > 0 puts the k-mer lookup table of
+// lookup_table.hpp:36-149 in front of the searches; the answers are the same.  One rank only: there is no distributed form, and
+// none is emulated by gathering.
+template <typename index_t, bool LCP, bool LC, typename Iterator>
+std::vector<std::pair<index_t, index_t> > locate(suffix_array<char, index_t, LCP, LC>& sa, Iterator begin, Iterator end,
+                                                 const std::vector<std::string>& patterns, unsigned int k = 0) {
+    if (sa.multi_context()) throw std::runtime_error("psacx: locate needs a single-rank communicator (the search runs on one GPU)");
+    std::vector<uint8_t> text(begin, end);
+    if (text.size() != sa.n) throw std::runtime_error("locate: text does not match the suffix array");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* a, const uint8_t* p, const uint64_t* f, uint64_t q, uint32_t k,
+                       uint32_t* l, uint32_t* u) { return psacx_locate_u32(c, t, n, a, p, f, q, k, l, u); }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* a, const uint8_t* p, const uint64_t* f, uint64_t q, uint32_t k,
+                       uint64_t* l, uint64_t* u) { return psacx_locate_u64(c, t, n, a, p, f, q, k, l, u); }
+    };
+    std::vector<uint8_t> pat;
+    std::vector<uint64_t> off(1, 0);
+    for (std::size_t i = 0; i < patterns.size(); ++i) {
+        pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+        off.push_back(pat.size());
+    }
+    const uint64_t q = (uint64_t)patterns.size();
+    std::vector<W> lb(patterns.size()), ub(patterns.size());
+    psacx::check(sa.context(), Call::run(sa.context(), text.data(), sa.n, reinterpret_cast<const W*>(sa.local_SA.data()), pat.data(), off.data(), q,
+                                         (uint32_t)k, lb.data(), ub.data()));
+    std::vector<std::pair<index_t, index_t> > out(patterns.size());
+    for (std::size_t i = 0; i < patterns.size(); ++i) out[i] = std::make_pair((index_t)lb[i], (index_t)ub[i]);
+    return out;
 }
 
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -19,7 +19,7 @@ PSACX_MAX_ROUNDS = 72
 # psacx_configure options (include/psacx.h); Context.configure(force_diet=1, ...) takes them by name
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
            "widen_last": 8, "no_digit_bytes": 9, "no_bucket_sort": 10, "isa_update": 11, "gather": 12, "no_heavy": 13, "no_whole": 14, "no_lazy_ranks": 15, "no_early_out": 16,
-           "no_spread_cursors": 17}
+           "no_spread_cursors": 17, "locate_shape": 18, "locate_count": 19}
 MULTI_OPTIONS = {"layout": 1, "slab": 2, "output_slack": 3, "trace": 4, "wire_piece": 5, "pieces": 6, "check_chunks": 7, "global_refine_sort": 8,
                  "one_stage": 9, "two_word": 10, "one_word": 11, "no_slices": 12, "slice_wide": 13, "slice_shape": 14}
 MULTI_FORCE_WIRE, MULTI_NO_RCCL, MULTI_SHM = 1, 2, 4
@@ -41,6 +41,7 @@ EXPORTS = [
     "psacx_suffix_tree_gsa_u32", "psacx_suffix_tree_gsa_u64", "psacx_suffix_tree_gsa_dev_u32", "psacx_suffix_tree_gsa_dev_u64",
     "psacx_check_suffix_tree_gsa_dev_u32", "psacx_check_suffix_tree_gsa_dev_u64", "psacx_dev_alloc", "psacx_dev_free", "psacx_copy_h2d", "psacx_copy_d2h", "psacx_sync",
     "psacx_rand_dna", "psacx_synth_text_dev",
+    "psacx_lookup_table_dev_u32", "psacx_lookup_table_dev_u64", "psacx_locate_dev_u32", "psacx_locate_dev_u64", "psacx_locate_u32", "psacx_locate_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -69,7 +70,7 @@ class Stats(C.Structure):
                 ("scatter_launches", C.c_uint64 * 3), ("scatter_records", C.c_uint64 * 3),
                 ("scatter_bytes", C.c_uint64 * 3), ("hist_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64), ("onew_passes", C.c_uint64),
                 ("heavy_rounds", C.c_uint64), ("heavy_records", C.c_uint64), ("light_records", C.c_uint64), ("level_gathers", C.c_uint64),
-                ("ms_host", C.c_double * 9)]
+                ("ms_host", C.c_double * 9), ("locate_fetches", C.c_uint64 * 2)]
 
 
 class PsacxError(RuntimeError):
@@ -127,6 +128,10 @@ def load():
         getattr(lib, "psacx_suffix_tree_gsa_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint32)]
         getattr(lib, "psacx_suffix_tree_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_check_suffix_tree_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
+    for suf in ("u32", "u64"):
+        getattr(lib, "psacx_lookup_table_dev_" + suf).argtypes = [vp, vp, u64, vp, u32, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_locate_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, vp]
+        getattr(lib, "psacx_locate_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, vp, vp]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_gsa_dev_u32.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

@@ -1,0 +1,158 @@
+// locate -- batched pattern search on the MI355X engine, the counterpart of the reference's
+// `desa-main -f <text> -c -q <patterns>` (the reference's src/desa_main.cpp):
+//   locate -f <text> -q <patterns, one per line> [-k K] [--index 32|64|auto] [--device N] [-o file]
+// The text goes up once; the suffix array is constructed in HBM (psacx_construct_dev_*), the lookup table for -k K > 0 is built
+// there (psacx_lookup_table_dev_*) and the patterns are located there (psacx_locate_dev_*).  Prints "lb ub" per pattern -- the
+// occurrences are SA[lb..ub) -- to stdout or the file of -o, and "SA time:" / "Table time:" / "Locate time: <ms> ms" to stderr.
+// An empty line is the empty pattern.
+#include <chrono>
+#include <cstdlib>
+#include <fstream>
+#include <iostream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../../include/psacx.h"
+
+static void usage() {
+    std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--index 32|64|auto] [--device N] [-o <file>]\n"
+                 "Locates every pattern in the suffix array of the text (MI355X engine): prints lb ub per pattern, the occurrences are SA[lb..ub).\n";
+}
+
+static void must(psacx_ctx* c, int rc) {
+    if (rc == PSACX_OK) return;
+    std::string msg = std::string("psacx: ") + psacx_strerror(rc);
+    const char* detail = c ? psacx_last_hip_error(c) : "";
+    if (detail && detail[0]) msg += std::string(" [") + detail + "]";
+    throw std::runtime_error(msg);
+}
+
+static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, uint32_t* sa, uint32_t* isa) { return psacx_construct_dev_u32(c, t, n, 0, 0, sa, isa, nullptr); }
+static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, uint64_t* sa, uint64_t* isa) { return psacx_construct_dev_u64(c, t, n, 0, 0, sa, isa, nullptr); }
+static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
+    return psacx_lookup_table_dev_u32(c, t, n, sa, k, tab, code, sg, e);
+}
+static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, uint32_t k, uint64_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
+    return psacx_lookup_table_dev_u64(c, t, n, sa, k, tab, code, sg, e);
+}
+static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, const uint32_t* tab, uint32_t k, const uint16_t* code, const uint8_t* pat,
+                  const uint64_t* poff, uint64_t q, uint32_t* lb, uint32_t* ub) { return psacx_locate_dev_u32(c, t, n, sa, tab, k, code, pat, poff, q, lb, ub); }
+static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code, const uint8_t* pat,
+                  const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) { return psacx_locate_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, lb, ub); }
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+template <typename IT>
+static int run(const std::string& text, const std::string& pat, const std::vector<uint64_t>& poff, uint32_t k, int device, std::ostream& out) {
+    const uint64_t n = text.size(), q = poff.size() - 1;
+    psacx_ctx* c = nullptr;
+    must(nullptr, psacx_create(&c, device, nullptr));
+    std::vector<void*> held;
+    auto dev = [&](uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes)); held.push_back(p); return p; };
+    auto release = [&]() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); };
+    try {
+        auto t0 = std::chrono::steady_clock::now();
+        uint8_t* d_text = (uint8_t*)dev(n);
+        IT* d_sa = (IT*)dev(n * sizeof(IT));
+        IT* d_isa = (IT*)dev(n * sizeof(IT));
+        must(c, psacx_copy_h2d(c, d_text, text.data(), n));
+        must(c, construct(c, d_text, n, d_sa, d_isa));
+        std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+        uint16_t code[256];
+        IT* d_table = nullptr;
+        if (k) {
+            auto t1 = std::chrono::steady_clock::now();
+            uint32_t sigma = 0;
+            uint64_t entries = 0;
+            must(c, table(c, d_text, n, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries));
+            d_table = (IT*)dev(entries * sizeof(IT));
+            must(c, table(c, d_text, n, d_sa, k, d_table, code, &sigma, &entries));
+            std::cerr << "Table time: " << ms_since(t1) << " ms" << std::endl;
+            std::cerr << "Table entries: " << entries << std::endl;
+        }
+        std::vector<IT> lb(q), ub(q);
+        if (q) {
+            uint8_t* d_pat = (uint8_t*)dev(pat.size() + 1);
+            uint64_t* d_poff = (uint64_t*)dev((q + 1) * sizeof(uint64_t));
+            IT* d_lb = (IT*)dev(q * sizeof(IT));
+            IT* d_ub = (IT*)dev(q * sizeof(IT));
+            if (!pat.empty()) must(c, psacx_copy_h2d(c, d_pat, pat.data(), pat.size()));
+            must(c, psacx_copy_h2d(c, d_poff, poff.data(), (q + 1) * sizeof(uint64_t)));
+            auto t2 = std::chrono::steady_clock::now();
+            must(c, locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
+            std::cerr << "Locate time: " << ms_since(t2) << " ms" << std::endl;
+            must(c, psacx_copy_d2h(c, lb.data(), d_lb, q * sizeof(IT)));
+            must(c, psacx_copy_d2h(c, ub.data(), d_ub, q * sizeof(IT)));
+        }
+        for (uint64_t i = 0; i < q; ++i) out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i] << '\n';
+    } catch (...) {
+        release();
+        throw;
+    }
+    release();
+    return 0;
+}
+
+static bool read_file(const std::string& fn, std::string& into) {
+    std::ifstream f(fn.c_str(), std::ios::binary | std::ios::ate);
+    if (!f) return false;
+    into.resize((std::size_t)f.tellg());
+    f.seekg(0);
+    if (!into.empty()) f.read(&into[0], (std::streamsize)into.size());
+    return true;
+}
+
+int main(int argc, char** argv) {
+    std::string file, queries, outfile, index = "auto";
+    int device = 0;
+    long k = 0;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto need = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { std::cerr << "error: missing value for " << name << std::endl; usage(); exit(EXIT_FAILURE); }
+            return argv[++i];
+        };
+        if (a == "-f" || a == "--file") file = need("-f");
+        else if (a == "-q" || a == "--queries") queries = need("-q");
+        else if (a == "-k") k = atol(need("-k"));
+        else if (a == "-o" || a == "--outfile") outfile = need("-o");
+        else if (a == "--device") device = atoi(need("--device"));
+        else if (a == "--index") index = need("--index");
+        else if (a == "-h" || a == "--help") { usage(); return 0; }
+        else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
+    }
+    if (file.empty() || queries.empty() || k < 0 || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    std::string text, lines;
+    if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
+    if (!read_file(queries, lines)) { std::cerr << "error: cannot open " << queries << std::endl; return EXIT_FAILURE; }
+    if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
+    // one pattern per line; a last line without its newline counts
+    std::string pat;
+    std::vector<uint64_t> poff(1, 0);
+    for (std::size_t b = 0; b < lines.size();) {
+        std::size_t e = lines.find('\n', b);
+        if (e == std::string::npos) e = lines.size();
+        pat.append(lines, b, e - b);
+        poff.push_back(pat.size());
+        b = e + 1;
+    }
+    const bool use32 = index == "32" || (index == "auto" && text.size() < 0xFFFFFFFEull);
+    try {
+        std::ofstream f;
+        if (!outfile.empty()) {
+            f.open(outfile.c_str(), std::ios::trunc);
+            if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
+        }
+        std::ostream& out = outfile.empty() ? std::cout : f;
+        const int rc = use32 ? run<uint32_t>(text, pat, poff, (uint32_t)k, device, out) : run<uint64_t>(text, pat, poff, (uint32_t)k, device, out);
+        out.flush();
+        if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
+        return rc;
+    } catch (const std::exception& e) {
+        std::cerr << "error: " << e.what() << std::endl;
+        return EXIT_FAILURE;
+    }
+}

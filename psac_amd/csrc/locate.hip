@@ -1,0 +1,190 @@
+// locate.hip -- batched pattern search over a suffix array resident in HBM, and the k-mer lookup table in front of it
+// (include/psacx.h: "pattern search"; kernels in locate.hpp).
+//
+// Stands in for sa_index::locate (the reference's include/seq_query.hpp:246-251) and lookup_index (lookup_table.hpp:36-149),
+// which desa-main -c -q drives (src/desa_main.cpp).  One GPU; no LCP, Lc or RMQ is consulted: on one GPU the text is as near as
+// they are.
+#include "engine.hpp"
+#include "locate.hpp"
+
+namespace psacx {
+
+static const uint64_t LOCATE_MAX_KEYS = 1ull << 30;
+
+// B^k, or 0 if that exceeds LOCATE_MAX_KEYS
+static uint64_t key_space(uint32_t B, uint32_t k) {
+    uint64_t e = 1;
+    for (uint32_t i = 0; i < k; ++i) { e *= B; if (e > LOCATE_MAX_KEYS) return 0; }
+    return e;
+}
+
+// The table by counting: every text position adds one to the bin of its key, then the bins become their exclusive prefix sums.
+// The SA is not consulted -- the table is defined by the text alone and must not inherit a wrong SA.
+// tab / B = sigma + 1 / keys = B^k as table_alphabet left them; d_table has keys + 1 entries.  Queued on the ctx stream.
+template <typename T>
+static int lookup_table_fill(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k, uint32_t B, uint64_t keys, const CodeTable& tab, T* d_table) {
+    const uint64_t E = keys + 1;
+    const uint64_t nb = (E + 256 * LOCATE_SCAN_ITEMS - 1) / (256 * LOCATE_SCAN_ITEMS);
+    PSACX_TRY(ensure_slab(c, nb * sizeof(unsigned long long) + 4096));
+    unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(c->slab);
+    PSACX_HIP(c, hipMemsetAsync(d_table, 0, E * sizeof(T), c->stream));
+    const int grid = grid_for(c, (n + LOCATE_STRIP - 1) / LOCATE_STRIP, 256, 8);
+    if (E <= LOCATE_LDS_BINS)
+        hipLaunchKernelGGL((kmer_count_kernel<T, true>), dim3(grid), dim3(256), 0, c->stream, d_text, n, k, B, keys / B, tab, d_table, E);
+    else
+        hipLaunchKernelGGL((kmer_count_kernel<T, false>), dim3(grid), dim3(256), 0, c->stream, d_text, n, k, B, keys / B, tab, d_table, E);
+    PSACX_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL((scan_sums_kernel<T>), dim3((unsigned)nb), dim3(256), 0, c->stream, (const T*)d_table, E, d_sums);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), 0, c->stream, d_sums, nb);
+    hipLaunchKernelGGL((scan_apply_kernel<T>), dim3((unsigned)nb), dim3(256), 0, c->stream, d_table, E, (const unsigned long long*)d_sums);
+    PSACX_HIP(c, hipGetLastError());
+    return PSACX_OK;
+}
+
+// code(), sigma and B^k of a text resident in HBM (one device histogram); PSACX_EINVAL where B^k exceeds LOCATE_MAX_KEYS
+static int table_alphabet(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k, CodeTable& tab, uint32_t& sigma, uint64_t& keys) {
+    PSACX_TRY(ensure_slab(c, 4096));
+    PSACX_TRY(tree_alphabet_dev(c, d_text, n, reinterpret_cast<unsigned long long*>(c->slab), tab, sigma));
+    keys = key_space(sigma + 1, k);
+    return keys ? PSACX_OK : PSACX_EINVAL;
+}
+
+template <typename T>
+int lookup_table_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* /*d_SA*/, uint32_t k, T* d_table, uint16_t* code, uint32_t* sigma,
+                     uint64_t* entries) {
+    if (!c || !d_text || !code || !sigma || !entries || n == 0 || k == 0) return PSACX_EINVAL;
+    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    CodeTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    uint64_t keys = 0;
+    const int rc = table_alphabet(c, d_text, n, k, tab, *sigma, keys);
+    std::memcpy(code, tab.c, sizeof(tab.c));
+    PSACX_TRY(rc);
+    *entries = keys + 1;
+    if (!d_table) return PSACX_OK;                    // size query
+    PSACX_TRY(lookup_table_fill<T>(c, d_text, n, k, *sigma + 1, keys, tab, d_table));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    return PSACX_OK;
+}
+
+template <typename T, int G>
+static void launch_locate(psacx_ctx* c, bool count, const uint8_t* d_text, uint64_t n, const T* d_SA, const T* d_table, uint32_t k, uint32_t B,
+                          const CodeTable& tab, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb, T* d_ub,
+                          const unsigned long long* d_bad, unsigned long long* d_counters) {
+    const int grid = grid_for(c, q * G, 256, 8);
+    if (count)
+        hipLaunchKernelGGL((locate_kernel<T, G, true>), dim3(grid), dim3(256), 0, c->stream, d_text, n, d_SA, d_table, k, B, tab, d_pat, d_poff, q,
+                           d_lb, d_ub, d_bad, d_counters);
+    else
+        hipLaunchKernelGGL((locate_kernel<T, G, false>), dim3(grid), dim3(256), 0, c->stream, d_text, n, d_SA, d_table, k, B, tab, d_pat, d_poff, q,
+                           d_lb, d_ub, d_bad, d_counters);
+}
+
+template <typename T>
+int locate_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_SA, const T* d_table, uint32_t k, const uint16_t* code,
+               const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb, T* d_ub) {
+    if (!c) return PSACX_EINVAL;
+    if ((d_table == nullptr) != (k == 0) || (code == nullptr) != (k == 0)) return PSACX_EINVAL;
+    if (q == 0) return PSACX_OK;
+    if (!d_text || !d_SA || !d_pat || !d_poff || !d_lb || !d_ub || n == 0) return PSACX_EINVAL;
+    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
+    CodeTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    uint32_t B = 1;
+    if (k) {
+        std::memcpy(tab.c, code, sizeof(tab.c));
+        for (int ch = 0; ch < 256; ++ch) B = std::max<uint32_t>(B, (uint32_t)tab.c[ch] + 1);
+        if (B < 2 || key_space(B, k) == 0) return PSACX_EINVAL;
+    }
+    PSACX_HIP(c, hipSetDevice(c->device));
+    PSACX_TRY(ensure_slab(c, 4096));
+    unsigned long long* d_words = reinterpret_cast<unsigned long long*>(c->slab);      // [0] malformed offsets, [1], [2] the fetch counters
+    PSACX_HIP(c, hipMemsetAsync(d_words, 0, 3 * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(locate_offsets_kernel, dim3(grid_for(c, q, 256, 8)), dim3(256), 0, c->stream, d_poff, q, d_words);
+    PSACX_HIP(c, hipGetLastError());
+    const bool count = c->knobs.locate_count;
+    if (c->knobs.locate_shape == 2)
+        launch_locate<T, 8>(c, count, d_text, n, d_SA, d_table, k, B, tab, d_pat, d_poff, q, d_lb, d_ub, d_words, d_words + 1);
+    else
+        launch_locate<T, 1>(c, count, d_text, n, d_SA, d_table, k, B, tab, d_pat, d_poff, q, d_lb, d_ub, d_words, d_words + 1);
+    PSACX_HIP(c, hipGetLastError());
+    unsigned long long words[3] = {0, 0, 0};
+    PSACX_HIP(c, hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (words[0]) return PSACX_EINVAL;                // poff[0] != 0 or a descending pair: the kernel wrote nothing
+    c->stats.locate_fetches[0] = words[1];
+    c->stats.locate_fetches[1] = words[2];
+    return PSACX_OK;
+}
+
+// The host-pointer form: everything is staged in device memory of its own for the time of the call (the slab belongs to the calls
+// above), the table is built when k > 0, and the two result arrays come back.
+template <typename T>
+int locate_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const T* SA, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k,
+                T* lb, T* ub) {
+    if (!c) return PSACX_EINVAL;
+    if (q == 0) return PSACX_OK;
+    if (!text || !SA || !poff || !lb || !ub || n == 0) return PSACX_EINVAL;
+    if (poff[0] != 0) return PSACX_EINVAL;
+    for (uint64_t i = 0; i < q; ++i) if (poff[i + 1] < poff[i]) return PSACX_EINVAL;
+    if (poff[q] && !pat) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    enum { TEXT, SA_, PAT, POFF, LB, UB, TABLE, NBUF };
+    size_t sizes[NBUF] = {n, n * sizeof(T), poff[q] ? poff[q] : 1, (q + 1) * sizeof(uint64_t), q * sizeof(T), q * sizeof(T), 0};
+    const void* src[4] = {text, SA, pat, poff};
+    void* d[NBUF] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int rc = PSACX_OK;
+    auto alloc = [&](int b) {
+        if (rc != PSACX_OK) return;
+        const hipError_t e = hipMalloc(&d[b], sizes[b]);
+        if (e != hipSuccess) { c->hip_err = std::string("hipMalloc(locate): ") + hipGetErrorString(e); (void)hipGetLastError(); rc = PSACX_ENOMEM; }
+    };
+    auto step = [&](hipError_t r) { if (rc == PSACX_OK && r != hipSuccess) { c->hip_err = hipGetErrorString(r); (void)hipGetLastError(); rc = PSACX_EHIP; } };
+    for (int b = TEXT; b <= UB; ++b) alloc(b);
+    for (int b = TEXT; b <= POFF && rc == PSACX_OK; ++b)
+        if (src[b] && (b != PAT || poff[q])) step(hipMemcpyAsync(d[b], src[b], b == PAT ? (size_t)poff[q] : sizes[b], hipMemcpyHostToDevice, c->stream));
+    CodeTable tab;
+    if (rc == PSACX_OK && k) {                        // one histogram for the alphabet, then the table sized by it
+        uint32_t sigma = 0;
+        uint64_t keys = 0;
+        rc = table_alphabet(c, (const uint8_t*)d[TEXT], n, k, tab, sigma, keys);
+        if (rc == PSACX_OK) { sizes[TABLE] = (keys + 1) * sizeof(T); alloc(TABLE); }
+        if (rc == PSACX_OK) rc = lookup_table_fill<T>(c, (const uint8_t*)d[TEXT], n, k, sigma + 1, keys, tab, (T*)d[TABLE]);
+    }
+    if (rc == PSACX_OK)
+        rc = locate_dev<T>(c, (const uint8_t*)d[TEXT], n, (const T*)d[SA_], (const T*)d[TABLE], k, k ? tab.c : nullptr, (const uint8_t*)d[PAT],
+                           (const uint64_t*)d[POFF], q, (T*)d[LB], (T*)d[UB]);
+    if (rc == PSACX_OK) {
+        step(hipMemcpyAsync(lb, d[LB], sizes[LB], hipMemcpyDeviceToHost, c->stream));
+        step(hipMemcpyAsync(ub, d[UB], sizes[UB], hipMemcpyDeviceToHost, c->stream));
+    }
+    step(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < NBUF; ++b) if (d[b]) (void)hipFree(d[b]);
+    return rc;
+}
+
+} // namespace psacx
+
+using namespace psacx;
+
+extern "C" {
+
+int psacx_lookup_table_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, uint32_t k, uint32_t* table, uint16_t code[256],
+                               uint32_t* sigma, uint64_t* entries) { return lookup_table_dev<uint32_t>(c, t, n, sa, k, table, code, sigma, entries); }
+int psacx_lookup_table_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, uint32_t k, uint64_t* table, uint16_t code[256],
+                               uint32_t* sigma, uint64_t* entries) { return lookup_table_dev<uint64_t>(c, t, n, sa, k, table, code, sigma, entries); }
+int psacx_locate_dev_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, const uint32_t* table, uint32_t k, const uint16_t code[256],
+                         const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t* lb, uint32_t* ub) {
+    return locate_dev<uint32_t>(c, t, n, sa, table, k, code, pat, poff, q, lb, ub);
+}
+int psacx_locate_dev_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* table, uint32_t k, const uint16_t code[256],
+                         const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) {
+    return locate_dev<uint64_t>(c, t, n, sa, table, k, code, pat, poff, q, lb, ub);
+}
+int psacx_locate_u32(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k,
+                     uint32_t* lb, uint32_t* ub) { return locate_host<uint32_t>(c, t, n, sa, pat, poff, q, k, lb, ub); }
+int psacx_locate_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k,
+                     uint64_t* lb, uint64_t* ub) { return locate_host<uint64_t>(c, t, n, sa, pat, poff, q, k, lb, ub); }
+
+} // extern "C"

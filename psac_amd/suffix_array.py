@@ -316,6 +316,62 @@ def check_suffix_tree_gsa_device(ctx, d_text, n, d_off, m, d_sa, d_lcp, d_nodes,
     return list(out)
 
 
+def pattern_buffer(patterns):
+    """The layout psacx_locate_* takes: (the patterns back to back as uint8, their q + 1 offsets as uint64).  A pattern is bytes, a str
+    (latin-1) or an array of bytes; an empty one is legal."""
+    parts = [np.frombuffer(x.encode("latin-1") if isinstance(x, str) else bytes(x), dtype=np.uint8) if isinstance(x, (str, bytes, bytearray))
+             else np.ascontiguousarray(x, dtype=np.uint8) for x in patterns]
+    off = np.zeros(len(parts) + 1, np.uint64)
+    if parts:
+        off[1:] = np.cumsum([p.size for p in parts])
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), off
+
+
+def lookup_table_device(ctx, d_text, n, d_sa, k, d_table, index_bits):
+    """psacx_lookup_table_dev_*: the k-mer lookup table of a text resident in HBM (lookup_index, lookup_table.hpp:36-149, with dense
+    keys; include/psacx.h defines it).  d_table receives B^k + 1 entries of the index type, B = sigma + 1; with d_table=None only
+    the sizes are computed (d_sa may be None then).  Returns (code, sigma, entries): code = the 256 alphabet codes as uint16,
+    which locate_device takes."""
+    fn = getattr(ctx._lib, "psacx_lookup_table_dev_u%d" % index_bits)
+    code = np.zeros(256, np.uint16)
+    sigma, entries = C.c_uint32(0), C.c_uint64(0)
+    ctx._pre()
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_sa) if d_sa else None, int(k), C.c_void_p(d_table) if d_table else None,
+                 _ptr(code), C.byref(sigma), C.byref(entries)))
+    return code, sigma.value, entries.value
+
+
+def locate_device(ctx, d_text, n, d_sa, d_table, k, code, d_pat, d_poff, q, d_lb, d_ub, index_bits):
+    """psacx_locate_dev_*: [lb, ub) of q patterns in the suffix array at d_sa (sa_index::locate, seq_query.hpp:246-251), everything
+    resident in HBM (raw device addresses): d_pat the patterns back to back, d_poff their q + 1 uint64 offsets, d_lb / d_ub q entries
+    of the index type each.  d_table / k / code as lookup_table_device left them, or None / 0 / None for the search without a table."""
+    fn = getattr(ctx._lib, "psacx_locate_dev_u%d" % index_bits)
+    cd = None if code is None else np.ascontiguousarray(code, dtype=np.uint16)
+    ctx._pre()
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_sa), C.c_void_p(d_table) if d_table else None, int(k),
+                 _ptr(cd) if cd is not None else None, C.c_void_p(d_pat), C.c_void_p(d_poff), int(q), C.c_void_p(d_lb), C.c_void_p(d_ub)))
+
+
+def locate(text, SA, patterns, k=0, ctx=None):
+    """psacx_locate_*: (lb, ub) arrays -- pattern i occurs at SA[lb[i]:ub[i]]; where it does not occur lb[i] == ub[i] is its insertion
+    point -- for a list of patterns (bytes, str or byte arrays) in the suffix array SA of text.  k > 0 builds the k-mer lookup table
+    first and starts every search in its bucket; the answers are the same.  Host arrays; everything is staged for the call."""
+    if isinstance(text, str):
+        text = text.encode("latin-1")
+    t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    sa = np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("locate needs a uint32 or uint64 suffix array")
+    pat, off = pattern_buffer(patterns)
+    q = int(off.size - 1)
+    lb, ub = np.zeros(q, sa.dtype), np.zeros(q, sa.dtype)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_locate_u%d" % (sa.dtype.itemsize * 8))
+    ctx._pre()
+    ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), _ptr(lb), _ptr(ub)))
+    return lb, ub
+
+
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
     """check_SA / check_lcp on buffers resident in HBM (check_suffix_array.hpp:56-126).  Returns the four
     error counters of psacx_check_dev_*; all zero means correct."""
