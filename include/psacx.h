@@ -92,6 +92,8 @@ typedef struct psacx_stats {
     /* psacx_locate_dev_* with PSACX_OPT_LOCATE_COUNT set, last call: [0] SA entries fetched, [1] text words fetched (8 bytes or less each, counted per load in either kernel shape);
        a bisection step is one of the first and at least one of the second, each waiting for the one before it.  0 without the option. */
     uint64_t locate_fetches[2];
+    uint64_t rebucket_1w;          /* 1 when the first round of the last construction ran rebucket_first_1w_kernel, the 32-bit form of the rebucket kernel on
+                                      one-word records, 0 when it ran the generic rebucket_first_kernel */
 } psacx_stats;
 
 /* life cycle ------------------------------------------------------------- */
@@ -134,12 +136,14 @@ int psacx_trim(psacx_ctx* ctx);
  *   NO_SPREAD_CURSORS the partition levels of the SA -> ISA path run their tiles in order (default: striped over several destination classes,
  *                     so that the workgroups running together do not all reserve and write inside one of them)
  *   LOCATE_SHAPE      psacx_locate_*: 1 = one pattern per lane (the default), 2 = eight lanes per pattern, 64 characters per step (A/B runs)
- *   LOCATE_COUNT      psacx_locate_*: the kernel counts its fetches into psacx_stats.locate_fetches (slower; tools/locate_time.py)          */
+ *   LOCATE_COUNT      psacx_locate_*: the kernel counts its fetches into psacx_stats.locate_fetches (slower; tools/locate_time.py)
+ *   GENERIC_REBUCKET  the first round on one-word records runs the generic rebucket kernel, not its 32-bit form (A/B runs)          */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
-    PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_COUNT
+    PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
+    PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
 /* Debug shim, the ONLY place where the library looks at the environment, and only when called: resets the options of ctx and sets those

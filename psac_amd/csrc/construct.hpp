@@ -402,6 +402,7 @@ template <typename T> struct IsaLevels {
     // skip (split rounds, heavy_keys.hpp): per scan tile of the list whether it lies inside a heavy run that keeps its rank -- tiles of such entries are left out
     int add(const uint64_t* pairs, uint64_t cnt, const ulonglong2* skip = nullptr) {
         static_assert((PB * PI) % ScanCfg<T>::TILE == 0 || sizeof(T) != 8, "a tile of pairs covers whole scan tiles");
+        static_assert((PB * PI) / ScanCfg<T>::TILE == 2 || sizeof(T) != 8, "rebucket_pure_kernel finds the other scan tile of a tile of pairs as tile ^ 1");
         hipLaunchKernelGGL((partition_packed_kernel<T, PB, PI, 0, CB>), dim3(striped_grid((cnt + PB * PI - 1) / (PB * PI), stripes)), dim3(PB), 0, c->stream, (const T*)nullptr,
                            (const T*)nullptr, pairs, lvl_a, cnt, isa_narrow_shift(lv9, 0), lv9 == 1 ? c1() : c0(), (uint64_t)0, (const unsigned*)nullptr, 0u,
                            (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, skip, skip ? (unsigned)((PB * PI) / ScanCfg<T>::TILE) : 0u, stripes);
@@ -899,6 +900,19 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
                 PSACX_TRY(scan_carries<T>(c, w, ntiles));
                 PSACX_HIP(c, hipMemsetAsync(w.d_cursors, 0, ((size_t)1 << ISA_NARROW_CB) * sizeof(unsigned) + sizeof(unsigned), c->stream));
                 lazy_ids = n >= (1ull << 22);
+                // the lean 32-bit kernel where its assumptions hold (rebucket_1w_math.hpp: rb1w_fits); PSACX_OPT_GENERIC_REBUCKET pins the generic one.
+                // Its gain is its third workgroup per CU: 80 VGPRs and no scratch, which the compiler reaches only with the two opaque values of
+                // rb1w_fresh (sa_kernels.hpp).  After a change of the kernel or of the compiler, look at the resource remark of the gfx950 build
+                // (-Rpass-analysis=kernel-resource-usage; figures in DESIGN.md 3.3) and at the A/B of profiles/rebucket_1w_ab.txt.
+                if (!kn.generic_rebucket && rb1w_fits(ks.lc, ks.c1, ks.c2, onew_view.low, onew_view.sfield, n)) {
+                    c->stats.rebucket_1w = 1;
+                    hipLaunchKernelGGL((rebucket_first_1w_kernel<RB1W_BLOCK, ScanCfg<T>::TILE / RB1W_BLOCK, WITH_LCP, ISA_NARROW_CB>), dim3((unsigned)ntiles), dim3(RB1W_BLOCK), 0,
+                                       c->stream, reinterpret_cast<const uint64_t*>(sorted.k1), reinterpret_cast<const uint64_t*>(onew_w1),
+                                       reinterpret_cast<const uint64_t*>(sorted.k2), n, onew_view, rb1w_shape(ks.lc, ks.c1, ks.c2, onew_view.low, onew_view.sfield, n),
+                                       reinterpret_cast<uint64_t*>(w.bsa), reinterpret_cast<uint64_t*>(d_lcp), w.d_carry, w.d_nact, w.d_nunf,
+                                       reinterpret_cast<uint64_t*>(pyr1), reinterpret_cast<uint64_t*>(w.x.v),
+                                       isa_narrow_shift(isa_narrow_levels<T>(n, kn), 0), w.d_cursors, reinterpret_cast<uint64_t*>(d_sa), lazy_ids ? 1 : 0);
+                } else
                 hipLaunchKernelGGL((rebucket_first_kernel<T, RB1W_BLOCK, ScanCfg<T>::TILE / RB1W_BLOCK, WITH_LCP, false, ISA_NARROW_CB, true, true>), dim3((unsigned)ntiles),
                                    dim3(RB1W_BLOCK), 0, c->stream, sorted.k1, sorted.k2, (const T*)nullptr, n, ks, w.bsa, d_lcp, w.d_carry, w.d_nact, w.d_nunf, n,
                                    Boundary<T>(), pyr1, (unsigned*)nullptr, 0, reinterpret_cast<uint32_t*>(w.x.v), (uint32_t*)nullptr,

@@ -62,6 +62,8 @@ struct Knobs {
                                   // tie stage's radix path and the multi-GPU engine read) although the kernels after the sort could read one-word records
     bool no_spread_cursors = false; // PSACX_OPT_NO_SPREAD_CURSORS: the packed partition levels of the SA -> ISA path run their tiles in order, every resident workgroup
                                   // in one parent class (construct.hpp: isa_stripes; A/B runs)
+    bool generic_rebucket = false; // PSACX_OPT_GENERIC_REBUCKET: the first round on one-word records runs rebucket_first_kernel, not its 32-bit form rebucket_first_1w_kernel
+                                  // (sa_kernels.hpp; parity suite and A/B runs)
     int locate_shape = 0;         // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (locate.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
 };

@@ -28,6 +28,7 @@ namespace psacx {
 constexpr unsigned HEAVY_MAXB = 4096;
 constexpr unsigned HEAVY_PAD = 1;                 // stride of the per-bucket reservation counters in words: thread b of a workgroup adds to counter b, so a wave's 64 atomics go to
                                                   // eight lines and are combined per line (tools/ubench_atomic.hip: 43 - 170 G atomics/s side by side, 24 G/s on a line each)
+static_assert(HEAVY_PAD == 1, "HeavyView (sa_kernels.hpp) reads the counters as eq[b]");
 
 struct HeavyTabs {
     uint64_t* bstart;          // [nb + 1] first list entry of every bucket

@@ -19,6 +19,7 @@
 #endif
 #include <type_traits>
 #include "dev_common.hpp"
+#include "rebucket_1w_math.hpp"
 
 namespace psacx {
 
@@ -1128,6 +1129,289 @@ __global__ __launch_bounds__(BLOCK) RB_WAVES_ATTR void rebucket_first_kernel(
                 const unsigned p = tid + j * BLOCK;
                 if (p < count) part_val[dest[j]] = (uint32_t)stage[p];
             }
+        }
+    }
+}
+
+// load_run_x / store_run_x (dev_common.hpp) for runs of eight 64-bit entries, with the places inside the wave's LDS region written as one
+// base per thread plus constants (slot e + e / 8: a run starts at 9 * lane, row i at 72 * i + lane + lane / 8), and the values to store
+// made by a functor one at a time, so that no array of eight 64-bit values has to exist beside the rows
+template <typename F>
+__device__ __forceinline__ void rb1w_store_run(uint64_t* __restrict__ p, uint64_t wb, uint64_t n, unsigned lane, uint64_t* xw, F f) {
+    constexpr int ITEMS = 8, ROW = WAVE + WAVE / 8;
+    uint64_t* const run = xw + lane * (ITEMS + 1);
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) run[j] = f(j);
+    xrun_order();
+    const uint64_t* const rows = xw + lane + (lane >> 3);
+    uint64_t r[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) r[i] = rows[i * ROW];
+    xrun_order();
+    uint64_t* __restrict__ q = p + wb + lane;
+    if (wb + (uint64_t)WAVE * ITEMS <= n) {
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) q[i * WAVE] = r[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) if (wb + (uint64_t)i * WAVE + lane < n) q[i * WAVE] = r[i];
+    }
+}
+// a value the compiler takes as new: what is computed from it is computed again instead of being kept in registers from an earlier phase
+__device__ __forceinline__ unsigned rb1w_fresh(unsigned x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ unsigned rb1w_fresh_uniform(unsigned x) { asm volatile("" : "+s"(x)); return x; }
+
+// ------------------------------------------------------------------ K6 + K7, first round, one-word records of at most 2^32 suffixes
+// rebucket_first_kernel<uint64_t, BLOCK, ITEMS, WITH_LCP, false, PCB, true, true> without a Boundary (one GPU), with sa_out, and nothing
+// 64-bit in a per-record register array (the generic form holds word 1, word 2, suffix, id and LCP of every record as 64-bit values, 113
+// VGPRs, two workgroups per CU).  A record is kept as the 32-bit rest of its prefix and its 32-bit suffix; its bucket is only looked at
+// where a thread's run meets a bucket border (at most 255 places in the whole array).  Neighbours with different rests in one bucket get
+// their LCP from a 32-bit clz (rebucket_1w_math.hpp); neighbours with equal leading parts are the tied records, whose two words are
+// read from S1t / S2 there and then.  Ids are not kept: a record's rank (id - 1, 32 bits) is its own position at a head and the last
+// head's elsewhere, and the scan over the tile runs on tile-local head positions.  LCP values travel as bytes (2k <= 255) and are
+// widened at the store.  What it writes is what the generic kernel writes, up to the order of the pairs inside a destination class.
+// The neighbours of a run come from the lanes beside it (LDS between waves, one load per tile edge) instead of two loads per thread.
+template <int BLOCK, int ITEMS, bool WITH_LCP, int PCB = 9>
+__global__ __launch_bounds__(BLOCK, 6) void rebucket_first_1w_kernel(
+    const uint64_t* __restrict__ S1, const uint64_t* __restrict__ S1t, const uint64_t* __restrict__ S2, uint64_t n, OneWordView ow, Rb1wShape sh,
+    uint64_t* __restrict__ Bsa, uint64_t* __restrict__ LCP, const uint64_t* __restrict__ carry_in, uint64_t* __restrict__ n_active,
+    uint64_t* __restrict__ n_unf, uint64_t* __restrict__ pyr1, uint64_t* __restrict__ part_out, unsigned part_shift,
+    unsigned* __restrict__ part_cursors, uint64_t* __restrict__ sa_out, int lazy_ids) {
+    constexpr int TILE = BLOCK * ITEMS, NW = BLOCK / WAVE, NCLS = 1 << PCB;
+    static_assert(ITEMS == 8, "eight LCP bytes in two words, eight head flags and the next one in a mask");
+    static_assert(BLOCK >= 257 && BLOCK >= NCLS, "one thread per table entry and per class");
+    static_assert(TILE < (1 << 16), "both counters of a tile reduced in one word");
+    static_assert(64 % ITEMS == 0, "a group of 64 entries must sit inside one wave");
+    constexpr size_t XP_RUNS = sizeof(uint64_t) * NW * XRUN_WORDS<ITEMS>::N, XP_STAGE = sizeof(uint64_t) * (size_t)TILE;
+    __shared__ __attribute__((aligned(16))) unsigned char xp_raw[XP_RUNS > XP_STAGE ? XP_RUNS : XP_STAGE];
+    __shared__ unsigned long long s_off[257];
+    __shared__ uint32_t s_last[NW][2];          // the last record of every wave (rest, suffix): the predecessor of the next wave's first
+    __shared__ unsigned s_scan[NW], s_h0[NW], s_cnt[NW];
+    __shared__ unsigned pcnt[NCLS], pstart[NCLS], pscan_tmp[NW + 1];
+    __shared__ uint64_t pbase[NCLS];
+    const unsigned tid = threadIdx.x, lane = lane_id(), wave = tid / WAVE;
+    const unsigned tile = blockIdx.x;
+    const uint64_t tbase = (uint64_t)tile * TILE;
+    const uint64_t e0 = tbase + (uint64_t)tid * ITEMS;
+    uint64_t* const xw = reinterpret_cast<uint64_t*>(xp_raw) + wave * XRUN_WORDS<ITEMS>::N;
+    // valid records of this run
+    const unsigned nv = e0 + ITEMS <= n ? (unsigned)ITEMS : (e0 < n ? (unsigned)(n - e0) : 0u);
+    const unsigned vmask = (1u << nv) - 1u;
+    const bool have_p = e0 > 0;
+
+    // (everything that has a long way from memory is asked for first)
+    const unsigned long long my_off = tid < 257 ? ow.off[tid] : 0ull;
+    const uint64_t carry64 = carry_in[tile];
+    uint64_t xprev = 0, xnext = 0;
+    if (tid == 0 && have_p) xprev = S1[e0 - 1];
+    const bool have_tq = tid == BLOCK - 1 && e0 + ITEMS < n;
+    if (have_tq) xnext = S1[e0 + ITEMS];
+    uint32_t rest[ITEMS], sa[ITEMS];
+    {
+        uint64_t x[ITEMS];
+        load_run_x<uint64_t, ITEMS>(S1, e0, n, x, 0ull, xw);
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) { rest[j] = (uint32_t)(x[j] >> sh.sfield); sa[j] = (uint32_t)x[j]; }
+    }
+    for (int i = tid; i < NCLS; i += BLOCK) pcnt[i] = 0;
+    if (tid < 257) s_off[tid] = my_off;
+    if (lane == WAVE - 1) { s_last[wave][0] = rest[ITEMS - 1]; s_last[wave][1] = sa[ITEMS - 1]; }
+    __syncthreads();
+    ow.off = s_off;
+    uint32_t prest = (uint32_t)__shfl_up((int)rest[ITEMS - 1], 1, WAVE), psa = (uint32_t)__shfl_up((int)sa[ITEMS - 1], 1, WAVE);
+    if (lane == 0) {
+        if (wave) { prest = s_last[wave - 1][0]; psa = s_last[wave - 1][1]; }
+        else { prest = (uint32_t)(xprev >> sh.sfield); psa = (uint32_t)xprev; }
+    }
+
+    // LCP with the record before, one byte per record: the common case first (same bucket, the rests differ)
+    uint32_t lcb[2] = {0u, 0u};
+    {
+        uint32_t pr = prest;
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) { lcb[j >> 2] |= rb1w_lead_lcp_rest(pr, rest[j], sh) << ((j & 3) * 8); pr = rest[j]; }
+    }
+    // bit j: record j lies in another bucket than the record before it (bit ITEMS: the record after the run); the borders' LCP on the way
+    unsigned bdiff = 0;
+    if (nv) {
+        OneWordCursor cu;
+        cu.start(ow, have_p ? e0 - 1 : 0);
+        if (cu.end <= e0 + nv) {          // (else the predecessor, the run and the record after it share a bucket)
+            unsigned pb = cu.b;
+#pragma unroll
+            for (int j = 0; j <= ITEMS; ++j) {
+                if (e0 + j < n) {
+                    const unsigned b = cu.at(ow, e0 + j);
+                    if (b != pb) {
+                        bdiff |= 1u << j;
+                        if (j < ITEMS) lcb[(j & 7) >> 2] = (lcb[(j & 7) >> 2] & ~(0xFFu << ((j & 3) * 8))) | (rb1w_lead_lcp_bucket(pb, b, sh) << ((j & 3) * 8));
+                    }
+                    pb = b;
+                }
+            }
+        }
+    }
+    // bit j: record j has the leading part of the record before it (both are tied records then)
+    unsigned eqp = 0;
+    {
+        uint32_t pr = prest;
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            if (rest[j] == pr && !((bdiff >> j) & 1u) && (j || have_p)) eqp |= 1u << j;
+            pr = rest[j];
+        }
+        eqp &= vmask;
+    }
+    if (eqp) {
+        // tied records: both words of every one of them, asked for four records at a time
+        const unsigned tied = eqp | (eqp >> 1);
+        uint64_t p1 = 0, p2 = 0;
+        if (eqp & 1u) { p1 = S1t[e0 - 1]; p2 = S2[e0 - 1]; }
+#pragma unroll
+        for (int h = 0; h < ITEMS; h += 4) {
+            uint64_t t1[4], t2[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool t = (tied >> (h + j)) & 1u;
+                t1[j] = t ? S1t[e0 + h + j] : 0ull; t2[j] = t ? S2[e0 + h + j] : 0ull;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if ((eqp >> (h + j)) & 1u) {
+                    const unsigned c = rb1w_window_lcp(p1, p2, t1[j], t2[j], sh);
+                    lcb[h >> 2] = (lcb[h >> 2] & ~(0xFFu << (j * 8))) | (c << (j * 8));
+                }
+                p1 = t1[j]; p2 = t2[j];
+            }
+        }
+    }
+    // the lengths of the two suffixes cap the value; heads
+    unsigned heads = 0;
+    {
+        uint32_t ps = psa;
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            unsigned c = (lcb[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
+            c = rb1w_cap(rb1w_cap(c, ps, sh), sa[j], sh);
+            const bool very_first = j == 0 && !have_p;          // nothing sorts before this record
+            if (very_first) c = 0;
+            if (very_first || c < sh.two_k || !((vmask >> j) & 1u)) heads |= 1u << j;
+            lcb[j >> 2] = (lcb[j >> 2] & ~(0xFFu << ((j & 3) * 8))) | (c << ((j & 3) * 8));
+            ps = sa[j];
+        }
+    }
+    // the head flag of the first record of the next tile (the tile's last thread)
+    bool tile_next_head = true;
+    if (have_tq) {
+        const uint32_t qrest = (uint32_t)(xnext >> sh.sfield), qsa = (uint32_t)xnext;
+        if (qrest == rest[ITEMS - 1] && !((bdiff >> ITEMS) & 1u)) {
+            const uint64_t e = e0 + ITEMS;
+            unsigned c = rb1w_window_lcp(S1t[e - 1], S2[e - 1], S1t[e], S2[e], sh);
+            c = rb1w_cap(rb1w_cap(c, sa[ITEMS - 1], sh), qsa, sh);
+            tile_next_head = c < sh.two_k;
+        }
+    }
+    // the last head before every run: a max-scan over tile-local positions + 1 (0 = none); the first head flag of every wave rides along
+    const unsigned hm = heads & vmask;
+    const unsigned run = hm ? tid * ITEMS + (32u - (unsigned)__builtin_clz(hm)) : 0u;
+    const unsigned inc = wave_scan_inclusive<unsigned>(run, OpMax());
+    if (lane == WAVE - 1) s_scan[wave] = inc;
+    if (lane == 0) s_h0[wave] = heads & 1u;
+    __syncthreads();
+    unsigned excl = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { const unsigned s = s_scan[w]; if ((unsigned)w < wave && s > excl) excl = s; }
+    {
+        const unsigned prev = (unsigned)__shfl_up((int)inc, 1, WAVE);
+        if (lane && prev > excl) excl = prev;
+        unsigned nh = (unsigned)__shfl_down((int)(heads & 1u), 1, WAVE);
+        if (lane == WAVE - 1) nh = wave + 1 < NW ? s_h0[wave + 1] : (tile_next_head ? 1u : 0u);
+        heads |= nh << ITEMS;
+    }
+    // activity: not a head, or a head followed by a non-head
+    unsigned nact = 0, nub = 0;
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+        if ((vmask >> j) & 1u) {
+            const bool h = (heads >> j) & 1u, hn = (heads >> (j + 1)) & 1u;
+            if (!h || !hn) ++nact;
+            if (h && !hn) ++nub;
+        }
+    }
+    {
+        const unsigned both = wave_reduce<unsigned>(nact | (nub << 16), OpSum());
+        if (lane == 0) s_cnt[wave] = both;
+    }
+    // the fused partition level: places inside the classes (counted before the barrier the tile counters need anyway), two to a word
+    uint32_t slot2[ITEMS / 2];
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+        const unsigned d = (sa[j] >> part_shift) & (NCLS - 1);
+        const unsigned sl = (vmask >> j) & 1u ? atomicAdd(&pcnt[d], 1u) : 0u;
+        slot2[j >> 1] = (j & 1) ? (slot2[j >> 1] | (sl << 16)) : sl;
+    }
+    __syncthreads();
+    unsigned both_counts = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) both_counts += s_cnt[w];
+    const unsigned tact = both_counts & 0xFFFFu, tub = both_counts >> 16;
+    if (tid == 0) { n_active[tile] = tact; n_unf[tile] = tub; }
+    // ranks: a head's is its position, everybody else carries the last head's (not kept: made again where the pairs are staged)
+    const uint32_t carry0 = excl ? (uint32_t)tbase + excl - 1u : rb1w_rank_of_id(carry64);
+    const uint64_t wb = e0 - (uint64_t)lane * ITEMS;
+    if (!(lazy_ids && tact == 0)) {
+        const unsigned hf = rb1w_fresh(hm);
+        rb1w_store_run(Bsa, wb, n, lane, xw, [&](int j) {
+            const unsigned m = hf & ((2u << j) - 1u);          // the heads of the run up to record j
+            return rb1w_id_of_rank(m ? rb1w_rank_of_head(e0) + (31u - (unsigned)__builtin_clz(m)) : carry0);
+        });
+    }
+    if (WITH_LCP)
+        rb1w_store_run(LCP, wb, n, lane, xw, [&](int j) { return (heads >> j) & 1u ? (uint64_t)((lcb[j >> 2] >> ((j & 3) * 8)) & 0xFFu) : n; });
+    rb1w_store_run(sa_out, wb, n, lane, xw, [&](int j) { return (uint64_t)sa[j]; });
+    if (WITH_LCP && pyr1) {
+        // level 1 of the min-pyramid; the sentinel n as all ones while the values are 32-bit
+        uint32_t m = ~0u;
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const uint32_t c = (lcb[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
+            if ((hm >> j) & 1u && c < m) m = c;
+        }
+#pragma unroll
+        for (int d = 1; d < 64 / ITEMS; d <<= 1) { const uint32_t o = shfl_xor<uint32_t>(m, d); m = o < m ? o : m; }
+        if ((tid & (64 / ITEMS - 1)) == 0 && e0 < n) pyr1[e0 >> 6] = m == ~0u ? n : (uint64_t)m;
+    }
+    // the pairs (suffix, rank) leave partitioned into 2^PCB destination classes by suffix >> part_shift
+    uint64_t* const stage = reinterpret_cast<uint64_t*>(xp_raw);
+    const unsigned count = n - tbase < (uint64_t)TILE ? (unsigned)(n - tbase) : (unsigned)TILE;
+    const unsigned tot = tid < NCLS ? pcnt[tid] : 0u;
+    unsigned total;
+    const unsigned bs = block_scan_exclusive<BLOCK, unsigned>(tot, OpSum(), 0u, pscan_tmp, &total);
+    if (tid < NCLS) {
+        pstart[tid] = bs;
+        if (tot) {
+            const unsigned at = atomicAdd(&part_cursors[tid], tot);
+            pbase[tid] = ((uint64_t)tid << part_shift) + at - bs;
+        }
+    }
+    __syncthreads();          // (the runs of every wave have left the region the stage lies in: block_scan_exclusive has barriers too)
+    {
+        const unsigned hf = rb1w_fresh(hm), shift2 = rb1w_fresh_uniform(part_shift);          // (the classes are cut out of the suffixes again, not kept)
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const unsigned d = (sa[j] >> shift2) & (NCLS - 1);
+            const unsigned m = hf & ((2u << j) - 1u);
+            const uint32_t rank = m ? rb1w_rank_of_head(e0) + (31u - (unsigned)__builtin_clz(m)) : carry0;
+            if ((vmask >> j) & 1u) stage[((slot2[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu) + pstart[d]] = (uint64_t)sa[j] | ((uint64_t)rank << 32);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+        const unsigned p = tid + j * BLOCK;
+        if (p < count) {
+            const uint64_t x = stage[p];
+            part_out[pbase[((uint32_t)x >> part_shift) & (NCLS - 1)] + p] = x;
         }
     }
 }
