@@ -135,7 +135,8 @@ int psacx_trim(psacx_ctx* ctx);
  *                     first round has written them, under the SA -> ISA inversion; copied again if refinement rounds follow)
  *   NO_SPREAD_CURSORS the partition levels of the SA -> ISA path run their tiles in order (default: striped over several destination classes,
  *                     so that the workgroups running together do not all reserve and write inside one of them)
- *   LOCATE_SHAPE      psacx_locate_*: 1 = one pattern per lane (the default), 2 = eight lanes per pattern, 64 characters per step (A/B runs)
+ *   LOCATE_SHAPE      psacx_locate_*: 1 = one pattern per lane (the default), 2 = eight lanes per pattern, 64 characters per step (A/B runs);
+ *                     no effect on psacx_locate_gsa_*, which has the first shape only
  *   LOCATE_COUNT      psacx_locate_*: the kernel counts its fetches into psacx_stats.locate_fetches (slower; tools/locate_time.py)
  *   GENERIC_REBUCKET  the first round on one-word records runs the generic rebucket kernel, not its 32-bit form (A/B runs)          */
 enum {
@@ -463,6 +464,101 @@ int psacx_locate_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint
                      uint64_t q, uint32_t k, uint32_t* lb, uint32_t* ub);
 int psacx_locate_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* SA, const uint8_t* pat, const uint64_t* poff,
                      uint64_t q, uint32_t k, uint64_t* lb, uint64_t* ub);
+
+/* pattern search over string sets -------------------------------------------------
+ * The query side of psacx_construct_gsa_*: the same search over the generalized suffix array of a string set.  The reference has
+ * the pieces -- sa_index::locate (seq_query.hpp:246-251), lookup_index (lookup_table.hpp:36-149) and the string set
+ * (stringset.hpp:33-81) -- but no query over a set; psacx_locate_dev_* cannot stand in for one, because it compares up to the end of
+ * the text and a pattern would match across the seam of two strings.  One GPU.
+ *
+ * Definitions.  The m strings lie back to back in text[0..n); offsets[0..m] ascends strictly from 0 to n (no empty string).
+ * end(p) is the offset at which the string holding position p ends.  Suffix i is S[i..end(i)).  Bytes compare as unsigned
+ * values, and a proper prefix is smaller.
+ *
+ *     lb(P) = #{ i : S[i..end(i)) < P }
+ *     ub(P) = lb(P) + #{ i : P is a prefix of S[i..end(i)) }
+ *
+ *  - On a correct generalized suffix array the occurrences of P are exactly SA[lb..ub).  Equal suffixes lie in text order there, so
+ *    nothing is ambiguous.
+ *  - A pattern never matches across a string end.
+ *  - If P does not occur, lb == ub == the insertion point.  m_P == 0 gives [0, n).
+ *  - With m == 1 everything here equals the plain form above.
+ *
+ * String ends.  The index carries a bitmap of n + 1 bits, (n >> 5) + 1 words of 32: bit p = "a string starts at p, or p == n".
+ * psacx_string_ends_dev builds it from the offsets: *words = (n >> 5) + 1, and d_ends == NULL only computes that (the size query;
+ * d_offsets is not read then).  Offsets that do not start at 0, end at n and ascend strictly return PSACX_EINVAL before anything
+ * is written (the rules of psacx_check_gsa_dev_*).  It is built once per index and handed to the calls below, as the lookup table
+ * is: no query call does O(n) work for it.
+ *
+ * Lookup table.  code() and B as above (the alphabet of the whole text).  The keys are cut at string ends:
+ *
+ *     key_k(i) = sum over j < k of c_j * B^(k-1-j),   c_j = code(S[i+j]) if i + j < end(i), else 0.
+ *
+ * The table has B^k + 1 entries, table[v] = #{ i : key_k(i) < v }; k >= 1, and B^k > 2^30 returns PSACX_EINVAL.  It is counted from
+ * the text and the bitmap, never from the SA.  d_table == NULL is the size query (d_ends may be NULL then).
+ *
+ * Use of the table by a pattern: the rule of the plain form, word for word.  Let j = min(m_P, k).
+ *  - If any of P[0..j) has code 0, the table is not used for that pattern.  It is searched over [0, n).
+ *  - Otherwise v is the key of P[0..j) padded with zeros, and w = v + B^(k-j).
+ *     - For m_P <= k the answer is [table[v], table[w]) with no search.
+ *     - For m_P > k both bounds are searched inside [table[v], table[v+1]).  Comparisons may start at character k, because every
+ *       suffix in that bucket has at least k characters before its string ends and shares them with P.
+ *
+ * Totality, as for the plain form.
+ *  - Whatever SA, table and bitmap hold, nothing is read at or beyond n, in the text or in the pattern buffer, and the bitmap is
+ *    not read beyond bit n.  An SA entry >= n is the empty suffix.  Table entries are clamped to n, and an inverted bucket is empty.
+ *  - Every search terminates, and lb <= ub <= n.
+ *
+ * psacx_locate_gsa_dev_*: arguments as psacx_locate_dev_*, with d_ends after n.  The mix rules for d_table, k and code, the check of
+ * poff on the device before any result is written, and q == 0 are those of the plain form.  Nothing is allocated per call beyond
+ * the 4 KiB of the ctx slab.  The kernel is one pattern per lane.  PSACX_OPT_LOCATE_SHAPE = 2 has no effect here: there is no
+ * eight-lane form for string sets.  A bisection step is still two dependent fetches: when SA[mid] has arrived, the bitmap words of
+ * the next 8 characters and the text word are fetched together and the text word is cut at the first set bit; a comparison reads
+ * at most ceil(m_P / 32) + 1 bitmap words.  With PSACX_OPT_LOCATE_COUNT, psacx_stats.locate_fetches counts SA entries and text
+ * words as for the plain form.  Bitmap words are not counted.
+ * psacx_locate_gsa_*: the host-pointer form; k == 0 means no table.  It stages text, offsets, SA and patterns, builds the bitmap
+ * (malformed offsets: PSACX_EINVAL), builds the table when k > 0, copies the two result arrays back, and frees what it allocated
+ * on every path. */
+int psacx_string_ends_dev(psacx_ctx* ctx, const uint64_t* d_offsets, uint64_t m, uint64_t n, uint32_t* d_ends, uint64_t* words);
+int psacx_lookup_table_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, uint32_t k,
+                                   uint32_t* d_table, uint16_t code[256], uint32_t* sigma, uint64_t* entries);
+int psacx_lookup_table_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, uint32_t k,
+                                   uint64_t* d_table, uint16_t code[256], uint32_t* sigma, uint64_t* entries);
+int psacx_locate_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint32_t* d_SA,
+                             const uint32_t* d_table, uint32_t k, const uint16_t code[256],
+                             const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                             uint32_t* d_lb, uint32_t* d_ub);
+int psacx_locate_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint64_t* d_SA,
+                             const uint64_t* d_table, uint32_t k, const uint16_t code[256],
+                             const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                             uint64_t* d_lb, uint64_t* d_ub);
+int psacx_locate_gsa_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                         const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t* lb, uint32_t* ub);
+int psacx_locate_gsa_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                         const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint64_t* lb, uint64_t* ub);
+
+/* occurrence lists ------------------------------------------------------------------
+ * The positions behind a batch of intervals [lb_j, ub_j) of either search, in HBM.
+ *
+ *     c_j = ub_j - lb_j if lb_j <= ub_j <= n, else 0; with limit > 0, c_j is capped at limit.
+ *     start = the exclusive prefix sums of c (q + 1 entries of 64 bits), start[q] = *total.
+ *     pos[start_j + t] = SA[lb_j + t] for t < c_j: SA order, which is pinned.  Sorting by position is not part of this.
+ *     sid[start_j + t] = the string holding that position: the largest s with offsets[s] <= pos, and m for a pos >= n.
+ *
+ *  - d_offsets == NULL: one text (m is ignored).  d_sid, where not NULL, needs d_offsets and d_pos (PSACX_EINVAL otherwise).  The
+ *    offsets are only searched, never trusted: any m + 1 values give some s in [0, m).
+ *  - d_pos == NULL is the size query: start and *total only.
+ *  - *total > cap returns PSACX_ERANGE; start and *total are valid, and nothing is written to d_pos or d_sid.
+ *  - q == 0 gives *total = 0 and PSACX_OK.  No input is written.  SA entries are copied as they are, entries >= n included.
+ *  - The expansion is balanced by output: a workgroup owns a fixed tile of output slots, finds its first pattern by one binary
+ *    search in start, and walks forward from there, so the cost per output does not depend on how the counts are spread.  The
+ *    scan's block sums live in the ctx slab, 8 bytes per 4096 patterns beyond its 4 KiB. */
+int psacx_occurrences_dev_u32(psacx_ctx* ctx, const uint32_t* d_SA, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                              const uint32_t* d_lb, const uint32_t* d_ub, uint64_t q, uint64_t limit,
+                              uint64_t* d_start, uint32_t* d_pos, uint32_t* d_sid, uint64_t cap, uint64_t* total);
+int psacx_occurrences_dev_u64(psacx_ctx* ctx, const uint64_t* d_SA, uint64_t n, const uint64_t* d_offsets, uint64_t m,
+                              const uint64_t* d_lb, const uint64_t* d_ub, uint64_t q, uint64_t limit,
+                              uint64_t* d_start, uint64_t* d_pos, uint64_t* d_sid, uint64_t cap, uint64_t* total);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

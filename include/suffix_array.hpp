@@ -600,4 +600,113 @@ std::vector<std::pair<index_t, index_t> > locate(suffix_array<char, index_t, LCP
     return out;
 }
 
+// The same over the generalized suffix array of a string set: `ss` is the set `sa.construct_ss(ss, ...)` was built from.  Suffix i
+// ends where its string ends, so no pattern matches across two strings (psacx.h: "pattern search over string sets").
+template <typename index_t, bool LCP>
+std::vector<std::pair<index_t, index_t> > locate(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss,
+                                                 const std::vector<std::string>& patterns, unsigned int k = 0) {
+    if (sa.multi_context()) throw std::runtime_error("psacx: locate needs a single-rank communicator (the search runs on one GPU)");
+    if (ss.sum_sizes != sa.n) throw std::runtime_error("locate: string set does not match the suffix array");
+    std::vector<uint8_t> text; text.reserve(sa.n);
+    std::vector<uint64_t> soff(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) {
+        text.insert(text.end(), reinterpret_cast<const uint8_t*>(ss.str_begins[s]), reinterpret_cast<const uint8_t*>(ss.str_begins[s]) + ss.sizes[s]);
+        soff.push_back(text.size());
+    }
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* a, const uint8_t* p, const uint64_t* f,
+                       uint64_t q, uint32_t k, uint32_t* l, uint32_t* u) { return psacx_locate_gsa_u32(c, t, n, o, m, a, p, f, q, k, l, u); }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* a, const uint8_t* p, const uint64_t* f,
+                       uint64_t q, uint32_t k, uint64_t* l, uint64_t* u) { return psacx_locate_gsa_u64(c, t, n, o, m, a, p, f, q, k, l, u); }
+    };
+    std::vector<uint8_t> pat;
+    std::vector<uint64_t> off(1, 0);
+    for (std::size_t i = 0; i < patterns.size(); ++i) {
+        pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+        off.push_back(pat.size());
+    }
+    const uint64_t q = (uint64_t)patterns.size();
+    std::vector<W> lb(patterns.size()), ub(patterns.size());
+    psacx::check(sa.context(), Call::run(sa.context(), text.data(), sa.n, soff.data(), (uint64_t)ss.sizes.size(),
+                                         reinterpret_cast<const W*>(sa.local_SA.data()), pat.data(), off.data(), q, (uint32_t)k, lb.data(), ub.data()));
+    std::vector<std::pair<index_t, index_t> > out(patterns.size());
+    for (std::size_t i = 0; i < patterns.size(); ++i) out[i] = std::make_pair((index_t)lb[i], (index_t)ub[i]);
+    return out;
+}
+
+// The occurrence lists of a batch of intervals [lb[j], ub[j]) of locate (psacx.h: "occurrence lists"): the occurrences of pattern j
+// are pos[start[j] .. start[j + 1]) = local_SA[lb[j] .. ub[j]), in that order, at most `limit` of them where limit > 0; sid, filled
+// by the form that takes the string set, names the string holding each.  The lists are made on the GPU (psacx_occurrences_dev_*).
+template <typename index_t>
+struct occurrence_lists {
+    std::vector<std::size_t> start;
+    std::vector<index_t> pos, sid;
+};
+
+namespace psacx {
+template <typename index_t, bool LCP, bool LC>
+occurrence_lists<index_t> occurrences_of(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<uint64_t>* soff, const std::vector<index_t>& lb,
+                                         const std::vector<index_t>& ub, std::size_t limit) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    if (sa.multi_context()) throw std::runtime_error("psacx: occurrences needs a single-rank communicator (the lists are made on one GPU)");
+    if (lb.size() != ub.size()) throw std::runtime_error("occurrences: lb and ub differ in length");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint32_t* a, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* l, const uint32_t* u, uint64_t q, uint64_t lim,
+                       uint64_t* st, uint32_t* p, uint32_t* s, uint64_t cap, uint64_t* tot) { return psacx_occurrences_dev_u32(c, a, n, o, m, l, u, q, lim, st, p, s, cap, tot); }
+        static int run(psacx_ctx* c, const uint64_t* a, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* l, const uint64_t* u, uint64_t q, uint64_t lim,
+                       uint64_t* st, uint64_t* p, uint64_t* s, uint64_t cap, uint64_t* tot) { return psacx_occurrences_dev_u64(c, a, n, o, m, l, u, q, lim, st, p, s, cap, tot); }
+    };
+    psacx_ctx* c = sa.context();
+    const uint64_t q = (uint64_t)lb.size(), n = (uint64_t)sa.n, m = soff ? (uint64_t)soff->size() - 1 : 0;
+    occurrence_lists<index_t> out;
+    out.start.assign(q + 1, 0);
+    std::vector<void*> held;
+    struct Free {                                            // the device buffers go on every path
+        psacx_ctx* c; std::vector<void*>& v;
+        ~Free() { for (std::size_t i = 0; i < v.size(); ++i) (void)psacx_dev_free(c, v[i]); }
+    } guard = {c, held};
+    (void)guard;
+    auto dev = [&](const void* src, uint64_t bytes) -> void* {
+        void* p = nullptr;
+        check(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1));
+        held.push_back(p);
+        if (src && bytes) check(c, psacx_copy_h2d(c, p, src, bytes));
+        return p;
+    };
+    const W* d_sa = (const W*)dev(sa.local_SA.data(), n * sizeof(W));
+    const W* d_lb = (const W*)dev(lb.data(), q * sizeof(W));
+    const W* d_ub = (const W*)dev(ub.data(), q * sizeof(W));
+    const uint64_t* d_off = soff ? (const uint64_t*)dev(soff->data(), (m + 1) * sizeof(uint64_t)) : nullptr;
+    uint64_t* d_start = (uint64_t*)dev(nullptr, (q + 1) * sizeof(uint64_t));
+    uint64_t total = 0;
+    check(c, Call::run(c, d_sa, n, d_off, m, d_lb, d_ub, q, (uint64_t)limit, d_start, (W*)nullptr, (W*)nullptr, 0, &total));
+    out.pos.assign(total, 0);
+    if (soff) out.sid.assign(total, 0);
+    W* d_pos = (W*)dev(nullptr, total * sizeof(W));
+    W* d_sid = soff ? (W*)dev(nullptr, total * sizeof(W)) : nullptr;
+    check(c, Call::run(c, d_sa, n, d_off, m, d_lb, d_ub, q, (uint64_t)limit, d_start, d_pos, d_sid, total, &total));
+    check(c, psacx_copy_d2h(c, out.start.data(), d_start, (q + 1) * sizeof(uint64_t)));
+    if (total) check(c, psacx_copy_d2h(c, out.pos.data(), d_pos, total * sizeof(W)));
+    if (total && soff) check(c, psacx_copy_d2h(c, out.sid.data(), d_sid, total * sizeof(W)));
+    return out;
+}
+} // namespace psacx
+
+template <typename index_t, bool LCP, bool LC>
+occurrence_lists<index_t> occurrences(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<index_t>& lb, const std::vector<index_t>& ub,
+                                      std::size_t limit = 0) {
+    return psacx::occurrences_of(sa, (const std::vector<uint64_t>*)nullptr, lb, ub, limit);
+}
+
+template <typename index_t, bool LCP>
+occurrence_lists<index_t> occurrences(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, const std::vector<index_t>& lb,
+                                      const std::vector<index_t>& ub, std::size_t limit = 0) {
+    if (ss.sum_sizes != sa.n) throw std::runtime_error("occurrences: string set does not match the suffix array");
+    std::vector<uint64_t> soff(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) soff.push_back(soff.back() + ss.sizes[s]);
+    return psacx::occurrences_of(sa, &soff, lb, ub, limit);
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -42,6 +42,8 @@ EXPORTS = [
     "psacx_check_suffix_tree_gsa_dev_u32", "psacx_check_suffix_tree_gsa_dev_u64", "psacx_dev_alloc", "psacx_dev_free", "psacx_copy_h2d", "psacx_copy_d2h", "psacx_sync",
     "psacx_rand_dna", "psacx_synth_text_dev",
     "psacx_lookup_table_dev_u32", "psacx_lookup_table_dev_u64", "psacx_locate_dev_u32", "psacx_locate_dev_u64", "psacx_locate_u32", "psacx_locate_u64",
+    "psacx_string_ends_dev", "psacx_lookup_table_gsa_dev_u32", "psacx_lookup_table_gsa_dev_u64", "psacx_locate_gsa_dev_u32", "psacx_locate_gsa_dev_u64",
+    "psacx_locate_gsa_u32", "psacx_locate_gsa_u64", "psacx_occurrences_dev_u32", "psacx_occurrences_dev_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -132,6 +134,11 @@ def load():
         getattr(lib, "psacx_lookup_table_dev_" + suf).argtypes = [vp, vp, u64, vp, u32, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_locate_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, vp]
         getattr(lib, "psacx_locate_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, vp, vp]
+        getattr(lib, "psacx_lookup_table_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, u32, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_locate_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp]
+        getattr(lib, "psacx_locate_gsa_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, vp, vp]
+        getattr(lib, "psacx_occurrences_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+    lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_gsa_dev_u32.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

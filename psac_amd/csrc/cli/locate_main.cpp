@@ -1,10 +1,15 @@
 // locate -- batched pattern search on the MI355X engine, the counterpart of the reference's
 // `desa-main -f <text> -c -q <patterns>` (the reference's src/desa_main.cpp):
-//   locate -f <text> -q <patterns, one per line> [-k K] [--index 32|64|auto] [--device N] [-o file]
+//   locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--index 32|64|auto] [--device N] [-o file]
 // The text goes up once; the suffix array is constructed in HBM (psacx_construct_dev_*), the lookup table for -k K > 0 is built
 // there (psacx_lookup_table_dev_*) and the patterns are located there (psacx_locate_dev_*).  Prints "lb ub" per pattern -- the
 // occurrences are SA[lb..ub) -- to stdout or the file of -o, and "SA time:" / "Table time:" / "Locate time: <ms> ms" to stderr.
 // An empty line is the empty pattern.
+// --set reads -f as gsac does: the strings are the runs between '\n'.  The generalized suffix array is constructed in HBM
+// (psacx_construct_gsa_dev_*), the bitmap of the string ends beside it (psacx_string_ends_dev, "Ends time:"), and table and search
+// are those of a string set (psacx_lookup_table_gsa_dev_*, psacx_locate_gsa_dev_*): no pattern matches across two strings.
+// --occ [LIMIT] prints the occurrences of every pattern after its "lb ub", on the same line (psacx_occurrences_dev_*,
+// "Occurrences time:"), at most LIMIT each if LIMIT > 0: text positions, or string:offset-in-string with --set.
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -16,8 +21,9 @@
 #include "../../../include/psacx.h"
 
 static void usage() {
-    std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--index 32|64|auto] [--device N] [-o <file>]\n"
-                 "Locates every pattern in the suffix array of the text (MI355X engine): prints lb ub per pattern, the occurrences are SA[lb..ub).\n";
+    std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--index 32|64|auto] [--device N] [-o <file>]\n"
+                 "Locates every pattern in the suffix array of the text (MI355X engine): prints lb ub per pattern, the occurrences are SA[lb..ub).\n"
+                 "--set: the strings of -f are its lines, and no pattern matches across two of them.  --occ [LIMIT]: print the occurrences too.\n";
 }
 
 static void must(psacx_ctx* c, int rc) {
@@ -41,13 +47,43 @@ static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa
 static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code, const uint8_t* pat,
                   const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) { return psacx_locate_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, lb, ub); }
 
+static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint32_t* sa, uint32_t* isa) {
+    return psacx_construct_gsa_dev_u32(c, t, n, off, m, 0, 0, sa, isa, nullptr);
+}
+static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint64_t* sa, uint64_t* isa) {
+    return psacx_construct_gsa_dev_u64(c, t, n, off, m, 0, 0, sa, isa, nullptr);
+}
+static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t*, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg,
+                 uint64_t* e) { return psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, tab, code, sg, e); }
+static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t*, uint32_t k, uint64_t* tab, uint16_t* code, uint32_t* sg,
+                 uint64_t* e) { return psacx_lookup_table_gsa_dev_u64(c, t, n, ends, k, tab, code, sg, e); }
+static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, const uint32_t* tab, uint32_t k, const uint16_t* code,
+                  const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t* lb, uint32_t* ub) {
+    return psacx_locate_gsa_dev_u32(c, t, n, ends, sa, tab, k, code, pat, poff, q, lb, ub);
+}
+static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code,
+                  const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) {
+    return psacx_locate_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, lb, ub);
+}
+static int occurrences(psacx_ctx* c, const uint32_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* lb, const uint32_t* ub, uint64_t q,
+                       uint64_t limit, uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total) {
+    return psacx_occurrences_dev_u32(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
+}
+static int occurrences(psacx_ctx* c, const uint64_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* lb, const uint64_t* ub, uint64_t q,
+                       uint64_t limit, uint64_t* start, uint64_t* pos, uint64_t* sid, uint64_t cap, uint64_t* total) {
+    return psacx_occurrences_dev_u64(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
+}
+
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// soff: the offsets of the strings of --set (empty without it); occ: print the occurrences, at most limit each if limit > 0
 template <typename IT>
-static int run(const std::string& text, const std::string& pat, const std::vector<uint64_t>& poff, uint32_t k, int device, std::ostream& out) {
-    const uint64_t n = text.size(), q = poff.size() - 1;
+static int run(const std::string& text, const std::vector<uint64_t>& soff, const std::string& pat, const std::vector<uint64_t>& poff, uint32_t k,
+               bool occ, uint64_t limit, int device, std::ostream& out) {
+    const uint64_t n = text.size(), q = poff.size() - 1, m = soff.empty() ? 0 : soff.size() - 1;
+    const bool set = m != 0;
     psacx_ctx* c = nullptr;
     must(nullptr, psacx_create(&c, device, nullptr));
     std::vector<void*> held;
@@ -58,22 +94,39 @@ static int run(const std::string& text, const std::string& pat, const std::vecto
         uint8_t* d_text = (uint8_t*)dev(n);
         IT* d_sa = (IT*)dev(n * sizeof(IT));
         IT* d_isa = (IT*)dev(n * sizeof(IT));
+        uint64_t* d_soff = set ? (uint64_t*)dev((m + 1) * sizeof(uint64_t)) : nullptr;
         must(c, psacx_copy_h2d(c, d_text, text.data(), n));
-        must(c, construct(c, d_text, n, d_sa, d_isa));
+        if (set) {
+            must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
+            must(c, construct(c, d_text, n, d_soff, m, d_sa, d_isa));
+        } else {
+            must(c, construct(c, d_text, n, d_sa, d_isa));
+        }
         std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+        uint32_t* d_ends = nullptr;
+        if (set) {
+            auto te = std::chrono::steady_clock::now();
+            uint64_t words = 0;
+            must(c, psacx_string_ends_dev(c, nullptr, m, n, nullptr, &words));
+            d_ends = (uint32_t*)dev(words * sizeof(uint32_t));
+            must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
+            std::cerr << "Ends time: " << ms_since(te) << " ms" << std::endl;
+        }
         uint16_t code[256];
         IT* d_table = nullptr;
         if (k) {
             auto t1 = std::chrono::steady_clock::now();
             uint32_t sigma = 0;
             uint64_t entries = 0;
-            must(c, table(c, d_text, n, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries));
+            must(c, set ? table(c, d_text, n, d_ends, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries)
+                        : table(c, d_text, n, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries));
             d_table = (IT*)dev(entries * sizeof(IT));
-            must(c, table(c, d_text, n, d_sa, k, d_table, code, &sigma, &entries));
+            must(c, set ? table(c, d_text, n, d_ends, d_sa, k, d_table, code, &sigma, &entries) : table(c, d_text, n, d_sa, k, d_table, code, &sigma, &entries));
             std::cerr << "Table time: " << ms_since(t1) << " ms" << std::endl;
             std::cerr << "Table entries: " << entries << std::endl;
         }
-        std::vector<IT> lb(q), ub(q);
+        std::vector<IT> lb(q), ub(q), pos, sid;
+        std::vector<uint64_t> start(q + 1, 0);
         if (q) {
             uint8_t* d_pat = (uint8_t*)dev(pat.size() + 1);
             uint64_t* d_poff = (uint64_t*)dev((q + 1) * sizeof(uint64_t));
@@ -82,12 +135,35 @@ static int run(const std::string& text, const std::string& pat, const std::vecto
             if (!pat.empty()) must(c, psacx_copy_h2d(c, d_pat, pat.data(), pat.size()));
             must(c, psacx_copy_h2d(c, d_poff, poff.data(), (q + 1) * sizeof(uint64_t)));
             auto t2 = std::chrono::steady_clock::now();
-            must(c, locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
+            must(c, set ? locate(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub)
+                        : locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
             std::cerr << "Locate time: " << ms_since(t2) << " ms" << std::endl;
             must(c, psacx_copy_d2h(c, lb.data(), d_lb, q * sizeof(IT)));
             must(c, psacx_copy_d2h(c, ub.data(), d_ub, q * sizeof(IT)));
+            if (occ) {
+                auto t3 = std::chrono::steady_clock::now();
+                uint64_t* d_start = (uint64_t*)dev((q + 1) * sizeof(uint64_t));
+                uint64_t total = 0;
+                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, q, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
+                IT* d_pos = (IT*)dev(total * sizeof(IT) + 1);
+                IT* d_sid = set ? (IT*)dev(total * sizeof(IT) + 1) : nullptr;
+                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, q, limit, d_start, d_pos, d_sid, total, &total));
+                std::cerr << "Occurrences time: " << ms_since(t3) << " ms" << std::endl;
+                pos.resize(total);
+                must(c, psacx_copy_d2h(c, start.data(), d_start, (q + 1) * sizeof(uint64_t)));
+                if (total) must(c, psacx_copy_d2h(c, pos.data(), d_pos, total * sizeof(IT)));
+                if (set) { sid.resize(total); if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT))); }
+            }
         }
-        for (uint64_t i = 0; i < q; ++i) out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i] << '\n';
+        for (uint64_t i = 0; i < q; ++i) {
+            out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i];
+            if (occ)
+                for (uint64_t t = start[i]; t < start[i + 1]; ++t) {
+                    out << ' ';
+                    if (set) out << (uint64_t)sid[t] << ':' << (uint64_t)pos[t] - soff[(std::size_t)sid[t]]; else out << (uint64_t)pos[t];
+                }
+            out << '\n';
+        }
     } catch (...) {
         release();
         throw;
@@ -109,6 +185,8 @@ int main(int argc, char** argv) {
     std::string file, queries, outfile, index = "auto";
     int device = 0;
     long k = 0;
+    bool set = false, occ = false;
+    unsigned long long limit = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* name) -> const char* {
@@ -121,6 +199,11 @@ int main(int argc, char** argv) {
         else if (a == "-o" || a == "--outfile") outfile = need("-o");
         else if (a == "--device") device = atoi(need("--device"));
         else if (a == "--index") index = need("--index");
+        else if (a == "--set") set = true;
+        else if (a == "--occ") {
+            occ = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') limit = strtoull(argv[++i], nullptr, 10);
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
@@ -128,6 +211,19 @@ int main(int argc, char** argv) {
     std::string text, lines;
     if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     if (!read_file(queries, lines)) { std::cerr << "error: cannot open " << queries << std::endl; return EXIT_FAILURE; }
+    std::vector<uint64_t> soff;
+    if (set) {                                        // the strings are the runs between '\n', laid back to back (gsac)
+        std::string flat;
+        flat.reserve(text.size());
+        soff.push_back(0);
+        for (std::size_t b = 0; b < text.size();) {
+            std::size_t e = text.find('\n', b);
+            if (e == std::string::npos) e = text.size();
+            if (e > b) { flat.append(text, b, e - b); soff.push_back(flat.size()); }
+            b = e + 1;
+        }
+        text.swap(flat);
+    }
     if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
     // one pattern per line; a last line without its newline counts
     std::string pat;
@@ -147,7 +243,8 @@ int main(int argc, char** argv) {
             if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
         }
         std::ostream& out = outfile.empty() ? std::cout : f;
-        const int rc = use32 ? run<uint32_t>(text, pat, poff, (uint32_t)k, device, out) : run<uint64_t>(text, pat, poff, (uint32_t)k, device, out);
+        const int rc = use32 ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, device, out)
+                             : run<uint64_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, device, out);
         out.flush();
         if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

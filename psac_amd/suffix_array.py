@@ -352,10 +352,62 @@ def locate_device(ctx, d_text, n, d_sa, d_table, k, code, d_pat, d_poff, q, d_lb
                  _ptr(cd) if cd is not None else None, C.c_void_p(d_pat), C.c_void_p(d_poff), int(q), C.c_void_p(d_lb), C.c_void_p(d_ub)))
 
 
-def locate(text, SA, patterns, k=0, ctx=None):
+def string_ends_device(ctx, d_off, m, n, d_ends):
+    """psacx_string_ends_dev: the bitmap of the string ends of a set resident in HBM -- bit p = "a string starts at p, or p == n" --
+    from its m + 1 uint64 offsets at d_off, into the (n >> 5) + 1 uint32 words at d_ends.  It belongs to the index as the lookup
+    table does: lookup_table_gsa_device and locate_gsa_device take it.  With d_ends=None only the size is computed.  Returns the
+    number of words."""
+    words = C.c_uint64(0)
+    ctx._pre()
+    ctx.check(ctx._lib.psacx_string_ends_dev(ctx.handle, C.c_void_p(d_off) if d_off else None, int(m), int(n),
+                                             C.c_void_p(d_ends) if d_ends else None, C.byref(words)))
+    return words.value
+
+
+def lookup_table_gsa_device(ctx, d_text, n, d_ends, k, d_table, index_bits):
+    """psacx_lookup_table_gsa_dev_*: lookup_table_device for a string set, its keys cut at the string ends of the bitmap at d_ends
+    (string_ends_device).  With d_table=None only the sizes are computed.  Returns (code, sigma, entries)."""
+    fn = getattr(ctx._lib, "psacx_lookup_table_gsa_dev_u%d" % index_bits)
+    code = np.zeros(256, np.uint16)
+    sigma, entries = C.c_uint32(0), C.c_uint64(0)
+    ctx._pre()
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_ends) if d_ends else None, int(k), C.c_void_p(d_table) if d_table else None,
+                 _ptr(code), C.byref(sigma), C.byref(entries)))
+    return code, sigma.value, entries.value
+
+
+def locate_gsa_device(ctx, d_text, n, d_ends, d_sa, d_table, k, code, d_pat, d_poff, q, d_lb, d_ub, index_bits):
+    """psacx_locate_gsa_dev_*: locate_device over the generalized suffix array of a string set: suffix i ends where its string
+    ends, so no pattern matches across two strings.  d_ends is the bitmap of string_ends_device; d_table / k / code as
+    lookup_table_gsa_device left them, or None / 0 / None."""
+    fn = getattr(ctx._lib, "psacx_locate_gsa_dev_u%d" % index_bits)
+    cd = None if code is None else np.ascontiguousarray(code, dtype=np.uint16)
+    ctx._pre()
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_ends) if d_ends else None, C.c_void_p(d_sa),
+                 C.c_void_p(d_table) if d_table else None, int(k), _ptr(cd) if cd is not None else None, C.c_void_p(d_pat), C.c_void_p(d_poff),
+                 int(q), C.c_void_p(d_lb), C.c_void_p(d_ub)))
+
+
+def occurrences_device(ctx, d_sa, n, d_off, m, d_lb, d_ub, q, limit, d_start, d_pos, d_sid, cap, index_bits):
+    """psacx_occurrences_dev_*: the occurrence lists of q intervals resident in HBM.  d_start receives q + 1 uint64 (the exclusive
+    prefix sums of the counts, each capped at limit where limit > 0), d_pos the positions SA[lb_j + t] in SA order, d_sid (with
+    d_off, the m + 1 string offsets) the string holding each.  d_pos=None is the size query.  Returns the total; raises
+    PsacxError -2 where it exceeds cap, with d_start valid and d_pos untouched."""
+    fn = getattr(ctx._lib, "psacx_occurrences_dev_u%d" % index_bits)
+    total = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, opt(d_sa), int(n), opt(d_off), int(m), opt(d_lb), opt(d_ub), int(q), int(limit), opt(d_start), opt(d_pos), opt(d_sid),
+                 int(cap), C.byref(total)))
+    return total.value
+
+
+def locate(text, SA, patterns, k=0, ctx=None, offsets=None):
     """psacx_locate_*: (lb, ub) arrays -- pattern i occurs at SA[lb[i]:ub[i]]; where it does not occur lb[i] == ub[i] is its insertion
     point -- for a list of patterns (bytes, str or byte arrays) in the suffix array SA of text.  k > 0 builds the k-mer lookup table
-    first and starts every search in its bucket; the answers are the same.  Host arrays; everything is staged for the call."""
+    first and starts every search in its bucket; the answers are the same.  Host arrays; everything is staged for the call.
+    offsets: text is a string set laid back to back, offsets its m + 1 string offsets and SA its generalized suffix array
+    (psacx_locate_gsa_*); a pattern then never matches across two strings."""
     if isinstance(text, str):
         text = text.encode("latin-1")
     t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
@@ -366,10 +418,58 @@ def locate(text, SA, patterns, k=0, ctx=None):
     q = int(off.size - 1)
     lb, ub = np.zeros(q, sa.dtype), np.zeros(q, sa.dtype)
     ctx = ctx if ctx is not None else Context(0)
-    fn = getattr(ctx._lib, "psacx_locate_u%d" % (sa.dtype.itemsize * 8))
     ctx._pre()
-    ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), _ptr(lb), _ptr(ub)))
+    if offsets is None:
+        fn = getattr(ctx._lib, "psacx_locate_u%d" % (sa.dtype.itemsize * 8))
+        ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), _ptr(lb), _ptr(ub)))
+    else:
+        so = np.ascontiguousarray(offsets, dtype=np.uint64)
+        fn = getattr(ctx._lib, "psacx_locate_gsa_u%d" % (sa.dtype.itemsize * 8))
+        ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(so), so.size - 1, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), _ptr(lb),
+                     _ptr(ub)))
     return lb, ub
+
+
+def occurrences(SA, lb, ub, limit=0, offsets=None, ctx=None):
+    """(start, pos) -- or (start, pos, sid) with offsets -- of the intervals [lb[j], ub[j]) of locate(): the occurrences of
+    pattern j are pos[start[j]:start[j + 1]] = SA[lb[j]:ub[j]], in SA order, at most limit of them where limit > 0; sid names
+    the string of the set holding each.  Host arrays, staged for the call; the lists are made on the GPU (psacx_occurrences_dev_*)."""
+    sa = np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("occurrences needs a uint32 or uint64 suffix array")
+    bits = sa.dtype.itemsize * 8
+    lo, hi = np.ascontiguousarray(lb, dtype=sa.dtype), np.ascontiguousarray(ub, dtype=sa.dtype)
+    if lo.size != hi.size:
+        raise ValueError("lb and ub differ in length")
+    q, n = int(lo.size), int(sa.size)
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    m = 0 if so is None else int(so.size - 1)
+    ctx = ctx if ctx is not None else Context(0)
+    start = np.zeros(q + 1, np.uint64)
+    held = []
+
+    def put(arr):
+        p = ctx.alloc(max(1, arr.nbytes))
+        held.append(p)
+        if arr.nbytes:
+            ctx.h2d(p, arr)
+        return p
+    try:
+        d_sa, d_lb, d_ub, d_start = put(sa), put(lo), put(hi), put(start)
+        d_off = None if so is None else put(so)
+        total = occurrences_device(ctx, d_sa, n, d_off, m, d_lb, d_ub, q, limit, d_start, None, None, 0, bits)
+        pos, sid = np.zeros(total, sa.dtype), np.zeros(total, sa.dtype)
+        d_pos, d_sid = put(pos), (None if so is None else put(sid))
+        occurrences_device(ctx, d_sa, n, d_off, m, d_lb, d_ub, q, limit, d_start, d_pos, d_sid, total, bits)
+        ctx.d2h(start, d_start)
+        if total:
+            ctx.d2h(pos, d_pos)
+            if so is not None:
+                ctx.d2h(sid, d_sid)
+    finally:
+        for p in held:
+            ctx.free(p)
+    return (start, pos) if so is None else (start, pos, sid)
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
