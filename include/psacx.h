@@ -537,6 +537,80 @@ int psacx_locate_gsa_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const 
 int psacx_locate_gsa_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
                          const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint64_t* lb, uint64_t* ub);
 
+/* longest match and matching statistics ---------------------------------------------
+ * The question one level above locate: how long is the longest prefix of a query that occurs, and where?  psacx_locate_*
+ * answers a pattern that does not occur with a bare insertion point; these calls answer it with the length of its longest
+ * matching prefix and that prefix's interval, and can do so for every suffix of every pattern in one launch (the matching
+ * statistics of the patterns).  The reference has no counterpart.  One GPU.
+ *
+ * Definitions.  Text, suffixes, byte order, lb(), ub(), code(), the table and the bitmap of the string ends are exactly those of
+ * the two blocks above: in the plain form suffix i is S[i..n), in the set form it is S[i..end(i)).  For a query Q of m bytes:
+ *
+ *     len(Q)   = max { d <= m : Q[0..d) is a prefix of some suffix }         (d = 0 always qualifies)
+ *     [lb, ub) = [ lb(Q[0..len)), ub(Q[0..len)) )                             (the locate interval of the matched prefix)
+ *
+ *  - len == m means Q occurs, and [lb, ub) is what locate returns.  len == 0 gives [0, n).
+ *  - On a correct SA the interval is never empty for n >= 1.
+ *  - Nothing is ambiguous: all three values are functions of the text (and the offsets) alone.
+ *  - In the set form a match never crosses a string end.
+ *
+ * Which queries.  flags == 0: one query per pattern, Q_j = pat[poff[j] .. poff[j+1]), and q results.
+ * flags & PSACX_MATCH_SUFFIXES: one query per byte of the pattern buffer.  Slot p in [0, poff[q]) belongs to the pattern j with
+ * poff[j] <= p < poff[j+1]; its query is pat[p .. poff[j+1]); there are poff[q] results, in buffer order.  Empty patterns own no
+ * slot.  These are the matching statistics of every pattern.
+ *
+ * Cap.  max_len > 0 truncates every query to its first max_len bytes before anything else, so len <= max_len.  max_len == 0
+ * means no cap.
+ *
+ * Table.  With a correct table the three results equal those without one, for every query.  Non-emptiness of the bucket of
+ * Q[0..j) is monotone in j, so the longest prefix of at most min(m, k) bytes that occurs is found from table entries alone;
+ * only a query whose first k bytes occur, with m > k, is searched, inside its bucket.  A byte with code 0 (absent from the
+ * text) at position i of Q bounds len <= i: unlike locate, this form never falls back to a search over [0, n) because of such
+ * a byte.
+ *
+ * Totality, as for locate.  Whatever SA, table and bitmap hold, nothing is read out of range: text and pattern buffer never at
+ * or beyond their ends, the bitmap never beyond bit n, the table only inside its B^k + 1 entries.  Every loop terminates.
+ * len <= m (and <= max_len), and lb <= ub <= n.  On arrays that are no suffix array, table or bitmap of the text the values are
+ * otherwise unspecified.
+ *
+ * psacx_match_dev_* / psacx_match_gsa_dev_*: arguments as psacx_locate_dev_* / psacx_locate_gsa_dev_*; d_len, d_lb and d_ub
+ * (index type) receive out_entries results each.  out_entries is the room the caller has: it must equal q, or poff[q] in the
+ * suffix mode.  A mismatch, poff[0] != 0 or a descending pair returns PSACX_EINVAL, found on the device before any result is
+ * written.  The mix rules for d_table / k / code are those of locate; unknown flag bits return PSACX_EINVAL; q == 0 returns
+ * PSACX_OK (out_entries must be 0).  Nothing is allocated per call beyond the 4 KiB of the ctx slab.  With
+ * PSACX_OPT_LOCATE_COUNT, psacx_stats.locate_fetches counts SA entries and text words as for locate; for a batch of patterns
+ * that all occur the counts equal those of the locate call.
+ * psacx_match_* / psacx_match_gsa_*: the host-pointer forms; k == 0 means no table.  They stage text, (offsets,) SA and
+ * patterns, build the bitmap and the table when k > 0, copy the three result arrays back -- q entries each, or poff[q] in the
+ * suffix mode -- and free what they allocated on every path. */
+#define PSACX_MATCH_SUFFIXES 1u
+int psacx_match_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_SA,
+                        const uint32_t* d_table, uint32_t k, const uint16_t code[256],
+                        const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                        uint32_t flags, uint64_t max_len, uint64_t out_entries, uint32_t* d_len, uint32_t* d_lb, uint32_t* d_ub);
+int psacx_match_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_SA,
+                        const uint64_t* d_table, uint32_t k, const uint16_t code[256],
+                        const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                        uint32_t flags, uint64_t max_len, uint64_t out_entries, uint64_t* d_len, uint64_t* d_lb, uint64_t* d_ub);
+int psacx_match_gsa_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint32_t* d_SA,
+                            const uint32_t* d_table, uint32_t k, const uint16_t code[256],
+                            const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                            uint32_t flags, uint64_t max_len, uint64_t out_entries, uint32_t* d_len, uint32_t* d_lb, uint32_t* d_ub);
+int psacx_match_gsa_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint64_t* d_SA,
+                            const uint64_t* d_table, uint32_t k, const uint16_t code[256],
+                            const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                            uint32_t flags, uint64_t max_len, uint64_t out_entries, uint64_t* d_len, uint64_t* d_lb, uint64_t* d_ub);
+int psacx_match_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint32_t* SA, const uint8_t* pat, const uint64_t* poff,
+                    uint64_t q, uint32_t k, uint32_t flags, uint64_t max_len, uint32_t* len, uint32_t* lb, uint32_t* ub);
+int psacx_match_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* SA, const uint8_t* pat, const uint64_t* poff,
+                    uint64_t q, uint32_t k, uint32_t flags, uint64_t max_len, uint64_t* len, uint64_t* lb, uint64_t* ub);
+int psacx_match_gsa_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                        const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t flags, uint64_t max_len,
+                        uint32_t* len, uint32_t* lb, uint32_t* ub);
+int psacx_match_gsa_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                        const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t flags, uint64_t max_len,
+                        uint64_t* len, uint64_t* lb, uint64_t* ub);
+
 /* occurrence lists ------------------------------------------------------------------
  * The positions behind a batch of intervals [lb_j, ub_j) of either search, in HBM.
  *

@@ -709,4 +709,75 @@ occurrence_lists<index_t> occurrences(suffix_array<char, index_t, LCP, false>& s
     return psacx::occurrences_of(sa, &soff, lb, ub, limit);
 }
 
+// Longest match (psacx.h: "longest match and matching statistics"): for every query the length of its longest prefix that occurs
+// and the locate interval of that prefix -- it occurs at local_SA[lb[i] .. ub[i]); len[i] == 0 gives [0, n).  One query per
+// pattern, or with suffixes = true one per byte of the patterns laid back to back (the query at byte p is the rest of its pattern
+// from p on: the matching statistics of every pattern), in that order.  max_len > 0 cuts every query to that many bytes.  k > 0
+// puts the k-mer lookup table in front; the answers are the same.  One rank only, as locate.
+template <typename index_t>
+struct match_lists {
+    std::vector<index_t> len, lb, ub;
+};
+
+namespace psacx {
+// soff: the offsets of a string set, or nullptr for one text
+template <typename index_t, bool LCP, bool LC>
+match_lists<index_t> match_of(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff,
+                              const std::vector<std::string>& patterns, unsigned int k, bool suffixes, std::size_t max_len) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* a, const uint8_t* p, const uint64_t* f,
+                       uint64_t q, uint32_t k, uint32_t fl, uint64_t ml, uint32_t* d, uint32_t* l, uint32_t* u) {
+            return o ? psacx_match_gsa_u32(c, t, n, o, m, a, p, f, q, k, fl, ml, d, l, u) : psacx_match_u32(c, t, n, a, p, f, q, k, fl, ml, d, l, u);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* a, const uint8_t* p, const uint64_t* f,
+                       uint64_t q, uint32_t k, uint32_t fl, uint64_t ml, uint64_t* d, uint64_t* l, uint64_t* u) {
+            return o ? psacx_match_gsa_u64(c, t, n, o, m, a, p, f, q, k, fl, ml, d, l, u) : psacx_match_u64(c, t, n, a, p, f, q, k, fl, ml, d, l, u);
+        }
+    };
+    std::vector<uint8_t> pat;
+    std::vector<uint64_t> off(1, 0);
+    for (std::size_t i = 0; i < patterns.size(); ++i) {
+        pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+        off.push_back(pat.size());
+    }
+    const uint64_t q = (uint64_t)patterns.size();
+    const std::size_t entries = suffixes ? pat.size() : patterns.size();
+    std::vector<W> len(entries), lb(entries), ub(entries);
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, soff ? soff->data() : (const uint64_t*)nullptr, soff ? (uint64_t)soff->size() - 1 : 0,
+                                  reinterpret_cast<const W*>(sa.local_SA.data()), pat.data(), off.data(), q, (uint32_t)k,
+                                  suffixes ? PSACX_MATCH_SUFFIXES : 0u, (uint64_t)max_len, len.data(), lb.data(), ub.data()));
+    match_lists<index_t> out;
+    out.len.assign(len.begin(), len.end());
+    out.lb.assign(lb.begin(), lb.end());
+    out.ub.assign(ub.begin(), ub.end());
+    return out;
+}
+} // namespace psacx
+
+template <typename index_t, bool LCP, bool LC, typename Iterator>
+match_lists<index_t> match(suffix_array<char, index_t, LCP, LC>& sa, Iterator begin, Iterator end, const std::vector<std::string>& patterns,
+                           unsigned int k = 0, bool suffixes = false, std::size_t max_len = 0) {
+    if (sa.multi_context()) throw std::runtime_error("psacx: match needs a single-rank communicator (the search runs on one GPU)");
+    std::vector<uint8_t> text(begin, end);
+    if (text.size() != sa.n) throw std::runtime_error("match: text does not match the suffix array");
+    return psacx::match_of(sa, text, (const std::vector<uint64_t>*)nullptr, patterns, k, suffixes, max_len);
+}
+
+// The same over the generalized suffix array of a string set: a match never crosses a string end.
+template <typename index_t, bool LCP>
+match_lists<index_t> match(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, const std::vector<std::string>& patterns,
+                           unsigned int k = 0, bool suffixes = false, std::size_t max_len = 0) {
+    if (sa.multi_context()) throw std::runtime_error("psacx: match needs a single-rank communicator (the search runs on one GPU)");
+    if (ss.sum_sizes != sa.n) throw std::runtime_error("match: string set does not match the suffix array");
+    std::vector<uint8_t> text; text.reserve(sa.n);
+    std::vector<uint64_t> soff(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) {
+        text.insert(text.end(), reinterpret_cast<const uint8_t*>(ss.str_begins[s]), reinterpret_cast<const uint8_t*>(ss.str_begins[s]) + ss.sizes[s]);
+        soff.push_back(text.size());
+    }
+    return psacx::match_of(sa, text, &soff, patterns, k, suffixes, max_len);
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -15,6 +15,7 @@ PSACX_LCP = 1
 PSACX_NO_FAST = 2
 PSACX_PROFILE = 4
 PSACX_MAX_ROUNDS = 72
+PSACX_MATCH_SUFFIXES = 1
 
 # psacx_configure options (include/psacx.h); Context.configure(force_diet=1, ...) takes them by name
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
@@ -44,6 +45,8 @@ EXPORTS = [
     "psacx_lookup_table_dev_u32", "psacx_lookup_table_dev_u64", "psacx_locate_dev_u32", "psacx_locate_dev_u64", "psacx_locate_u32", "psacx_locate_u64",
     "psacx_string_ends_dev", "psacx_lookup_table_gsa_dev_u32", "psacx_lookup_table_gsa_dev_u64", "psacx_locate_gsa_dev_u32", "psacx_locate_gsa_dev_u64",
     "psacx_locate_gsa_u32", "psacx_locate_gsa_u64", "psacx_occurrences_dev_u32", "psacx_occurrences_dev_u64",
+    "psacx_match_dev_u32", "psacx_match_dev_u64", "psacx_match_gsa_dev_u32", "psacx_match_gsa_dev_u64",
+    "psacx_match_u32", "psacx_match_u64", "psacx_match_gsa_u32", "psacx_match_gsa_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -138,6 +141,10 @@ def load():
         getattr(lib, "psacx_locate_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp]
         getattr(lib, "psacx_locate_gsa_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, vp, vp]
         getattr(lib, "psacx_occurrences_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_match_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, u32, u64, u64, vp, vp, vp]
+        getattr(lib, "psacx_match_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, u32, u64, u64, vp, vp, vp]
+        getattr(lib, "psacx_match_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, u32, u64, vp, vp, vp]
+        getattr(lib, "psacx_match_gsa_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, u32, u64, vp, vp, vp]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

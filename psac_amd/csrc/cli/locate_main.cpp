@@ -1,6 +1,7 @@
 // locate -- batched pattern search on the MI355X engine, the counterpart of the reference's
 // `desa-main -f <text> -c -q <patterns>` (the reference's src/desa_main.cpp):
-//   locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--index 32|64|auto] [--device N] [-o file]
+//   locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--longest [--suffixes] [--max-len L]]
+//          [--index 32|64|auto] [--device N] [-o file]
 // The text goes up once; the suffix array is constructed in HBM (psacx_construct_dev_*), the lookup table for -k K > 0 is built
 // there (psacx_lookup_table_dev_*) and the patterns are located there (psacx_locate_dev_*).  Prints "lb ub" per pattern -- the
 // occurrences are SA[lb..ub) -- to stdout or the file of -o, and "SA time:" / "Table time:" / "Locate time: <ms> ms" to stderr.
@@ -10,6 +11,10 @@
 // are those of a string set (psacx_lookup_table_gsa_dev_*, psacx_locate_gsa_dev_*): no pattern matches across two strings.
 // --occ [LIMIT] prints the occurrences of every pattern after its "lb ub", on the same line (psacx_occurrences_dev_*,
 // "Occurrences time:"), at most LIMIT each if LIMIT > 0: text positions, or string:offset-in-string with --set.
+// --longest answers every pattern with its longest prefix that occurs (psacx_match_dev_* / psacx_match_gsa_dev_*): prints
+// "len lb ub" per query -- the prefix of len bytes occurs at SA[lb..ub) -- and "Match time:" instead of "Locate time:".
+// --suffixes makes every byte of every pattern a query (the rest of its pattern from there on: the matching statistics, one line
+// per byte in the order of the patterns), --max-len L cuts every query to L bytes.  --occ lists the occurrences of the prefixes.
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -21,9 +26,12 @@
 #include "../../../include/psacx.h"
 
 static void usage() {
-    std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--index 32|64|auto] [--device N] [-o <file>]\n"
+    std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--longest [--suffixes] [--max-len L]]\n"
+                 "              [--index 32|64|auto] [--device N] [-o <file>]\n"
                  "Locates every pattern in the suffix array of the text (MI355X engine): prints lb ub per pattern, the occurrences are SA[lb..ub).\n"
-                 "--set: the strings of -f are its lines, and no pattern matches across two of them.  --occ [LIMIT]: print the occurrences too.\n";
+                 "--set: the strings of -f are its lines, and no pattern matches across two of them.  --occ [LIMIT]: print the occurrences too.\n"
+                 "--longest: print len lb ub of the longest prefix of every pattern that occurs; --suffixes: of every suffix of every pattern;\n"
+                 "--max-len L: of at most L bytes of each.\n";
 }
 
 static void must(psacx_ctx* c, int rc) {
@@ -65,6 +73,18 @@ static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* en
                   const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) {
     return psacx_locate_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, lb, ub);
 }
+static int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, const uint32_t* tab, uint32_t k, const uint16_t* code,
+                 const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint32_t* len, uint32_t* lb,
+                 uint32_t* ub) {
+    return ends ? psacx_match_gsa_dev_u32(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
+                : psacx_match_dev_u32(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
+}
+static int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code,
+                 const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint64_t* len, uint64_t* lb,
+                 uint64_t* ub) {
+    return ends ? psacx_match_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
+                : psacx_match_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
+}
 static int occurrences(psacx_ctx* c, const uint32_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* lb, const uint32_t* ub, uint64_t q,
                        uint64_t limit, uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total) {
     return psacx_occurrences_dev_u32(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
@@ -78,11 +98,13 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// soff: the offsets of the strings of --set (empty without it); occ: print the occurrences, at most limit each if limit > 0
+// soff: the offsets of the strings of --set (empty without it); occ: print the occurrences, at most limit each if limit > 0;
+// longest: --longest, with mflags (PSACX_MATCH_SUFFIXES for --suffixes) and max_len
 template <typename IT>
 static int run(const std::string& text, const std::vector<uint64_t>& soff, const std::string& pat, const std::vector<uint64_t>& poff, uint32_t k,
-               bool occ, uint64_t limit, int device, std::ostream& out) {
+               bool occ, uint64_t limit, bool longest, uint32_t mflags, uint64_t max_len, int device, std::ostream& out) {
     const uint64_t n = text.size(), q = poff.size() - 1, m = soff.empty() ? 0 : soff.size() - 1;
+    const uint64_t e = longest && (mflags & PSACX_MATCH_SUFFIXES) ? poff[q] : q;      // results: one per pattern, or one per byte of the patterns
     const bool set = m != 0;
     psacx_ctx* c = nullptr;
     must(nullptr, psacx_create(&c, device, nullptr));
@@ -125,37 +147,45 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
             std::cerr << "Table time: " << ms_since(t1) << " ms" << std::endl;
             std::cerr << "Table entries: " << entries << std::endl;
         }
-        std::vector<IT> lb(q), ub(q), pos, sid;
-        std::vector<uint64_t> start(q + 1, 0);
+        std::vector<IT> len(longest ? e : 0), lb(e), ub(e), pos, sid;
+        std::vector<uint64_t> start(e + 1, 0);
         if (q) {
             uint8_t* d_pat = (uint8_t*)dev(pat.size() + 1);
             uint64_t* d_poff = (uint64_t*)dev((q + 1) * sizeof(uint64_t));
-            IT* d_lb = (IT*)dev(q * sizeof(IT));
-            IT* d_ub = (IT*)dev(q * sizeof(IT));
+            IT* d_len = longest ? (IT*)dev(e * sizeof(IT) + 1) : nullptr;
+            IT* d_lb = (IT*)dev(e * sizeof(IT) + 1);
+            IT* d_ub = (IT*)dev(e * sizeof(IT) + 1);
             if (!pat.empty()) must(c, psacx_copy_h2d(c, d_pat, pat.data(), pat.size()));
             must(c, psacx_copy_h2d(c, d_poff, poff.data(), (q + 1) * sizeof(uint64_t)));
             auto t2 = std::chrono::steady_clock::now();
-            must(c, set ? locate(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub)
-                        : locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
-            std::cerr << "Locate time: " << ms_since(t2) << " ms" << std::endl;
-            must(c, psacx_copy_d2h(c, lb.data(), d_lb, q * sizeof(IT)));
-            must(c, psacx_copy_d2h(c, ub.data(), d_ub, q * sizeof(IT)));
+            if (longest) {
+                must(c, match(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, mflags, max_len, e, d_len, d_lb, d_ub));
+                std::cerr << "Match time: " << ms_since(t2) << " ms" << std::endl;
+                if (e) must(c, psacx_copy_d2h(c, len.data(), d_len, e * sizeof(IT)));
+            } else {
+                must(c, set ? locate(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub)
+                            : locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
+                std::cerr << "Locate time: " << ms_since(t2) << " ms" << std::endl;
+            }
+            if (e) must(c, psacx_copy_d2h(c, lb.data(), d_lb, e * sizeof(IT)));
+            if (e) must(c, psacx_copy_d2h(c, ub.data(), d_ub, e * sizeof(IT)));
             if (occ) {
                 auto t3 = std::chrono::steady_clock::now();
-                uint64_t* d_start = (uint64_t*)dev((q + 1) * sizeof(uint64_t));
+                uint64_t* d_start = (uint64_t*)dev((e + 1) * sizeof(uint64_t));
                 uint64_t total = 0;
-                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, q, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
+                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, e, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
                 IT* d_pos = (IT*)dev(total * sizeof(IT) + 1);
                 IT* d_sid = set ? (IT*)dev(total * sizeof(IT) + 1) : nullptr;
-                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, q, limit, d_start, d_pos, d_sid, total, &total));
+                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, e, limit, d_start, d_pos, d_sid, total, &total));
                 std::cerr << "Occurrences time: " << ms_since(t3) << " ms" << std::endl;
                 pos.resize(total);
-                must(c, psacx_copy_d2h(c, start.data(), d_start, (q + 1) * sizeof(uint64_t)));
+                must(c, psacx_copy_d2h(c, start.data(), d_start, (e + 1) * sizeof(uint64_t)));
                 if (total) must(c, psacx_copy_d2h(c, pos.data(), d_pos, total * sizeof(IT)));
                 if (set) { sid.resize(total); if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT))); }
             }
         }
-        for (uint64_t i = 0; i < q; ++i) {
+        for (uint64_t i = 0; i < e; ++i) {
+            if (longest) out << (uint64_t)len[i] << ' ';
             out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i];
             if (occ)
                 for (uint64_t t = start[i]; t < start[i + 1]; ++t) {
@@ -185,8 +215,8 @@ int main(int argc, char** argv) {
     std::string file, queries, outfile, index = "auto";
     int device = 0;
     long k = 0;
-    bool set = false, occ = false;
-    unsigned long long limit = 0;
+    bool set = false, occ = false, longest = false, suffixes = false;
+    unsigned long long limit = 0, max_len = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* name) -> const char* {
@@ -200,6 +230,9 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = atoi(need("--device"));
         else if (a == "--index") index = need("--index");
         else if (a == "--set") set = true;
+        else if (a == "--longest") longest = true;
+        else if (a == "--suffixes") suffixes = true;
+        else if (a == "--max-len") max_len = strtoull(need("--max-len"), nullptr, 10);
         else if (a == "--occ") {
             occ = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') limit = strtoull(argv[++i], nullptr, 10);
@@ -208,6 +241,7 @@ int main(int argc, char** argv) {
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
     if (file.empty() || queries.empty() || k < 0 || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    if (!longest && (suffixes || max_len)) { std::cerr << "error: --suffixes and --max-len belong to --longest" << std::endl; usage(); return EXIT_FAILURE; }
     std::string text, lines;
     if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     if (!read_file(queries, lines)) { std::cerr << "error: cannot open " << queries << std::endl; return EXIT_FAILURE; }
@@ -243,8 +277,8 @@ int main(int argc, char** argv) {
             if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
         }
         std::ostream& out = outfile.empty() ? std::cout : f;
-        const int rc = use32 ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, device, out)
-                             : run<uint64_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, device, out);
+        const int rc = use32 ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out)
+                             : run<uint64_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out);
         out.flush();
         if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

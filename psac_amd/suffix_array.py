@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PSACX_LCP, PSACX_NO_FAST, PSACX_PROFILE, PsacxError, Stats
+from ._lib import PSACX_MATCH_SUFFIXES as MATCH_SUFFIXES
 
 NEAREST_SM, NEAREST_EQ, FURTHEST_EQ = 0, 1, 2      # ansv_common.hpp:20-22
 
@@ -428,6 +429,62 @@ def locate(text, SA, patterns, k=0, ctx=None, offsets=None):
         ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(so), so.size - 1, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), _ptr(lb),
                      _ptr(ub)))
     return lb, ub
+
+
+def match_device(ctx, d_text, n, d_sa, d_table, k, code, d_pat, d_poff, q, flags, max_len, out_entries, d_len, d_lb, d_ub, index_bits):
+    """psacx_match_dev_*: for every query the length of its longest prefix that occurs and the locate interval of that prefix
+    (include/psacx.h: "longest match and matching statistics"), everything resident in HBM.  Arguments as locate_device; flags = 0
+    takes one query per pattern (out_entries = q), MATCH_SUFFIXES one per byte of the pattern buffer (out_entries = poff[q]);
+    max_len > 0 cuts every query to that many bytes.  d_len / d_lb / d_ub receive out_entries entries of the index type each."""
+    fn = getattr(ctx._lib, "psacx_match_dev_u%d" % index_bits)
+    cd = None if code is None else np.ascontiguousarray(code, dtype=np.uint16)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), C.c_void_p(d_sa), opt(d_table), int(k), _ptr(cd) if cd is not None else None,
+                 C.c_void_p(d_pat), C.c_void_p(d_poff), int(q), int(flags), int(max_len), int(out_entries), opt(d_len), opt(d_lb), opt(d_ub)))
+
+
+def match_gsa_device(ctx, d_text, n, d_ends, d_sa, d_table, k, code, d_pat, d_poff, q, flags, max_len, out_entries, d_len, d_lb, d_ub, index_bits):
+    """psacx_match_gsa_dev_*: match_device over the generalized suffix array of a string set; d_ends is the bitmap of
+    string_ends_device, and a match never crosses a string end."""
+    fn = getattr(ctx._lib, "psacx_match_gsa_dev_u%d" % index_bits)
+    cd = None if code is None else np.ascontiguousarray(code, dtype=np.uint16)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, C.c_void_p(d_text), int(n), opt(d_ends), C.c_void_p(d_sa), opt(d_table), int(k), _ptr(cd) if cd is not None else None,
+                 C.c_void_p(d_pat), C.c_void_p(d_poff), int(q), int(flags), int(max_len), int(out_entries), opt(d_len), opt(d_lb), opt(d_ub)))
+
+
+def match(text, SA, patterns, k=0, offsets=None, suffixes=False, max_len=0, ctx=None):
+    """psacx_match_*: (len, lb, ub) arrays -- the longest prefix of query i that occurs in text has len[i] bytes and occurs at
+    SA[lb[i]:ub[i]]; len[i] == 0 gives [0, n).  One query per pattern, or with suffixes=True one per byte of the pattern buffer (the
+    query at buffer position p is the rest of its pattern from p on: the matching statistics of every pattern), in buffer order.
+    max_len > 0 cuts every query to that many bytes.  k > 0 puts the k-mer lookup table in front; the answers are the same.
+    offsets: text is a string set and SA its generalized suffix array (psacx_match_gsa_*); a match never crosses a string end.
+    Host arrays; everything is staged for the call."""
+    if isinstance(text, str):
+        text = text.encode("latin-1")
+    t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    sa = np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("match needs a uint32 or uint64 suffix array")
+    pat, off = pattern_buffer(patterns)
+    q = int(off.size - 1)
+    entries = int(off[q]) if suffixes else q
+    ln, lb, ub = np.zeros(entries, sa.dtype), np.zeros(entries, sa.dtype), np.zeros(entries, sa.dtype)
+    flags = MATCH_SUFFIXES if suffixes else 0
+    ctx = ctx if ctx is not None else Context(0)
+    ctx._pre()
+    if offsets is None:
+        fn = getattr(ctx._lib, "psacx_match_u%d" % (sa.dtype.itemsize * 8))
+        ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), flags, int(max_len), _ptr(ln),
+                     _ptr(lb), _ptr(ub)))
+    else:
+        so = np.ascontiguousarray(offsets, dtype=np.uint64)
+        fn = getattr(ctx._lib, "psacx_match_gsa_u%d" % (sa.dtype.itemsize * 8))
+        ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(so), so.size - 1, _ptr(sa), _ptr(pat) if pat.size else None, _ptr(off), q, int(k), flags,
+                     int(max_len), _ptr(ln), _ptr(lb), _ptr(ub)))
+    return ln, lb, ub
 
 
 def occurrences(SA, lb, ub, limit=0, offsets=None, ctx=None):
