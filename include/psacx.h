@@ -634,6 +634,82 @@ int psacx_occurrences_dev_u64(psacx_ctx* ctx, const uint64_t* d_SA, uint64_t n, 
                               const uint64_t* d_lb, const uint64_t* d_ub, uint64_t q, uint64_t limit,
                               uint64_t* d_start, uint64_t* d_pos, uint64_t* d_sid, uint64_t cap, uint64_t* total);
 
+/* range minimum and longest common extension -------------------------------------------
+ * The two questions that need ISA and LCP: what is the minimum of LCP[l..r) and where does it first occur, and how far do two
+ * text positions agree.  The reference has the sequential structure (rmq<>::query, rmq.hpp:186, returns the first minimum of a
+ * range; par_rmq.hpp spreads it over ranks); nothing of it queries positions of the text.  One GPU.  The text is no argument
+ * of any call here.
+ *
+ * Definitions.  V[0..n) is an array of the index type T, "all ones" is the largest value of T.
+ *
+ *     range_j = [lo_j, min(hi_j, n))
+ *     min_j   = min V[range_j]
+ *     arg_j   = the smallest position in range_j that holds min_j        (the first minimum, as std::min_element)
+ *
+ *  - An empty range (lo_j >= min(hi_j, n)) gives min_j = all ones and arg_j = n.
+ *  - A value of all ones is legal in V; arg_j still lies inside the range.
+ *
+ * Index.  The 64-ary min-pyramid of V from level 1 upwards -- level[L][i] = min V[64^L i .. 64^L (i + 1)) -- and, for every
+ * such level, the running minima of each group of 64 entries from its left end and from its right end.  Level 0 is V itself:
+ * a second copy would not fit the bound.  *entries counts entries of T: 3 (n / 63) and a few per level, at least 1 and at most
+ * n / 16 + 4096.  The index holds values only, never positions a query would use as an address; it is opaque otherwise and
+ * valid for as long as V does not change.
+ *
+ * Longest common extension.  Text S[0..n) with its ISA and LCP (LCP[i] = the common prefix of the suffixes of ranks i - 1 and
+ * i), or a string set with the arrays of psacx_construct_gsa_* and its m + 1 offsets.
+ *
+ *     end(p) = n in the plain form (d_offsets == NULL, m ignored); in the set form the end of the string that holds p: the
+ *              smallest offset above p, clamped to (p, n].  A position >= n is the empty suffix and its end is itself.
+ *     L      = min(end(a) - a, end(b) - b)
+ *     lce_e(a, b) = max { d <= L : #{ j < d : S[a+j] != S[b+j] } <= e },   e = max_mismatch; e = 0 is the plain LCE.
+ *
+ * From the arrays, for a != b and both below n, with r = ISA[a] and s = ISA[b]:
+ *
+ *     lce_0(a, b) = min LCP[min(r, s) + 1 .. max(r, s) + 1);           lce_0(a, a) = end(a) - a.
+ *
+ * For e > 0 the kangaroo walk: add lce_0(a + d, b + d) to d; stop when d >= L; otherwise the byte at d differs by definition,
+ * and while the budget lasts it is stepped over and the walk goes on.  At most e + 1 range minima per pair.
+ *  - The offsets are only searched (one binary search per side), never trusted, as in psacx_occurrences_dev_*.
+ *  - The set form with e = 0 and a != b searches no offsets: the generalized LCP is cut at string ends already.
+ *
+ * Totality.  Whatever V, ISA, LCP, index and offsets hold, nothing is read out of range: every address follows from lo, hi, a,
+ * b and n, an ISA entry >= n is clamped to n - 1, and offsets are read inside their m + 1 entries.  Every loop ends.
+ * arg_j lies in range_j or equals n.  len <= n - max(a, b), and 0 for a position >= n.  On arrays that are not the ISA, LCP and
+ * index of one text, the values are otherwise unspecified.
+ *
+ * psacx_rmq_index_dev_*: builds the index of d_values into d_index; d_index == NULL is the size query (d_values may be NULL
+ * then).  n == 0 is legal.  It is built once per array and handed to the calls below, as the lookup table is: no query call
+ * does O(n) work.  n beyond the index type, or beyond 2^48, returns PSACX_ERANGE.  After psacx_profile(ctx, 1),
+ * psacx_stats.ms_rmq_build receives the time of the level-1 kernel alone, the one pass over the values (tools/lce_time.py).
+ * psacx_rmq_dev_*: d_lo / d_hi hold q range ends each; d_min / d_arg receive q entries each.  Either may be NULL (the first
+ * minimum is then not searched for); both NULL returns PSACX_EINVAL.  q == 0 returns PSACX_OK.  Nothing is allocated per call,
+ * and no input is written.  Sixteen lanes answer one range: two 64-entry groups of V at most, one entry of the index per lane
+ * above them, one wait; the position costs a second walk of at most 2 levels - 1 groups.
+ * psacx_lce_dev_*: d_index is the range-minimum index of d_LCP; d_a / d_b hold q positions each, d_len receives q lengths.
+ * d_offsets != NULL with m == 0 or m > n returns PSACX_EINVAL.
+ * psacx_rmq_* / psacx_lce_*: the host-pointer forms.  They stage the arrays, build the index, copy the results back, and free
+ * what they allocated on every path. */
+int psacx_rmq_index_dev_u32(psacx_ctx* ctx, const uint32_t* d_values, uint64_t n, uint32_t* d_index, uint64_t* entries);
+int psacx_rmq_index_dev_u64(psacx_ctx* ctx, const uint64_t* d_values, uint64_t n, uint64_t* d_index, uint64_t* entries);
+int psacx_rmq_dev_u32(psacx_ctx* ctx, const uint32_t* d_values, uint64_t n, const uint32_t* d_index,
+                      const uint32_t* d_lo, const uint32_t* d_hi, uint64_t q, uint32_t* d_min, uint32_t* d_arg);
+int psacx_rmq_dev_u64(psacx_ctx* ctx, const uint64_t* d_values, uint64_t n, const uint64_t* d_index,
+                      const uint64_t* d_lo, const uint64_t* d_hi, uint64_t q, uint64_t* d_min, uint64_t* d_arg);
+int psacx_lce_dev_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint32_t* d_ISA, const uint32_t* d_LCP,
+                      const uint32_t* d_index, const uint32_t* d_a, const uint32_t* d_b, uint64_t q, uint64_t max_mismatch,
+                      uint32_t* d_len);
+int psacx_lce_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint64_t* d_ISA, const uint64_t* d_LCP,
+                      const uint64_t* d_index, const uint64_t* d_a, const uint64_t* d_b, uint64_t q, uint64_t max_mismatch,
+                      uint64_t* d_len);
+int psacx_rmq_u32(psacx_ctx* ctx, const uint32_t* values, uint64_t n, const uint32_t* lo, const uint32_t* hi, uint64_t q,
+                  uint32_t* min, uint32_t* arg);
+int psacx_rmq_u64(psacx_ctx* ctx, const uint64_t* values, uint64_t n, const uint64_t* lo, const uint64_t* hi, uint64_t q,
+                  uint64_t* min, uint64_t* arg);
+int psacx_lce_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* ISA, const uint32_t* LCP,
+                  const uint32_t* a, const uint32_t* b, uint64_t q, uint64_t max_mismatch, uint32_t* len);
+int psacx_lce_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* ISA, const uint64_t* LCP,
+                  const uint64_t* a, const uint64_t* b, uint64_t q, uint64_t max_mismatch, uint64_t* len);
+
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP
  * (suffix_array.hpp:183-194, :217-228; src/psac.cpp:85-93 block-decomposes the input).  A psacx_multi stands for the

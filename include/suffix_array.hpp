@@ -780,4 +780,78 @@ match_lists<index_t> match(suffix_array<char, index_t, LCP, false>& sa, simple_d
     return psacx::match_of(sa, text, &soff, patterns, k, suffixes, max_len);
 }
 
+// Longest common extension (psacx.h: "range minimum and longest common extension"): len[i] = how far the text positions a[i]
+// and b[i] agree when up to max_mismatch differing characters are stepped over, from local_B (the inverse suffix array) and
+// local_LCP alone -- the text is not needed.  A position at or beyond n is the empty suffix.  The suffix array must have been
+// constructed with its LCP.  One rank only, as match.
+namespace psacx {
+template <typename index_t, bool LC>
+std::vector<index_t> lce_of(suffix_array<char, index_t, true, LC>& sa, const std::vector<uint64_t>* soff, const std::vector<index_t>& a,
+                            const std::vector<index_t>& b, std::size_t max_mismatch) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* isa, const uint32_t* lcp, const uint32_t* x, const uint32_t* y,
+                       uint64_t q, uint64_t e, uint32_t* len) { return psacx_lce_u32(c, n, o, m, isa, lcp, x, y, q, e, len); }
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* isa, const uint64_t* lcp, const uint64_t* x, const uint64_t* y,
+                       uint64_t q, uint64_t e, uint64_t* len) { return psacx_lce_u64(c, n, o, m, isa, lcp, x, y, q, e, len); }
+    };
+    if (a.size() != b.size()) throw std::runtime_error("lce: a and b differ in length");
+    if (sa.local_B.size() != sa.n || sa.local_LCP.size() != sa.n) throw std::runtime_error("lce: the suffix array holds no ISA and LCP of its text");
+    std::vector<W> x(a.begin(), a.end()), y(b.begin(), b.end()), len(a.size());
+    check(sa.context(), Call::run(sa.context(), sa.n, soff ? soff->data() : (const uint64_t*)nullptr, soff ? (uint64_t)soff->size() - 1 : 0,
+                                  reinterpret_cast<const W*>(sa.local_B.data()), reinterpret_cast<const W*>(sa.local_LCP.data()), x.data(), y.data(),
+                                  (uint64_t)x.size(), (uint64_t)max_mismatch, len.data()));
+    return std::vector<index_t>(len.begin(), len.end());
+}
+} // namespace psacx
+
+template <typename index_t, bool LC>
+std::vector<index_t> lce(suffix_array<char, index_t, true, LC>& sa, const std::vector<index_t>& a, const std::vector<index_t>& b,
+                         std::size_t max_mismatch = 0) {
+    if (sa.multi_context()) throw std::runtime_error("psacx: lce needs a single-rank communicator (the queries run on one GPU)");
+    return psacx::lce_of(sa, (const std::vector<uint64_t>*)nullptr, a, b, max_mismatch);
+}
+
+// The same over the arrays of a string set: an extension ends where either string does.
+template <typename index_t>
+std::vector<index_t> lce(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, const std::vector<index_t>& a,
+                         const std::vector<index_t>& b, std::size_t max_mismatch = 0) {
+    if (sa.multi_context()) throw std::runtime_error("psacx: lce needs a single-rank communicator (the queries run on one GPU)");
+    if (ss.sum_sizes != sa.n) throw std::runtime_error("lce: string set does not match the suffix array");
+    std::vector<uint64_t> soff(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) soff.push_back(soff.back() + ss.sizes[s]);
+    return psacx::lce_of(sa, &soff, a, b, max_mismatch);
+}
+
+// Range minima over local_LCP: min[i] is the minimum of local_LCP[lo[i] .. min(hi[i], n)) and arg[i] the smallest position that
+// holds it (the first minimum, as the reference's rmq<>::query returns it); an empty range gives all ones and n.
+template <typename index_t>
+struct range_minima {
+    std::vector<index_t> min, arg;
+};
+
+template <typename index_t, bool LC>
+range_minima<index_t> range_min(suffix_array<char, index_t, true, LC>& sa, const std::vector<index_t>& lo, const std::vector<index_t>& hi) {
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint32_t* v, uint64_t n, const uint32_t* l, const uint32_t* h, uint64_t q, uint32_t* m, uint32_t* a) {
+            return psacx_rmq_u32(c, v, n, l, h, q, m, a);
+        }
+        static int run(psacx_ctx* c, const uint64_t* v, uint64_t n, const uint64_t* l, const uint64_t* h, uint64_t q, uint64_t* m, uint64_t* a) {
+            return psacx_rmq_u64(c, v, n, l, h, q, m, a);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: range_min needs a single-rank communicator (the queries run on one GPU)");
+    if (lo.size() != hi.size()) throw std::runtime_error("range_min: lo and hi differ in length");
+    if (sa.local_LCP.size() != sa.n) throw std::runtime_error("range_min: the suffix array holds no LCP of its text");
+    std::vector<W> l(lo.begin(), lo.end()), h(hi.begin(), hi.end()), mn(lo.size()), at(lo.size());
+    psacx::check(sa.context(), Call::run(sa.context(), reinterpret_cast<const W*>(sa.local_LCP.data()), sa.n, l.data(), h.data(), (uint64_t)l.size(),
+                                         mn.data(), at.data()));
+    range_minima<index_t> out;
+    out.min.assign(mn.begin(), mn.end());
+    out.arg.assign(at.begin(), at.end());
+    return out;
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

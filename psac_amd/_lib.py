@@ -47,6 +47,8 @@ EXPORTS = [
     "psacx_locate_gsa_u32", "psacx_locate_gsa_u64", "psacx_occurrences_dev_u32", "psacx_occurrences_dev_u64",
     "psacx_match_dev_u32", "psacx_match_dev_u64", "psacx_match_gsa_dev_u32", "psacx_match_gsa_dev_u64",
     "psacx_match_u32", "psacx_match_u64", "psacx_match_gsa_u32", "psacx_match_gsa_u64",
+    "psacx_rmq_index_dev_u32", "psacx_rmq_index_dev_u64", "psacx_rmq_dev_u32", "psacx_rmq_dev_u64", "psacx_lce_dev_u32", "psacx_lce_dev_u64",
+    "psacx_rmq_u32", "psacx_rmq_u64", "psacx_lce_u32", "psacx_lce_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -145,6 +147,11 @@ def load():
         getattr(lib, "psacx_match_gsa_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, u32, u64, u64, vp, vp, vp]
         getattr(lib, "psacx_match_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, u32, u64, vp, vp, vp]
         getattr(lib, "psacx_match_gsa_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, u32, u64, vp, vp, vp]
+        getattr(lib, "psacx_rmq_index_dev_" + suf).argtypes = [vp, vp, u64, vp, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_rmq_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, vp]
+        getattr(lib, "psacx_lce_dev_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp]
+        getattr(lib, "psacx_rmq_" + suf).argtypes = [vp, vp, u64, vp, vp, u64, vp, vp]
+        getattr(lib, "psacx_lce_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, u64, u64, vp]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

@@ -529,6 +529,68 @@ def occurrences(SA, lb, ub, limit=0, offsets=None, ctx=None):
     return (start, pos) if so is None else (start, pos, sid)
 
 
+def rmq_index_device(ctx, d_values, n, d_index, index_bits):
+    """psacx_rmq_index_dev_*: the range-minimum index of n values resident in HBM (include/psacx.h: "range minimum and longest
+    common extension").  d_index=None is the size query.  Returns the number of index entries (of the index type)."""
+    fn = getattr(ctx._lib, "psacx_rmq_index_dev_u%d" % index_bits)
+    entries = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(fn(ctx.handle, opt(d_values), int(n), opt(d_index), C.byref(entries)))
+    return entries.value
+
+
+def rmq_device(ctx, d_values, n, d_index, d_lo, d_hi, q, d_min, d_arg, index_bits):
+    """psacx_rmq_dev_*: for each of q ranges [lo, min(hi, n)) the minimum and the smallest position that holds it; an empty range
+    gives all ones and n.  d_min or d_arg may be None."""
+    fn = getattr(ctx._lib, "psacx_rmq_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(fn(ctx.handle, opt(d_values), int(n), opt(d_index), opt(d_lo), opt(d_hi), int(q), opt(d_min), opt(d_arg)))
+
+
+def lce_device(ctx, n, d_off, m, d_isa, d_lcp, d_index, d_a, d_b, q, max_mismatch, d_len, index_bits):
+    """psacx_lce_dev_*: the longest common extension of q pairs of text positions with up to max_mismatch mismatches, from ISA, LCP
+    and the range-minimum index of LCP, all resident in HBM.  d_off (with m): the m + 1 offsets of a string set, None for one text."""
+    fn = getattr(ctx._lib, "psacx_lce_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(fn(ctx.handle, int(n), opt(d_off), int(m), opt(d_isa), opt(d_lcp), opt(d_index), opt(d_a), opt(d_b), int(q), int(max_mismatch),
+                 opt(d_len)))
+
+
+def rmq(values, lo, hi, ctx=None):
+    """psacx_rmq_*: (min, arg) arrays -- the minimum of values[lo[j]:hi[j]] and the first position holding it; an empty range
+    gives all ones and len(values).  Host arrays; everything is staged for the call."""
+    v = np.ascontiguousarray(values)
+    if v.dtype not in (np.uint32, np.uint64):
+        raise TypeError("rmq needs uint32 or uint64 values")
+    l, h = np.ascontiguousarray(lo, dtype=v.dtype), np.ascontiguousarray(hi, dtype=v.dtype)
+    if l.size != h.size:
+        raise ValueError("lo and hi differ in length")
+    mn, arg = np.zeros(l.size, v.dtype), np.zeros(l.size, v.dtype)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_rmq_u%d" % (v.dtype.itemsize * 8))
+    ctx.check(fn(ctx.handle, _ptr(v), v.size, _ptr(l), _ptr(h), l.size, _ptr(mn), _ptr(arg)))
+    return mn, arg
+
+
+def lce(ISA, LCP, a, b, max_mismatch=0, offsets=None, ctx=None):
+    """psacx_lce_*: how far the text positions a[j] and b[j] agree when up to max_mismatch differing characters are stepped over,
+    from the inverse suffix array and the LCP array alone.  offsets: the arrays are those of a string set (construct_gsa) and an
+    extension ends where either string does.  Host arrays; everything is staged for the call."""
+    isa, lcp = np.ascontiguousarray(ISA), np.ascontiguousarray(LCP)
+    if isa.dtype not in (np.uint32, np.uint64) or lcp.dtype != isa.dtype or lcp.size != isa.size:
+        raise TypeError("lce needs ISA and LCP of one length, both uint32 or both uint64")
+    pa, pb = np.ascontiguousarray(a, dtype=isa.dtype), np.ascontiguousarray(b, dtype=isa.dtype)
+    if pa.size != pb.size:
+        raise ValueError("a and b differ in length")
+    out = np.zeros(pa.size, isa.dtype)
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_lce_u%d" % (isa.dtype.itemsize * 8))
+    ctx.check(fn(ctx.handle, isa.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(isa), _ptr(lcp), _ptr(pa),
+                 _ptr(pb), pa.size, int(max_mismatch), _ptr(out)))
+    return out
+
+
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
     """check_SA / check_lcp on buffers resident in HBM (check_suffix_array.hpp:56-126).  Returns the four
     error counters of psacx_check_dev_*; all zero means correct."""
