@@ -138,12 +138,15 @@ int psacx_trim(psacx_ctx* ctx);
  *   LOCATE_SHAPE      psacx_locate_*: 1 = one pattern per lane (the default), 2 = eight lanes per pattern, 64 characters per step (A/B runs);
  *                     no effect on psacx_locate_gsa_*, which has the first shape only
  *   LOCATE_COUNT      psacx_locate_*: the kernel counts its fetches into psacx_stats.locate_fetches (slower; tools/locate_time.py)
- *   GENERIC_REBUCKET  the first round on one-word records runs the generic rebucket kernel, not its 32-bit form (A/B runs)          */
+ *   GENERIC_REBUCKET  the first round on one-word records runs the generic rebucket kernel, not its 32-bit form (A/B runs)
+ *   PLAIN_SIDE_KERNELS the tile histograms of the top digit and the tie scan of the one-word first round run their one-tile-per-workgroup
+ *                     kernels (top_digit_hist_kernel, tie_resolve_1w_kernel), not the persistent ones (parity tests, A/B runs)          */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
+    PSACX_OPT_PLAIN_SIDE_KERNELS,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);

@@ -773,7 +773,15 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
             PSACX_HIP(c, hipMemsetAsync(d_big, 0, sizeof(unsigned long long), c->stream));
             const uint64_t nb = (n + (uint64_t)TB * TI - 1) / ((uint64_t)TB * TI);
             if constexpr (sizeof(T) == 8) {
-                if (onew_recs)          // S1: the one-word records; the array the last pass did not write takes word 1 of the tied suffixes
+                // S1: the one-word records; the array the last pass did not write takes word 1 of the tied suffixes.  With the bytes of the
+                // last pass: persistent waves, a tile of 64 x 32 places each per trip, four workgroups per CU (sa_kernels.hpp;
+                // PSACX_OPT_PLAIN_SIDE_KERNELS pins the workgroup-per-tile kernel)
+                const uint64_t nwt = (n + (uint64_t)WAVE * TI - 1) / ((uint64_t)WAVE * TI);
+                if (onew_recs && tie_bytes && !kn.plain_side_kernels)
+                    hipLaunchKernelGGL((tie_resolve_1w_waves_kernel<TB, TI, TG>), dim3((unsigned)grid_for(c, nwt * WAVE, TB, 4)), dim3(TB), 0, c->stream,
+                                       reinterpret_cast<uint64_t*>(S1), reinterpret_cast<uint64_t*>(free_k1), reinterpret_cast<uint64_t*>(S2), n, onew_view, d_text, n,
+                                       tab, ks, d_big, (const uint8_t*)tie_bytes, nwt);
+                else if (onew_recs)
                     hipLaunchKernelGGL((tie_resolve_1w_kernel<TB, TI, TG>), dim3((unsigned)nb), dim3(TB), 0, c->stream, reinterpret_cast<uint64_t*>(S1),
                                        reinterpret_cast<uint64_t*>(free_k1), reinterpret_cast<uint64_t*>(S2), n, onew_view, d_text, n, tab, ks, d_big,
                                        (const uint8_t*)tie_bytes);

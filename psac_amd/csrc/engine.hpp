@@ -64,7 +64,9 @@ struct Knobs {
                                   // in one parent class (construct.hpp: isa_stripes; A/B runs)
     bool generic_rebucket = false; // PSACX_OPT_GENERIC_REBUCKET: the first round on one-word records runs rebucket_first_kernel, not its 32-bit form rebucket_first_1w_kernel
                                   // (sa_kernels.hpp; parity suite and A/B runs)
-    int locate_shape = 0;         // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (locate.hpp; A/B runs)
+    bool plain_side_kernels = false; // PSACX_OPT_PLAIN_SIDE_KERNELS: top_digit_hist_kernel and tie_resolve_1w_kernel (a workgroup per tile), not the persistent
+                                  // top_digit_hist_waves_kernel and tie_resolve_1w_waves_kernel (sa_kernels.hpp; parity tests and A/B runs)
+    int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (locate.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
 };
 
@@ -1148,7 +1150,13 @@ inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t*
             if (sc.h_base[0] * 4 >= samples * 3) return PSACX_RETRY_1STAGE;
             if (sc.h_base[0] * 8 > samples) return PSACX_RETRY_1W;
         }
-        hipLaunchKernelGGL((top_digit_hist_kernel<uint64_t, BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, text, n, n_text, tab, ks, tile_hist0);
+        // (persistent waves, a tile each per trip, five workgroups of 256 per CU -- 82 VGPRs: five waves per SIMD; four measured the same: sa_kernels.hpp; PSACX_OPT_PLAIN_SIDE_KERNELS pins the workgroup-per-tile form)
+        static_assert(TILE0 == 64 * WAVE, "top_digit_hist_waves_kernel: a wave takes a tile of 64 records per lane");
+        if (c->knobs.plain_side_kernels || (reinterpret_cast<uintptr_t>(tile_hist0) & 15u))
+            hipLaunchKernelGGL((top_digit_hist_kernel<uint64_t, BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, text, n, n_text, tab, ks, tile_hist0);
+        else
+            hipLaunchKernelGGL((top_digit_hist_waves_kernel<256>), dim3((unsigned)grid_for(c, ntiles * WAVE, 256, 5)), dim3(256), 0, c->stream, text, n, n_text, tab, ks,
+                               ntiles, tile_hist0);
         PSACX_HIP(c, hipGetLastError());
     }
     {

@@ -131,6 +131,7 @@ int psacx_configure(psacx_ctx* c, int option, uint64_t value) {
     case PSACX_OPT_LOCATE_SHAPE: if (value > 2) return PSACX_EINVAL; k.locate_shape = (int)value; return PSACX_OK;
     case PSACX_OPT_LOCATE_COUNT: k.locate_count = value != 0; return PSACX_OK;
     case PSACX_OPT_GENERIC_REBUCKET: k.generic_rebucket = value != 0; return PSACX_OK;
+    case PSACX_OPT_PLAIN_SIDE_KERNELS: k.plain_side_kernels = value != 0; return PSACX_OK;
     default: return PSACX_EINVAL;
     }
 }
@@ -145,7 +146,8 @@ int psacx_configure_from_env(psacx_ctx* c) {
         {"PSACX_NO_DIGIT_BYTES", PSACX_OPT_NO_DIGIT_BYTES}, {"PSACX_NO_BUCKET_SORT", PSACX_OPT_NO_BUCKET_SORT}, {"PSACX_NO_HEAVY", PSACX_OPT_NO_HEAVY},
         {"PSACX_NO_WHOLE", PSACX_OPT_NO_WHOLE}, {"PSACX_NO_LAZY_RANKS", PSACX_OPT_NO_LAZY_RANKS},
         {"PSACX_NO_EARLY_OUT", PSACX_OPT_NO_EARLY_OUT}, {"PSACX_NO_SPREAD_CURSORS", PSACX_OPT_NO_SPREAD_CURSORS},
-        {"PSACX_LOCATE_COUNT", PSACX_OPT_LOCATE_COUNT}, {"PSACX_GENERIC_REBUCKET", PSACX_OPT_GENERIC_REBUCKET}};
+        {"PSACX_LOCATE_COUNT", PSACX_OPT_LOCATE_COUNT}, {"PSACX_GENERIC_REBUCKET", PSACX_OPT_GENERIC_REBUCKET},
+        {"PSACX_PLAIN_SIDE_KERNELS", PSACX_OPT_PLAIN_SIDE_KERNELS}};
     (void)psacx_configure(c, PSACX_OPT_RESET, 0);
     for (const auto& f : flags) if (psacx_debug_env(f.name)) (void)psacx_configure(c, f.option, 1);
     if (const char* e = psacx_debug_env("PSACX_DIET_CAP")) (void)psacx_configure(c, PSACX_OPT_DIET_CAP, strtoull(e, nullptr, 10));

@@ -328,6 +328,108 @@ __global__ __launch_bounds__(BLOCK) void top_digit_hist_kernel(const uint8_t* __
     for (int d = threadIdx.x; d < RADIX; d += BLOCK) tile_hist[(uint64_t)blockIdx.x * RADIX + d] = lh[0][d] + lh[1][d] + lh[2][d] + lh[3][d];
 }
 
+// The same table in the shape of radix_tile_hist_bytes_kernel (radix.hpp), with persistent waves.  top_digit_hist_kernel spends a
+// workgroup's life -- table, zeroed counters, barrier, ONE round of loads, barrier, stores -- on 4 KB of text, so it runs at the latency of
+// that one round trip (1.6 TB/s at 2^32 characters against 4.4 for the byte histograms).  Here a WAVE owns a tile of 64 x 64 records and
+// loops over tiles t, t + (waves of the grid), ...; the grid is sized to the device.  A lane takes 64 consecutive records: the 64 + nch - 1
+// characters of their windows as four to six aligned 16-byte pieces, asked for one tile ahead, so that a wave counts one tile while the
+// loads of its next are in flight.  The counters are the wave's own 256 in LDS: no workgroup barrier after the one that publishes ctab.
+// Lanes whose run holds short suffixes (records below ks.spec), ends beyond n, or whose pieces would reach outside [0, n_text), take
+// the record-by-record path of top_digit_hist_kernel.  The pieces are aligned by ADDRESS, so any text pointer takes the fast path.
+// tile_hist must be 16-byte aligned (a lane stores four counters at once).
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK, 4) void top_digit_hist_waves_kernel(const uint8_t* __restrict__ text, uint64_t n, uint64_t n_text, CodeTable tab, KeyShape ks,
+                                                                        uint64_t ntiles, unsigned* __restrict__ tile_hist) {
+    constexpr int NW = BLOCK / WAVE, PER = 64, TILE = WAVE * PER, NP = 6, ND = 4 * NP;
+    static_assert(RADIX == 4 * WAVE, "a lane stores four counters");
+    __shared__ uint16_t ctab[256];
+    __shared__ __attribute__((aligned(16))) unsigned lh[NW][RADIX];
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = lane_id();
+    for (int i = threadIdx.x; i < 256; i += BLOCK) ctab[i] = tab.c[i];
+    for (int i = threadIdx.x; i < NW * RADIX; i += BLOCK) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    unsigned* const my = lh[wave];
+    const unsigned lc = ks.lc;
+    const unsigned nch = (8 + lc - 1) / lc < ks.c1 ? (8 + lc - 1) / lc : ks.c1;     // characters that reach into the top digit (1 .. 8)
+    const unsigned down = nch * lc > 8 ? nch * lc - 8 : 0, up = nch * lc < 8 ? 8 - nch * lc : 0;
+    const unsigned tmask = (1u << (nch * lc)) - 1u;                                  // (nch * lc <= 15)
+    const uint64_t nwaves = (uint64_t)gridDim.x * NW;
+    // the pieces of this lane's run in tile t; false: the lane takes the slow path (or the tile does not exist)
+    auto fetch = [&](uint64_t t, uint4 (&q)[NP], unsigned& lead) -> bool {
+        lead = 0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) q[i] = make_uint4(0, 0, 0, 0);
+        if (t >= ntiles) return false;
+        const uint64_t rec0 = t * TILE + (uint64_t)lane * PER;
+        if (rec0 < ks.spec || rec0 + PER > n) return false;
+        const uint64_t i0 = rec0 - ks.spec;
+        lead = (unsigned)(reinterpret_cast<uintptr_t>(text + i0) & 15u);
+        const unsigned np = (lead + PER + nch - 1 + 15) / 16;                        // 4 .. 6 pieces
+        if (i0 < lead || i0 - lead + 16ull * np > n_text) return false;
+        const uint4* __restrict__ a = reinterpret_cast<const uint4*>(text + (i0 - lead));
+#pragma unroll
+        for (int i = 0; i < NP; ++i) if ((unsigned)i < np) q[i] = a[i];
+        return true;
+    };
+    uint64_t tile = (uint64_t)blockIdx.x * NW + wave;
+    uint4 qa[NP];
+    unsigned la;
+    bool fa = fetch(tile, qa, la);
+    while (tile < ntiles) {
+        const uint64_t next = tile + nwaves;
+        uint4 qb[NP];
+        unsigned lb;
+        const bool fb = fetch(next, qb, lb);
+        if (fa) {
+            uint32_t w[ND + 1];
+#pragma unroll
+            for (int i = 0; i < NP; ++i) { w[4 * i] = qa[i].x; w[4 * i + 1] = qa[i].y; w[4 * i + 2] = qa[i].z; w[4 * i + 3] = qa[i].w; }
+            w[ND] = 0;
+            if (la) {                    // the window to byte 0: by la & 3 bytes, then by la >> 2 words
+#pragma unroll
+                for (int j = 0; j < ND; ++j) w[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], la & 3u);
+                if (la & 4u) {
+#pragma unroll
+                    for (int j = 0; j + 1 < ND; ++j) w[j] = w[j + 1];
+                }
+                if (la & 8u) {
+#pragma unroll
+                    for (int j = 0; j + 2 < ND; ++j) w[j] = w[j + 2];
+                }
+            }
+            // character k of the run enters the window of record k - (nch - 1)
+            unsigned t = 0;
+#pragma unroll
+            for (int k = 0; k < PER + 7; ++k) {
+                if (k < PER || (unsigned)(k - PER + 1) < nch) {
+                    t = ((t << lc) | (unsigned)ctab[(w[k >> 2] >> (8 * (k & 3))) & 255u]) & tmask;
+                    if (k >= 7 || (unsigned)k + 1 >= nch) atomicAdd(&my[((t >> down) << up) & 255u], 1u);
+                }
+            }
+        } else {
+            const uint64_t rec0 = tile * TILE + (uint64_t)lane * PER;
+#pragma unroll 1
+            for (int j = 0; j < PER; ++j) {
+                const uint64_t rec = rec0 + j;
+                if (rec >= n) break;
+                const uint64_t i = record_suffix(rec, ks.spec, n);
+                unsigned t = 0;
+                for (unsigned q = 0; q < nch; ++q) t = (t << lc) | (unsigned)((i + q < n_text) ? ctab[text[i + q]] : (uint16_t)0);
+                atomicAdd(&my[((t >> down) << up) & 255u], 1u);
+            }
+        }
+        xrun_order();
+        uint4* const mine = reinterpret_cast<uint4*>(my) + lane;
+        const uint4 cnt = *mine;
+        *mine = make_uint4(0, 0, 0, 0);
+        reinterpret_cast<uint4*>(tile_hist + tile * RADIX)[lane] = cnt;
+        xrun_order();
+#pragma unroll
+        for (int i = 0; i < NP; ++i) qa[i] = qb[i];
+        la = lb; fa = fb; tile = next;
+    }
+}
+
 // cnt characters of the text from position q0 on as codes of lc bits each, the first on top (cnt * lc <= 64; zeros beyond the end of the
 // text).  Away from the end the characters are read as 8-byte pieces, four asked for at a time, instead of one dependent byte load
 // after the other (a text with interspersed repeats sends a quarter of its suffixes through gather_prefix_ties_kernel: 42 byte loads
@@ -2140,6 +2242,242 @@ __global__ __launch_bounds__(BLOCK, 4) void tie_resolve_1w_kernel(uint64_t* __re
             if (moved) R[e + rank] = (key << ow.sfield) | sa;
         }
     }
+}
+
+// window_low_and_word2 for stretches of up to 64 characters (random DNA at 2^32 characters: 12 + 32, which that function reads as two
+// stretches one after the other, a predicated step per character and piece: 64 steps of some ten instructions each, two thirds of the
+// instructions of the tie scan, which is bound by issuing them).  One round of loads, eight 8-byte pieces in flight; the codes of a 32-bit
+// word of the text are put together in 32 bits and appended to word 1 or word 2 in one step -- the word that holds the border between the
+// two, or the end of the stretch, is split (which words those are is the same for every lane).  Same values as window_low_and_word2.
+__device__ __forceinline__ void window_low_and_word2_wide(const uint8_t* __restrict__ text, uint64_t n_text, const uint16_t* ctab, const KeyShape& ks,
+                                                          uint64_t sa, uint64_t have, unsigned lo1, uint64_t& k1, uint64_t& k2) {
+    const unsigned lc = ks.lc;
+    const unsigned nlow = (lo1 + lc - 1) / lc < ks.c1 ? (lo1 + lc - 1) / lc : ks.c1;
+    const unsigned lowbits = nlow * lc;
+    const uint64_t q0 = sa + ks.c1 - nlow;
+    const unsigned L = nlow + ks.c2;
+    if (L > 64 || q0 + 64 > n_text) { window_low_and_word2<uint64_t>(text, n_text, ctab, ks, sa, have, lo1, k1, k2); return; }
+    uint32_t x[16];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        uint64_t v = 0;
+        if ((unsigned)(8 * c) < L) __builtin_memcpy(&v, text + q0 + 8 * c, 8);
+        x[2 * c] = (uint32_t)v; x[2 * c + 1] = (uint32_t)(v >> 32);
+    }
+    uint64_t lo = 0, w2 = 0;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+        if ((unsigned)(4 * d) < L) {
+            const uint32_t e0 = ctab[x[d] & 255u], e1 = ctab[(x[d] >> 8) & 255u], e2 = ctab[(x[d] >> 16) & 255u], e3 = ctab[x[d] >> 24];
+            const uint32_t part = (((((e0 << lc) | e1) << lc) | e2) << lc) | e3;
+            const unsigned ab = L - 4u * d < 4u ? L - 4u * d : 4u;                                    // characters of this word inside the stretch,
+            const unsigned a = nlow > 4u * d ? (nlow - 4u * d < 4u ? nlow - 4u * d : 4u) : 0u;        // ... those of word 1 among them
+            const unsigned b = ab - a;
+            if (a == 4u) lo = (lo << (4u * lc)) | part;
+            else if (b == 4u) w2 = (w2 << (4u * lc)) | part;
+            else {
+                const uint64_t P = part;
+                if (a) lo = (lo << (a * lc)) | (P >> ((4u - a) * lc));
+                if (b) w2 = (w2 << (b * lc)) | ((P >> ((4u - ab) * lc)) & ((1ull << (b * lc)) - 1ull));
+            }
+        }
+    }
+    k1 = lowbits >= 64 ? lo : (((have >> lowbits) << lowbits) | lo);
+    k2 = w2;
+}
+
+// tie_resolve_1w_kernel with its chain of dependent round trips shortened (tb is required; R, W1, S2 and big end up the same).  That kernel
+// makes five round trips to memory per workgroup life -- tables, bytes, a divergent walk of every lane's candidates with as many trips as
+// the unluckiest lane has candidates, records of the groups, their text -- for some 64 candidates and 32 groups per tile of random text.  Here
+//  - the workgroups are persistent (the grid is sized to the device): ctab and the bucket starts are loaded once.  A tile is the 64 x 32
+//    places of one WAVE; a wave takes the tiles w, w + (waves of the grid), ... in order, on its own: no barrier after the one that
+//    publishes the tables (a barrier per tile made every wave wait for the one with the longest chain: 4.84 ms against 5.03);
+//  - the bytes of the next tile are asked for before the candidates of this one are looked at.  The byte before a lane's 32 places and
+//    the byte after them come from the neighbouring lanes; only the two bytes beside the tile are loaded (lanes 0 and 63, with the rest);
+//  - the wave compacts the candidate pairs of its tile into a list in LDS, in place order, and every lane tests one candidate per
+//    trip: ceil(candidates / 64) dependent record loads per wave.  Pair p of a tile is its places p - 1 and p (p = 0 .. 64 x 32; pair 0
+//    reaches into the tile before, whose wave tests it too as its last pair).  A tied pair whose predecessor in the list is not the tied
+//    pair p - 1 starts a group at place p - 1: the leaders come out in place order, and the wave orders its own groups, eight lanes per
+//    group as in tie_resolve_1w_kernel;
+//  - the two chains of a tile overlap with its neighbours': the record loads of the first 64 candidates of tile t are issued BEFORE the
+//    groups of tile t - 1 are ordered (records, then their text) and looked at after; in the group pass the records of the next eight
+//    groups are asked for before the text of these eight.
+// With the chains overlapped the kernel is bound by the instructions it issues (4.57 ms at 2^32 characters of random DNA whatever the
+// chains looked like), so
+//  - the windows of the tied suffixes are read by window_low_and_word2_wide (4.57 -> 4.02 ms together with the next item);
+//  - a tile that lies inside one bucket of the top digit asks the bucket table once (TileBucket), not once per candidate and group;
+//  - the record behind a group's eight places is read only when all eight tie.
+template <int BLOCK, int ITEMS, int G>
+__global__ __launch_bounds__(BLOCK, 4) void tie_resolve_1w_waves_kernel(uint64_t* __restrict__ R, uint64_t* __restrict__ W1, uint64_t* __restrict__ S2,
+                                                                     uint64_t n, OneWordView ow, const uint8_t* __restrict__ text, uint64_t n_text,
+                                                                     CodeTable tab, KeyShape ks, unsigned long long* __restrict__ big,
+                                                                     const uint8_t* __restrict__ tb, uint64_t ntiles) {
+    typedef uint64_t T;
+    constexpr int NW = BLOCK / WAVE, WT = WAVE * ITEMS;          // WT: places of a tile
+    static_assert(ITEMS == 32, "a thread takes the 32 bytes of its places as two 16-byte pieces");
+    static_assert(G == 8, "eight lanes per group");
+    static_assert(WT < 65536, "pairs and places of a tile as 16-bit entries");
+    __shared__ uint16_t ctab[256];
+    __shared__ unsigned long long s_off[257];
+    __shared__ uint16_t cands[NW][WT + 2];           // the candidate pairs of every wave's tile, ascending
+    __shared__ uint16_t leaders[NW][WT / 2 + 2];     // the first places of its groups, ascending (of the tile before, until its groups are ordered)
+    for (int i = threadIdx.x; i < 256; i += BLOCK) ctab[i] = tab.c[i];
+    for (int i = threadIdx.x; i < 257; i += BLOCK) s_off[i] = ow.off[i];
+    __syncthreads();
+    ow.off = s_off;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = lane_id(), m = lane & (G - 1), seg0 = lane & ~(unsigned)(G - 1);
+    uint16_t* const cl = cands[wave];
+    uint16_t* const ll = leaders[wave];
+    const T smask = (1ull << ow.sfield) - 1;
+    auto starts_bucket = [&](uint64_t e) -> bool { return ow.off[onew_bucket(ow, e)] == e; };
+    // the bytes of this lane's places in a tile; ext: the byte before the tile (lane 0) or after it (the last lane), 256 where there is none
+    auto fetch = [&](uint64_t tile, uint4& q0, uint4& q1, unsigned& ext) {
+        q0 = make_uint4(0, 0, 0, 0); q1 = q0; ext = 256u;
+        if (tile >= ntiles) return;
+        const uint64_t t0 = tile * WT, e0 = t0 + (uint64_t)lane * ITEMS;
+        if (e0 < n) { q0 = *reinterpret_cast<const uint4*>(tb + e0); q1 = *reinterpret_cast<const uint4*>(tb + e0 + 16); }
+        if (lane == 0 && t0) ext = tb[t0 - 1];
+        if (lane == WAVE - 1 && t0 + WT < n) ext = tb[t0 + WT];
+    };
+    // the groups of a tile (first place wb, nl leaders in ll): eight lanes per group, one member each (tie_resolve_1w_kernel, pass 2)
+    // (the record behind a group's eight places is read only when all eight tie: tie_resolve_1w_kernel reads it for every group, a line more for half of them)
+    struct GroupRecs { uint64_t e, bend; unsigned b; bool live; T rec; };
+    // A tile that lies inside ONE bucket of the top digit with every place its pairs and groups touch (a bucket is 1 / 256 of a random text:
+    // nearly every tile does) asks the bucket table once, not once per candidate and group: TileBucket.one, then b and its end hold for all
+    struct TileBucket { bool one; unsigned b; uint64_t end; };
+    auto tile_bucket = [&](uint64_t wb) -> TileBucket {
+        TileBucket t;
+        t.b = (unsigned)__builtin_amdgcn_readfirstlane((int)onew_bucket(ow, wb ? wb - 1 : 0));
+        t.end = ow.off[t.b + 1];
+        t.one = __builtin_amdgcn_readfirstlane((int)(t.end > wb + WT + G)) != 0;          // (places wb - 1 .. wb + WT + G - 1; no bucket starts at wb .. wb + WT then)
+        return t;
+    };
+    auto load_groups = [&](uint64_t wb, const TileBucket& tk, unsigned g0, unsigned nl) -> GroupRecs {
+        GroupRecs r;
+        const unsigned g = g0 + lane / G;
+        r.live = g < nl;
+        r.e = wb + (r.live ? (unsigned)ll[g] : 0u);
+        r.b = tk.b; r.bend = tk.end;              // a group does not reach over the end of its bucket
+        if (!tk.one) { r.b = onew_bucket(ow, r.e); r.bend = ow.off[r.b + 1]; }
+        r.rec = (r.live && r.e + m < r.bend) ? R[r.e + m] : (T)0;
+        return r;
+    };
+    auto order_groups = [&](uint64_t wb, const TileBucket& tk, unsigned nl) {
+        if (nl == 0) return;
+        GroupRecs nx = load_groups(wb, tk, 0, nl);
+        for (unsigned g0 = 0; g0 < nl; g0 += WAVE / G) {
+            const GroupRecs c = nx;
+            if (g0 + WAVE / G < nl) nx = load_groups(wb, tk, g0 + WAVE / G, nl);        // (other groups: what is stored below does not touch their places)
+            const T key = shfl<T>(c.rec >> ow.sfield, (int)seg0);
+            const bool same = c.live && c.e + m < c.bend && (c.rec >> ow.sfield) == key;
+            const unsigned mine = (unsigned)(__ballot(same) >> seg0) & ((1u << G) - 1u);
+            const unsigned len = (unsigned)__builtin_ctz(~mine);                // members: the leading run of equal prefixes
+            const bool full = c.live && len == (unsigned)G && c.e + G < c.bend;
+            bool too_long = false;
+            if (__ballot(full)) too_long = full && (R[c.e + G] >> ow.sfield) == key;
+            const bool member = c.live && !too_long && m < len;
+            if (c.live && too_long && m == 0) atomicAdd(big, 1ull);
+            const T sa = c.rec & smask;
+            T k1 = ~(T)0, k2 = ~(T)0;
+            if (member) {
+                window_low_and_word2_wide(text, n_text, ctab, ks, sa, (T)onew_word1(ow, c.b, c.rec), ow.lo1, k1, k2);
+            }
+            unsigned rank = 0;
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const T o1 = shfl<T>(k1, (int)(seg0 + j)), o2 = shfl<T>(k2, (int)(seg0 + j));
+                if (o1 < k1 || (o1 == k1 && (o2 < k2 || (o2 == k2 && (unsigned)j < m)))) ++rank;          // (equal windows keep their order: stable)
+            }
+            const bool moved = ((unsigned)(__ballot(member && rank != m) >> seg0) & ((1u << G) - 1u)) != 0;
+            if (member) {
+                W1[c.e + rank] = k1; S2[c.e + rank] = k2;
+                if (moved) R[c.e + rank] = (key << ow.sfield) | sa;
+            }
+        }
+    };
+    const uint64_t nwaves = (uint64_t)gridDim.x * NW;
+    uint64_t tile = (uint64_t)blockIdx.x * NW + wave;
+    uint4 a0, a1;
+    unsigned ax;
+    fetch(tile, a0, a1, ax);
+    uint64_t pwb = 0;               // the tile before: its first place, its bucket and the number of its groups, their leaders in ll
+    TileBucket ptk = {true, 0u, 0ull};
+    unsigned pnl = 0;
+    while (tile < ntiles) {
+        const uint64_t next = tile + nwaves;
+        uint4 b0, b1;
+        unsigned bx;
+        fetch(next, b0, b1, bx);
+        // (a long group met by anybody sends ALL ties through the caller's radix path: what this kernel would still order is thrown away)
+        const unsigned long long any_big = __hip_atomic_load(big, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t wb = tile * WT, e0 = wb + (uint64_t)lane * ITEMS;
+        const uint32_t w[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        const unsigned first = w[0] & 255u, last = w[7] >> 24;
+        unsigned before = shfl<unsigned>(last, (int)((lane + WAVE - 1) & (WAVE - 1))), after = shfl<unsigned>(first, (int)((lane + 1) & (WAVE - 1)));
+        if (lane == 0) before = ax;
+        if (lane == WAVE - 1) after = ax;
+        // bit j: the places e0 + j - 1 and e0 + j agree in their bytes (j = 0 .. 31; the last lane: j = 32 too, the wave's last pair)
+        uint64_t cand = 0;
+        {
+            unsigned prevb = before & 255u;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                const uint32_t x = w[d] ^ ((w[d] << 8) | prevb);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) if (((x >> (8 * k)) & 255u) == 0) cand |= 1ull << (4 * d + k);
+                prevb = w[d] >> 24;
+            }
+            if (before > 255u) cand &= ~1ull;
+            if (lane == WAVE - 1 && after == last) cand |= 1ull << ITEMS;
+            const uint64_t room = e0 < n ? n - e0 : 0;          // the second place of a pair lies inside the array
+            if (room <= (uint64_t)ITEMS) cand &= (1ull << room) - 1ull;
+        }
+        const unsigned cnt = (unsigned)__builtin_popcountll(cand);
+        const unsigned incl = wave_scan_inclusive<unsigned>(cnt, OpSum());
+        const unsigned nc = (unsigned)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
+        if (nc) {
+            unsigned o = incl - cnt;
+            while (cand) {
+                cl[o++] = (uint16_t)(lane * ITEMS + (unsigned)__builtin_ctzll(cand));
+                cand &= cand - 1;
+            }
+            xrun_order();
+        }
+        // the records of the first 64 candidates are asked for, the groups of the tile before are ordered, then the records are looked at
+        // (a group of the tile before may reach into this one and rewrite the suffix fields there: the prefixes compared here stay)
+        const unsigned p0 = lane < nc ? (unsigned)cl[lane] : ~0u;
+        T x0 = 0, y0 = 0;
+        if (lane < nc) { x0 = R[wb + p0 - 1]; y0 = R[wb + p0]; }
+        order_groups(pwb, ptk, any_big ? 0u : pnl);
+        xrun_order();
+        const TileBucket tk = tile_bucket(wb);
+        unsigned nl = 0;
+        {
+            unsigned carry_p = ~0u, carry_t = 0;
+            for (unsigned i0 = 0; i0 < nc; i0 += WAVE) {
+                const bool have = i0 + lane < nc;
+                unsigned p = p0;
+                T x = x0, y = y0;
+                if (i0) {
+                    p = have ? (unsigned)cl[i0 + lane] : ~0u;
+                    if (have) { x = R[wb + p - 1]; y = R[wb + p]; }
+                }
+                const unsigned tied = (have && (x >> ow.sfield) == (y >> ow.sfield) && (tk.one || !starts_bucket(wb + p))) ? 1u : 0u;
+                unsigned pp = shfl<unsigned>(p, (int)((lane + WAVE - 1) & (WAVE - 1))), pt = shfl<unsigned>(tied, (int)((lane + WAVE - 1) & (WAVE - 1)));
+                if (lane == 0) { pp = carry_p; pt = carry_t; }
+                const bool lead = tied && p != 0 && !(pt && pp + 1 == p);
+                const uint64_t L = __ballot(lead);
+                if (lead) ll[nl + (unsigned)__builtin_popcountll(L & lanemask_lt())] = (uint16_t)(p - 1);
+                nl += (unsigned)__builtin_popcountll(L);
+                carry_p = (unsigned)__builtin_amdgcn_readlane((int)p, WAVE - 1); carry_t = (unsigned)__builtin_amdgcn_readlane((int)tied, WAVE - 1);
+            }
+        }
+        xrun_order();
+        pwb = wb; ptk = tk; pnl = nl;
+        a0 = b0; a1 = b1; ax = bx;
+        tile = next;
+    }
+    order_groups(pwb, ptk, __hip_atomic_load(big, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0u : pnl);
 }
 
 // Stage 2, fallback: K1 / V are word 1 and suffix of the tied records (written by the compaction);
