@@ -66,7 +66,7 @@ struct Knobs {
                                   // (sa_kernels.hpp; parity suite and A/B runs)
     bool plain_side_kernels = false; // PSACX_OPT_PLAIN_SIDE_KERNELS: top_digit_hist_kernel and tie_resolve_1w_kernel (a workgroup per tile), not the persistent
                                   // top_digit_hist_waves_kernel and tie_resolve_1w_waves_kernel (sa_kernels.hpp; parity tests and A/B runs)
-    int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (locate.hpp; A/B runs)
+    int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (search.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
 };
 

@@ -6,6 +6,7 @@
 // The text is no argument of any call here.
 #include "engine.hpp"
 #include "rmq.hpp"
+#include "staging.hpp"
 
 namespace psacx {
 
@@ -93,29 +94,7 @@ int lce_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, const T
     return PSACX_OK;
 }
 
-// The host-pointer forms: the arrays are staged in device memory of their own for the time of the call, the index is built,
-// the results come back, and everything allocated is freed on every path.
-struct Staging {
-    psacx_ctx* c; int rc = PSACX_OK; std::vector<void*> mem;
-    explicit Staging(psacx_ctx* ctx) : c(ctx) {}
-    ~Staging() { for (void* p : mem) (void)hipFree(p); }
-    void* alloc(size_t bytes) {
-        if (rc != PSACX_OK) return nullptr;
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-        if (e != hipSuccess) { c->hip_err = std::string("hipMalloc(rmq): ") + hipGetErrorString(e); (void)hipGetLastError(); rc = PSACX_ENOMEM; return nullptr; }
-        mem.push_back(p);
-        return p;
-    }
-    void step(hipError_t r) { if (rc == PSACX_OK && r != hipSuccess) { c->hip_err = hipGetErrorString(r); (void)hipGetLastError(); rc = PSACX_EHIP; } }
-    void* upload(const void* src, size_t bytes) {
-        void* p = alloc(bytes);
-        if (p && src && bytes) step(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream));
-        return p;
-    }
-    void download(void* dst, const void* src, size_t bytes) { if (rc == PSACX_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); }
-};
-
+// The host-pointer forms: the arrays are staged (staging.hpp), the index is built and the results come back.
 template <typename T>
 int rmq_host(psacx_ctx* c, const T* values, uint64_t n, const T* lo, const T* hi, uint64_t q, T* mn, T* arg) {
     if (!c || (!mn && !arg)) return PSACX_EINVAL;
@@ -125,7 +104,7 @@ int rmq_host(psacx_ctx* c, const T* values, uint64_t n, const T* lo, const T* hi
     PSACX_HIP(c, hipSetDevice(c->device));
     RmqLayout Y;
     rmq_layout(n, Y);
-    Staging s(c);
+    Staging s(c, "rmq");
     T* d_values = (T*)s.upload(values, n * sizeof(T));
     T* d_lo = (T*)s.upload(lo, q * sizeof(T));
     T* d_hi = (T*)s.upload(hi, q * sizeof(T));
@@ -151,7 +130,7 @@ int lce_host(psacx_ctx* c, uint64_t n, const uint64_t* offsets, uint64_t m, cons
     PSACX_HIP(c, hipSetDevice(c->device));
     RmqLayout Y;
     rmq_layout(n, Y);
-    Staging s(c);
+    Staging s(c, "rmq");
     T* d_ISA = (T*)s.upload(ISA, n * sizeof(T));
     T* d_LCP = (T*)s.upload(LCP, n * sizeof(T));
     T* d_a = (T*)s.upload(a, q * sizeof(T));
