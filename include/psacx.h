@@ -713,6 +713,66 @@ int psacx_lce_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t 
 int psacx_lce_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* ISA, const uint64_t* LCP,
                   const uint64_t* a, const uint64_t* b, uint64_t q, uint64_t max_mismatch, uint64_t* len);
 
+/* suffix-prefix overlaps --------------------------------------------------------------
+ * The question a generalized suffix array of reads is built for: which suffixes of which strings are prefixes of which other
+ * strings -- the all-pairs suffix-prefix problem, whose answers are the edges of an overlap graph.  psacx_locate_gsa_* of a
+ * prefix returns every occurrence, not the ones that end their string.  The reference has no counterpart.  One GPU.  The text
+ * is no argument of any call here: ISA, LCP, the range-minimum index of LCP and the bitmap of the string ends answer it.
+ *
+ * Definitions.  Text, offsets o_0 .. o_m, end(p), suffix i = S[i..end(i)), the byte order and the bitmap are exactly those of
+ * "pattern search over string sets".  String j is S[o_j..o_{j+1}) with L_j bytes, X(j, d) its first d bytes.
+ *
+ *     T(j, d)   = { i : S[i..end(i)) == X(j, d) }          the suffixes that ARE X(j, d): they end their string after d bytes
+ *     olb(j, d) = #{ i : S[i..end(i)) < X(j, d) }          (= lb(X(j, d)) of locate)
+ *     oub(j, d) = olb(j, d) + |T(j, d)|
+ *
+ *  - On a correct generalized suffix array SA[olb..oub) is exactly T(j, d): an end sorts below every character, so the suffixes
+ *    equal to X(j, d) come first among those that start with it, and equal suffixes lie in text order.
+ *  - A member of T(j, d) may lie in string j itself: a border of j.  A member may be a whole string: that string is a prefix of
+ *    j.  Both are overlaps by the definition and both are reported.
+ *
+ * Depths asked.  d runs over [min_len, L_j - 1]; with PSACX_OVERLAP_WHOLE over [min_len, L_j].  The interval of d == L_j holds
+ * every string that ends with string j, string j itself (position o_j) among them.  min_len == 0 and unknown flag bits return
+ * PSACX_EINVAL.
+ *
+ * Output.  One slot per byte of the text, as in the suffix mode of match: slot p = o_j + d - 1 belongs to (j, d).
+ * lb[p], ub[p] = olb(j, d), oub(j, d) where d is asked and T(j, d) is not empty; every other slot holds 0, 0.  n entries of the
+ * index type each.  psacx_occurrences_dev_* takes the two arrays as they are, with q = n and the offsets: pos is where the
+ * overlap of length d onto string j starts, sid the string it comes from.
+ *
+ * The walk.  The overlaps of string j sit on the path from its leaf to the root of the suffix tree, which in LCP is a chain of
+ * previous-smaller-value steps from r = ISA[o_j].  With i = r and d = L_j - 1 (L_j with PSACX_OVERLAP_WHOLE), while d >= min_len:
+ *  1. if LCP[i] >= d, i becomes the largest x < i with LCP[x] <= d - 1 (none: stop).  Now i = olb(j, d).
+ *  2. T(j, d) is not empty iff the suffix SA[i] ends after d bytes: SA[i] + d <= n and that bit of the bitmap is set.
+ *  3. Then oub is the first x in (i, hi) whose bit SA[x] + d is clear, or hi; the bits are monotone there.  hi = r for d < L_j
+ *     (entry r is string j and longer than d); for d == L_j it is the first x > r with LCP[x] <= d - 1, or n.
+ *  4. d becomes LCP[i].  For the depths in between olb is still i and SA[i] is longer than they are: those slots are empty by
+ *     definition and are not searched.
+ * A few steps per string instead of one search per prefix.
+ *
+ * Totality.  Whatever SA, ISA, LCP, index, bitmap and offsets hold, nothing is read out of range: SA, ISA and LCP inside
+ * [0, n), the bitmap never beyond bit n, the index by its layout only.  Every loop ends: the depth falls strictly per step,
+ * and a step that would not lower it ends the walk.  lb <= ub <= n in every slot.  Offsets that do not start at 0, end at n
+ * and ascend strictly return PSACX_EINVAL before anything is written (the device check of psacx_string_ends_dev).  m == 0 or
+ * n == 0 returns PSACX_OK.  On arrays that are no index of one string set the values are otherwise unspecified.
+ *
+ * psacx_overlaps_dev_*: d_ends is the bitmap of psacx_string_ends_dev, d_index the index of psacx_rmq_index_dev_* over d_LCP.
+ * The call clears d_lb and d_ub itself and allocates nothing beyond the ctx slab.  No input is written.  Sixteen lanes walk
+ * one string; the end of a run is found by a 16-way partition, one probe per lane and round.
+ * psacx_overlaps_*: the host-pointer form.  It stages offsets, SA, ISA and LCP, builds the bitmap and the index, copies the 2 n
+ * entries back, and frees what it allocated on every path. */
+#define PSACX_OVERLAP_WHOLE 1u
+int psacx_overlaps_dev_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint32_t* d_ends,
+                           const uint32_t* d_SA, const uint32_t* d_ISA, const uint32_t* d_LCP, const uint32_t* d_index,
+                           uint64_t min_len, uint32_t flags, uint32_t* d_lb, uint32_t* d_ub);
+int psacx_overlaps_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint32_t* d_ends,
+                           const uint64_t* d_SA, const uint64_t* d_ISA, const uint64_t* d_LCP, const uint64_t* d_index,
+                           uint64_t min_len, uint32_t flags, uint64_t* d_lb, uint64_t* d_ub);
+int psacx_overlaps_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA, const uint32_t* ISA,
+                       const uint32_t* LCP, uint64_t min_len, uint32_t flags, uint32_t* lb, uint32_t* ub);
+int psacx_overlaps_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA, const uint64_t* ISA,
+                       const uint64_t* LCP, uint64_t min_len, uint32_t flags, uint64_t* lb, uint64_t* ub);
+
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP
  * (suffix_array.hpp:183-194, :217-228; src/psac.cpp:85-93 block-decomposes the input).  A psacx_multi stands for the

@@ -854,4 +854,40 @@ range_minima<index_t> range_min(suffix_array<char, index_t, true, LC>& sa, const
     return out;
 }
 
+// Suffix-prefix overlaps of a string set (psacx.h: "suffix-prefix overlaps"): for string j, which starts at offset o_j, and a
+// length d in [min_len, L_j - 1] (whole: up to L_j) the suffixes that are exactly the first d bytes of string j are
+// local_SA[lb[p] .. ub[p]) with p = o_j + d - 1; every other slot holds 0, 0.  Borders of string j and whole strings that are its
+// prefixes are among them.  n entries each; occurrences(sa, ss, lb, ub) lists positions and source strings.  The suffix array
+// must have been constructed from ss with its LCP.  One rank only, as lce.
+template <typename index_t>
+struct overlap_intervals {
+    std::vector<index_t> lb, ub;
+};
+
+template <typename index_t>
+overlap_intervals<index_t> overlaps(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, std::size_t min_len, bool whole = false) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, const uint32_t* isa, const uint32_t* lcp, uint64_t l,
+                       uint32_t f, uint32_t* lb, uint32_t* ub) { return psacx_overlaps_u32(c, n, o, m, s, isa, lcp, l, f, lb, ub); }
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, const uint64_t* isa, const uint64_t* lcp, uint64_t l,
+                       uint32_t f, uint64_t* lb, uint64_t* ub) { return psacx_overlaps_u64(c, n, o, m, s, isa, lcp, l, f, lb, ub); }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: overlaps needs a single-rank communicator (the queries run on one GPU)");
+    if (ss.sum_sizes != sa.n) throw std::runtime_error("overlaps: string set does not match the suffix array");
+    if (sa.local_SA.size() != sa.n || sa.local_B.size() != sa.n || sa.local_LCP.size() != sa.n)
+        throw std::runtime_error("overlaps: the suffix array holds no SA, ISA and LCP of its strings");
+    std::vector<uint64_t> soff(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) soff.push_back(soff.back() + ss.sizes[s]);
+    std::vector<W> lb(sa.n), ub(sa.n);
+    psacx::check(sa.context(), Call::run(sa.context(), sa.n, soff.data(), (uint64_t)soff.size() - 1, reinterpret_cast<const W*>(sa.local_SA.data()),
+                                         reinterpret_cast<const W*>(sa.local_B.data()), reinterpret_cast<const W*>(sa.local_LCP.data()),
+                                         (uint64_t)min_len, whole ? PSACX_OVERLAP_WHOLE : 0u, lb.data(), ub.data()));
+    overlap_intervals<index_t> out;
+    out.lb.assign(lb.begin(), lb.end());
+    out.ub.assign(ub.begin(), ub.end());
+    return out;
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

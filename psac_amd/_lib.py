@@ -16,6 +16,7 @@ PSACX_NO_FAST = 2
 PSACX_PROFILE = 4
 PSACX_MAX_ROUNDS = 72
 PSACX_MATCH_SUFFIXES = 1
+PSACX_OVERLAP_WHOLE = 1
 
 # psacx_configure options (include/psacx.h); Context.configure(force_diet=1, ...) takes them by name
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
@@ -50,6 +51,7 @@ EXPORTS = [
     "psacx_match_u32", "psacx_match_u64", "psacx_match_gsa_u32", "psacx_match_gsa_u64",
     "psacx_rmq_index_dev_u32", "psacx_rmq_index_dev_u64", "psacx_rmq_dev_u32", "psacx_rmq_dev_u64", "psacx_lce_dev_u32", "psacx_lce_dev_u64",
     "psacx_rmq_u32", "psacx_rmq_u64", "psacx_lce_u32", "psacx_lce_u64",
+    "psacx_overlaps_dev_u32", "psacx_overlaps_dev_u64", "psacx_overlaps_u32", "psacx_overlaps_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -153,6 +155,8 @@ def load():
         getattr(lib, "psacx_lce_dev_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp]
         getattr(lib, "psacx_rmq_" + suf).argtypes = [vp, vp, u64, vp, vp, u64, vp, vp]
         getattr(lib, "psacx_lce_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, u64, u64, vp]
+        getattr(lib, "psacx_overlaps_dev_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, u32, vp, vp]
+        getattr(lib, "psacx_overlaps_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, u32, vp, vp]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

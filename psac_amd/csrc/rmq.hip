@@ -1,14 +1,21 @@
-// rmq.hip -- the range-minimum index of an array resident in HBM, batched range minima with their first positions, and the
+// rmq.hip -- the range-minimum index of an array resident in HBM, batched range minima with their first positions, the
 // longest common extension of text positions from ISA and LCP (include/psacx.h: "range minimum and longest common extension";
-// kernels in rmq.hpp).
+// kernels in rmq.hpp), and the suffix-prefix overlaps of a string set from the same arrays ("suffix-prefix overlaps";
+// kernel in overlaps.hpp).
 //
 // Stands in for rmq<>::query (the reference's include/rmq.hpp:186) and, on one GPU, for what par_rmq.hpp answers across ranks.
 // The text is no argument of any call here.
 #include "engine.hpp"
 #include "rmq.hpp"
+#include "overlaps.hpp"
 #include "staging.hpp"
 
 namespace psacx {
+
+// check.hip: the offsets of a string set start at 0, end at n and ascend strictly (PSACX_EINVAL otherwise; waits); and the bitmap of
+// the string ends of valid offsets, queued on the ctx stream
+int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n);
+int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits);
 
 static const uint64_t RMQ_MAX_N = 1ull << 48;          // 64^PYR_MAX: the top level is one group
 
@@ -145,6 +152,55 @@ int lce_host(psacx_ctx* c, uint64_t n, const uint64_t* offsets, uint64_t m, cons
     return s.rc;
 }
 
+// psacx_overlaps_dev_*: the offsets are checked on the device before anything is written, the two outputs are cleared, and one
+// launch walks every string.  Nothing is allocated beyond the slab word of the offsets check.
+template <typename T>
+int overlaps_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, const uint32_t* d_ends, const T* d_SA, const T* d_ISA, const T* d_LCP,
+                 const T* d_index, uint64_t min_len, uint32_t flags, T* d_lb, T* d_ub) {
+    if (!c || min_len == 0 || (flags & ~(uint32_t)PSACX_OVERLAP_WHOLE)) return PSACX_EINVAL;
+    PSACX_TRY(rmq_check_n<T>(n));
+    if (m == 0 || n == 0) return PSACX_OK;
+    if (m > n || !d_off || !d_ends || !d_SA || !d_ISA || !d_LCP || !d_index || !d_lb || !d_ub) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    PSACX_TRY(string_offsets_valid_dev(c, d_off, m, n));
+    PSACX_HIP(c, hipMemsetAsync(d_lb, 0, n * sizeof(T), c->stream));
+    PSACX_HIP(c, hipMemsetAsync(d_ub, 0, n * sizeof(T), c->stream));
+    hipLaunchKernelGGL((overlaps_kernel<T>), dim3(grid_for(c, m * RMQ_LANES, 256, 8)), dim3(256), 0, c->stream, n, d_off, m, d_ends, d_SA, d_ISA,
+                       d_LCP, d_index, min_len, flags, d_lb, d_ub);
+    PSACX_HIP(c, hipGetLastError());
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    return PSACX_OK;
+}
+
+template <typename T>
+int overlaps_host(psacx_ctx* c, uint64_t n, const uint64_t* offsets, uint64_t m, const T* SA, const T* ISA, const T* LCP, uint64_t min_len,
+                  uint32_t flags, T* lb, T* ub) {
+    if (!c || min_len == 0 || (flags & ~(uint32_t)PSACX_OVERLAP_WHOLE)) return PSACX_EINVAL;
+    PSACX_TRY(rmq_check_n<T>(n));
+    if (m == 0 || n == 0) return PSACX_OK;
+    if (m > n || !offsets || !SA || !ISA || !LCP || !lb || !ub) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    RmqLayout Y;
+    rmq_layout(n, Y);
+    Staging s(c, "overlaps");
+    T* d_SA = (T*)s.upload(SA, n * sizeof(T));
+    T* d_ISA = (T*)s.upload(ISA, n * sizeof(T));
+    T* d_LCP = (T*)s.upload(LCP, n * sizeof(T));
+    uint64_t* d_off = (uint64_t*)s.upload(offsets, (m + 1) * sizeof(uint64_t));
+    uint32_t* d_ends = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
+    T* d_index = (T*)s.alloc(Y.entries * sizeof(T));
+    T* d_lb = (T*)s.alloc(n * sizeof(T));
+    T* d_ub = (T*)s.alloc(n * sizeof(T));
+    if (s.rc == PSACX_OK) s.rc = string_offsets_valid_dev(c, d_off, m, n);
+    if (s.rc == PSACX_OK) s.rc = string_ends_bitmap_dev(c, d_off, m, n, d_ends);
+    if (s.rc == PSACX_OK) s.rc = rmq_index_fill<T>(c, d_LCP, n, d_index);
+    if (s.rc == PSACX_OK) s.rc = overlaps_dev<T>(c, n, d_off, m, d_ends, d_SA, d_ISA, d_LCP, d_index, min_len, flags, d_lb, d_ub);
+    s.download(lb, d_lb, n * sizeof(T));
+    s.download(ub, d_ub, n * sizeof(T));
+    s.step(hipStreamSynchronize(c->stream));
+    return s.rc;
+}
+
 } // namespace psacx
 
 using namespace psacx;
@@ -170,5 +226,18 @@ extern "C" {
 PSACX_RMQ_ABI(u32, uint32_t)
 PSACX_RMQ_ABI(u64, uint64_t)
 #undef PSACX_RMQ_ABI
+
+#define PSACX_OVERLAPS_ABI(S, T)                                                                                                              \
+    int psacx_overlaps_dev_##S(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* ends, const T* sa, const T* isa,      \
+                               const T* lcp, const T* index, uint64_t min_len, uint32_t flags, T* lb, T* ub) {                                  \
+        return overlaps_dev<T>(c, n, off, m, ends, sa, isa, lcp, index, min_len, flags, lb, ub);                                                \
+    }                                                                                                                                           \
+    int psacx_overlaps_##S(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const T* sa, const T* isa, const T* lcp,                  \
+                           uint64_t min_len, uint32_t flags, T* lb, T* ub) {                                                                    \
+        return overlaps_host<T>(c, n, off, m, sa, isa, lcp, min_len, flags, lb, ub);                                                            \
+    }
+PSACX_OVERLAPS_ABI(u32, uint32_t)
+PSACX_OVERLAPS_ABI(u64, uint64_t)
+#undef PSACX_OVERLAPS_ABI
 
 } // extern "C"

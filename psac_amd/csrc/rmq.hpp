@@ -162,6 +162,57 @@ __device__ __forceinline__ uint64_t rmq_first(const T* __restrict__ values, cons
     return (j >= l && j < r) ? j : n;
 }
 
+// The left mirror of the two above.  Positions travel as p + 1 so that 0 is "none" and the group's answer is a maximum.
+__device__ __forceinline__ uint64_t rmq_group_reduce_last(uint64_t v) {
+#pragma unroll
+    for (int m = RMQ_LANES / 2; m >= 1; m >>= 1) { const uint64_t o = shfl_xor<uint64_t>(v, m); v = o > v ? o : v; }
+    return v;
+}
+
+// last position p of group g of a[0..len) with p < to and a[p] <= v, over the 16 lanes; ~0 if none
+template <typename T>
+__device__ __forceinline__ uint64_t rmq_last_le(const T* __restrict__ a, uint64_t len, uint64_t g, unsigned sub, uint64_t to, T v) {
+    T x[RMQ_PER];
+    rmq_load_part<T>(a, len, g, sub, x);
+    if (to > len) to = len;
+    const uint64_t e0 = (g << 6) + (uint64_t)sub * RMQ_PER;
+    uint64_t p1 = 0;
+#pragma unroll
+    for (int d = 0; d < RMQ_PER; ++d) if (e0 + d < to && x[d] <= v) p1 = e0 + d + 1;
+    return rmq_group_reduce_last(p1) - 1;                          // (0 - 1 = ~0: none)
+}
+
+// The largest position below i (0 <= i <= n) that holds a value <= v, or n if there is none: the previous value <= v, which in
+// LCP is the step from a node of the suffix tree to the ancestor of depth <= v.  The walk of rmq_first turned round: up while
+// the part of the group in front of p holds nothing, then down into the last child that qualifies.  At most 2 nlev - 1
+// dependent group loads, one or two where the answer is near; none of the addresses comes from memory.
+template <typename T>
+__device__ __forceinline__ uint64_t rmq_last(const T* __restrict__ values, const T* __restrict__ index, const RmqLayout& Y, unsigned sub,
+                                             uint64_t i, T v, uint64_t n) {
+    if (i == 0 || i > n) return n;
+    uint64_t p = i - 1, j = ~0ull;                      // p: the last candidate on level 0, the entry that holds it above
+    int found = -1;
+    bool open = true;
+#pragma unroll
+    for (int L = 0; L < PYR_MAX; ++L) {
+        if (!open || L >= Y.nlev) continue;
+        const T* a = L ? index + Y.lvl[L] : values;
+        // level 0 looks at the group of p up to p itself; above, at the entries in front of p's own (their blocks lie wholly below i)
+        j = rmq_last_le<T>(a, Y.len[L], p >> 6, sub, L ? p : p + 1, v);
+        if (j != ~0ull) { found = L; open = false; }
+        else if ((p >> 6) == 0) open = false;           // nothing in front of this group on this level
+        p >>= 6;
+    }
+    if (found < 0) return n;
+#pragma unroll
+    for (int L = PYR_MAX - 1; L > 0; --L) {
+        if (L > found || j == ~0ull) continue;          // (j == ~0: the parent qualified, no child does -- no index of these values)
+        const T* a = (L - 1) ? index + Y.lvl[L - 1] : values;
+        j = rmq_last_le<T>(a, Y.len[L - 1], j, sub, ~0ull, v);
+    }
+    return j < i ? j : n;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void rmq_kernel(const T* __restrict__ values, uint64_t n, const T* __restrict__ index,
                                                   const T* __restrict__ lo, const T* __restrict__ hi, uint64_t q,

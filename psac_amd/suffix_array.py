@@ -7,6 +7,7 @@ import numpy as np
 from . import _lib
 from ._lib import PSACX_LCP, PSACX_NO_FAST, PSACX_PROFILE, PsacxError, Stats
 from ._lib import PSACX_MATCH_SUFFIXES as MATCH_SUFFIXES
+from ._lib import PSACX_OVERLAP_WHOLE as OVERLAP_WHOLE
 
 NEAREST_SM, NEAREST_EQ, FURTHEST_EQ = 0, 1, 2      # ansv_common.hpp:20-22
 
@@ -224,6 +225,12 @@ class SuffixArray(object):
                           _ptr(self.local_SA), _ptr(self.local_B), _ptr(self.local_LCP) if self.lcp else None))
         self.string_offsets = off
         return self._after()
+
+    def overlaps(self, min_len, whole=False):
+        """The suffix-prefix overlaps of the string set of the last construct_ss (which needs lcp=True): overlaps() over its arrays."""
+        if getattr(self, "string_offsets", None) is None or not self.lcp or self.local_LCP.size != self.n:
+            raise ValueError("overlaps needs construct_ss with lcp=True first")
+        return overlaps(self.n, self.string_offsets, self.local_SA, self.local_B, self.local_LCP, min_len, whole, ctx=self.ctx)
 
     def construct_device(self, d_text, n, d_sa, d_isa, d_lcp=None, fast_resolval=True, k=0, profile=False, d_lc=None):
         """Same with every buffer already resident in HBM (raw device addresses)."""
@@ -589,6 +596,38 @@ def lce(ISA, LCP, a, b, max_mismatch=0, offsets=None, ctx=None):
     ctx.check(fn(ctx.handle, isa.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(isa), _ptr(lcp), _ptr(pa),
                  _ptr(pb), pa.size, int(max_mismatch), _ptr(out)))
     return out
+
+
+def overlaps_device(ctx, n, d_off, m, d_ends, d_sa, d_isa, d_lcp, d_index, min_len, flags, d_lb, d_ub, index_bits):
+    """psacx_overlaps_dev_*: the suffix-prefix overlaps of a string set resident in HBM (include/psacx.h: "suffix-prefix overlaps").
+    d_ends is the bitmap of string_ends_device, d_index the index of rmq_index_device over d_lcp; flags is 0 or OVERLAP_WHOLE.
+    d_lb / d_ub receive n entries of the index type each: slot o_j + d - 1 holds the interval of the suffixes that are the first d
+    bytes of string j, or 0, 0.  occurrences_device takes the two as they are, with q = n."""
+    fn = getattr(ctx._lib, "psacx_overlaps_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(fn(ctx.handle, int(n), opt(d_off), int(m), opt(d_ends), opt(d_sa), opt(d_isa), opt(d_lcp), opt(d_index), int(min_len), int(flags),
+                 opt(d_lb), opt(d_ub)))
+
+
+def overlaps(text_len_or_text, offsets, SA, ISA, LCP, min_len, whole=False, ctx=None):
+    """psacx_overlaps_*: (lb, ub) arrays of n entries -- for string j and a length d in [min_len, L_j - 1] (whole=True: up to L_j)
+    the suffixes that are exactly the first d bytes of string j are SA[lb[p]:ub[p]] with p = offsets[j] + d - 1; every other slot
+    holds 0, 0.  Borders of string j and whole strings that are its prefixes are among them.  From the arrays of a string set
+    (construct_ss with lcp) alone: the first argument only gives n, as a number or as anything with a length.  Host arrays;
+    everything is staged for the call.  occurrences(SA, lb, ub, offsets=offsets) lists positions and source strings."""
+    n = int(text_len_or_text) if isinstance(text_len_or_text, (int, np.integer)) else len(text_len_or_text)
+    sa, isa, lcp = np.ascontiguousarray(SA), np.ascontiguousarray(ISA), np.ascontiguousarray(LCP)
+    if sa.dtype not in (np.uint32, np.uint64) or isa.dtype != sa.dtype or lcp.dtype != sa.dtype:
+        raise TypeError("overlaps needs SA, ISA and LCP all uint32 or all uint64")
+    if sa.size != n or isa.size != n or lcp.size != n:
+        raise ValueError("SA, ISA and LCP must have n entries each")
+    so = np.ascontiguousarray(offsets, dtype=np.uint64)
+    lb, ub = np.zeros(n, sa.dtype), np.zeros(n, sa.dtype)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_overlaps_u%d" % (sa.dtype.itemsize * 8))
+    ctx.check(fn(ctx.handle, n, _ptr(so), max(0, so.size - 1), _ptr(sa), _ptr(isa), _ptr(lcp), int(min_len), OVERLAP_WHOLE if whole else 0,
+                 _ptr(lb), _ptr(ub)))
+    return lb, ub
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
