@@ -94,6 +94,9 @@ typedef struct psacx_stats {
     uint64_t locate_fetches[2];
     uint64_t rebucket_1w;          /* 1 when the first round of the last construction ran rebucket_first_1w_kernel, the 32-bit form of the rebucket kernel on
                                       one-word records, 0 when it ran the generic rebucket_first_kernel */
+    uint64_t group_sort;           /* the one-word prefix sort of the last construction: 0 = LSD passes on every digit inside the 256 buckets, 1 = upper digits most
+                                      significant first and the groups of the last 16 prefix bits sorted on chip, 2 = that form entered, a group longer
+                                      than its cap found, the remaining digits sorted LSD inside the partition reached */
 } psacx_stats;
 
 /* life cycle ------------------------------------------------------------- */
@@ -140,13 +143,17 @@ int psacx_trim(psacx_ctx* ctx);
  *   LOCATE_COUNT      psacx_locate_*: the kernel counts its fetches into psacx_stats.locate_fetches (slower; tools/locate_time.py)
  *   GENERIC_REBUCKET  the first round on one-word records runs the generic rebucket kernel, not its 32-bit form (A/B runs)
  *   PLAIN_SIDE_KERNELS the tile histograms of the top digit and the tie scan of the one-word first round run their one-tile-per-workgroup
- *                     kernels (top_digit_hist_kernel, tie_resolve_1w_kernel), not the persistent ones (parity tests, A/B runs)          */
+ *                     kernels (top_digit_hist_kernel, tie_resolve_1w_kernel), not the persistent ones (parity tests, A/B runs)
+ *   LSD_BUCKET_PASSES the one-word prefix sort of the first round sorts every digit below the top one by LSD passes inside the 256 buckets, not the
+ *                     upper digits most significant first and the last 16 bits on chip (psacx_stats.group_sort; parity tests, A/B runs)
+ *   FIRST_LEAD        test option: leading bits the two-stage first round sorts on; honoured when a multiple of 8, at least bits(n - 1) + 3, at most 40
+ *                     and at most the bits of the first key word, ignored otherwise (40 reaches the sub-bucket passes on small texts)          */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
-    PSACX_OPT_PLAIN_SIDE_KERNELS,
+    PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);

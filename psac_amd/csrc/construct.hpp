@@ -119,6 +119,9 @@ size_t carve(Arena& a, Work<T>& w, uint64_t n, bool with_lcp, T* d_lcp, bool die
     w.sc.d_hist = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
     w.sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
     w.sc.desc_bytes = sort_desc_bytes(n);
+    // (PSACX_OPT_FIRST_LEAD: a small text sorted on 40 leading bits needs the sub-bucket tables of a large one -- engine.hpp: onew_group_layout)
+    if (sizeof(T) == 8 && kn.first_lead == 32 + RADIX_BITS && n < (1ull << 30))
+        w.sc.desc_bytes += (size_t)(n / SORT_TILE_MIN + ONEW_SUB) * RADIX * sizeof(unsigned) + (size_t)ONEW_SUB * RADIX * 8 + (8u << 20);
     w.sc.d_desc = a.take<char>(w.sc.desc_bytes);
     w.sc.d_err = a.take<unsigned>(64);
     w.sc.d_summary = a.take<unsigned long long>(8);
@@ -663,6 +666,9 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
     // fewer than a quarter of the suffixes tied, which is cheaper than carrying word 2 through five passes
     const unsigned slack = 2;
     if (lead > bits_w1 && bits_for(n - 1) + slack <= bits_w1 && bits_w1 % RADIX_BITS == 0) lead = bits_w1;
+    // PSACX_OPT_FIRST_LEAD (tests): more leading bits than the text needs, e.g. the 40 of a text of 2^32 characters
+    if (kn.first_lead && kn.first_lead % RADIX_BITS == 0 && kn.first_lead >= bits_for(n - 1) + 3 && kn.first_lead <= 32 + RADIX_BITS && kn.first_lead <= bits_w1)
+        lead = kn.first_lead;
     bool two_stage = !gsa && n >= (1ull << 21) && !kn.one_stage && lead <= bits_w1 &&
                      lead + RADIX_BITS <= bits_w1 + bits_w2;     // at least one pass less
     psacx_round* r0 = &st.rounds[0];

@@ -66,6 +66,10 @@ struct Knobs {
                                   // (sa_kernels.hpp; parity suite and A/B runs)
     bool plain_side_kernels = false; // PSACX_OPT_PLAIN_SIDE_KERNELS: top_digit_hist_kernel and tie_resolve_1w_kernel (a workgroup per tile), not the persistent
                                   // top_digit_hist_waves_kernel and tie_resolve_1w_waves_kernel (sa_kernels.hpp; parity tests and A/B runs)
+    bool lsd_bucket_passes = false; // PSACX_OPT_LSD_BUCKET_PASSES: the one-word prefix sort runs LSD passes on all digits inside the 256 buckets, not the group form
+                                  // (onew_bucket_passes: upper digits most significant first, the last 16 bits on chip; parity tests and A/B runs)
+    unsigned first_lead = 0;      // PSACX_OPT_FIRST_LEAD: leading bits the two-stage first round sorts on (tests: 40 reaches the sub-bucket form of the group
+                                  // form at sizes a test can afford); honoured when a multiple of 8, >= bits_for(n - 1) + 3, <= 40 and <= the bits of word 1
     int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (search.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
 };
@@ -1026,7 +1030,8 @@ constexpr int PSACX_RETRY_1STAGE = 1002;
 #endif
 // Scratch layout of the bucket passes over one-word records.  h_tabs: bucket_off[0 .. 256] filled in (start of every bucket's records;
 // buckets without records own nothing), slab_start[0 .. 256] behind it is written here.
-struct OneWordLayout { unsigned slab; uint64_t total_slabs, vtiles; size_t hist_bytes, slab_bytes, tabs_bytes, need; };
+// group: the group form of onew_bucket_passes may run (onew_group_layout); sub_tiles: rows of the tile tables its sub-bucket passes need (0: none)
+struct OneWordLayout { unsigned slab; uint64_t total_slabs, vtiles; size_t hist_bytes, slab_bytes, tabs_bytes, need; bool group = false; uint64_t sub_tiles = 0; };
 template <int TILE>
 inline OneWordLayout onew_layout(unsigned long long* h_tabs, uint64_t ntiles_hint) {
     OneWordLayout lay;
@@ -1046,6 +1051,38 @@ inline OneWordLayout onew_layout(unsigned long long* h_tabs, uint64_t ntiles_hin
     lay.need = 256 + lay.hist_bytes + lay.slab_bytes + (size_t)RADIX * RADIX * 8 + lay.tabs_bytes;
     return lay;
 }
+// The group form of the bucket passes (onew_bucket_passes): the upper digits of the rest most significant digit first, the last 16 prefix bits
+// ordered on chip inside the groups that agree in everything above them (radix.hpp: group_sort16_kernel).  It runs for 24 or 32 prefix bits in
+// the word when a group is expected to hold at most half of GROUP_CAP records (texts of 2^22 .. 2^24 and of 2^30 .. 2^32 characters), and when the
+// scratch has room for its tables behind those of the 256-bucket form: a word for the largest group, and at 32 bits the tables of the 65 536
+// sub-buckets (radix.hpp: OneWordTabs) -- their starts, first tiles, the sub-bucket of every tile, a row of zeros, the 2^24 group starts -- and
+// tile histograms of n / tile + 65 536 rows.  Returns `lay` with the form switched on, or `lay` as it is.
+constexpr unsigned ONEW_SUB = RADIX * RADIX;
+struct OneWordGroupScratch { size_t max_word, zero_row, sub_off, first_tile, tile_sub, group_base, end; };
+inline OneWordGroupScratch onew_group_scratch(const OneWordLayout& lay) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    OneWordGroupScratch g;
+    g.max_word = 256 + lay.hist_bytes + lay.slab_bytes + (size_t)RADIX * RADIX * 8 + lay.tabs_bytes;
+    g.zero_row = g.max_word + 256;
+    g.sub_off = g.zero_row + (size_t)RADIX * 8;
+    g.first_tile = lay.sub_tiles ? g.sub_off + up((size_t)(ONEW_SUB + 1) * 8) : g.sub_off;
+    g.tile_sub = lay.sub_tiles ? g.first_tile + up((size_t)(ONEW_SUB + 1) * 4) : g.sub_off;
+    g.group_base = lay.sub_tiles ? g.tile_sub + up((size_t)lay.sub_tiles * 4) : g.sub_off;
+    g.end = lay.sub_tiles ? g.group_base + (size_t)ONEW_SUB * RADIX * 8 : g.sub_off;
+    return g;
+}
+template <int TILE>
+inline OneWordLayout onew_group_layout(OneWordLayout lay, uint64_t nrec, unsigned low, size_t scratch_bytes) {
+    if ((low != 24 && low != 32) || (nrec >> (low - 16 + 8)) > (uint64_t)GROUP_CAP / 2) return lay;
+    OneWordLayout g = lay;
+    g.group = true;
+    if (low == 32) {
+        g.sub_tiles = nrec / TILE + ONEW_SUB;            // (every sub-bucket owns ceil(size / tile) tiles)
+        g.hist_bytes = std::max(lay.hist_bytes, ((size_t)g.sub_tiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255);
+    }
+    g.need = onew_group_scratch(g).end;
+    return (g.need > scratch_bytes || g.sub_tiles >= (1ull << 31)) ? lay : g;
+}
 // The LSD passes inside the buckets: one-word records (rest of the prefix << sfield | suffix) of bucket b at [bucket_off[b], bucket_off[b + 1]) of `cur`,
 // `low` prefix bits in the word.  All but the last pass ping-pong between cur and oth; the last one writes word 1 ((b << low | rest) << lo1) into the
 // array it does not read (*s1 tells which) and the suffixes as words into sa_out.  h_tabs must stay untouched until the stream has passed the copy.
@@ -1055,10 +1092,11 @@ inline OneWordLayout onew_layout(unsigned long long* h_tabs, uint64_t ntiles_hin
 // -- written by the pass on the top digit and by every bucket pass but the last; the tile histograms then read it instead of the records.
 inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long long* h_tabs, const OneWordLayout& lay, uint64_t* cur, uint64_t* oth, uint64_t* sa_out,
                               unsigned sfield, unsigned low, unsigned lo1, uint64_t nrec, uint64_t** s1, OneWordView* view_out = nullptr, uint8_t* dig = nullptr,
-                              uint64_t in_pad = 0, uint8_t* tie_bytes = nullptr) {
+                              uint64_t in_pad = 0, uint8_t* tie_bytes = nullptr, unsigned long long* h_word = nullptr) {
     // tie_bytes (with view_out): the last pass leaves the LOWEST byte of the prefix bits of the record at every place there: two neighbours that
     // tie on the prefix agree in it, two that do not agree in it once in 256 -- the tie stage reads these bytes instead of the records
     // in_pad: in the input of the FIRST pass the records of bucket b lie b * in_pad places further than bucket_off says (prefix_sort_1w)
+    // h_word (pinned, with lay.group, view_out, dig and tie_bytes): the group form runs (onew_group_layout) and reads the largest group back here
     constexpr int BLOCK = 512, ITEMS_B = PSACX_1W_ITEMS, TILE = BLOCK * ITEMS_B;
     unsigned* tile_hist = reinterpret_cast<unsigned*>(scratch + 256);
     unsigned long long* slab_tot = reinterpret_cast<unsigned long long*>(scratch + 256 + lay.hist_bytes);
@@ -1077,37 +1115,113 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
                        (unsigned)total_slabs, (unsigned)(lay.slab * TILE), slab_info);
     PSACX_HIP(c, hipGetLastError());
     const int npass = (int)((low + RADIX_BITS - 1) / RADIX_BITS);
-    for (int j = 0; j < npass; ++j) {
-        const bool last = j + 1 == npass;
-        const int shift = (int)sfield + j * RADIX_BITS;
-        {
-            ProfScope ps(c, TC_SORT_TILEHIST);
-            if (dig && j > 0) hipLaunchKernelGGL((radix_tile_hist_bytes_kernel<BLOCK, ITEMS_B>), dim3((unsigned)((vtiles + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0, c->stream,
-                                                 (const uint8_t*)dig, tb, (unsigned)vtiles, tile_hist);
-            else
-            hipLaunchKernelGGL((radix_tile_hist1w_kernel<BLOCK, ITEMS_B>), dim3((unsigned)vtiles), dim3(BLOCK), 0, c->stream, (const uint64_t*)cur, tb, shift, tile_hist,
-                               j == 0 ? in_pad : (uint64_t)0);
-            hipLaunchKernelGGL(radix_slab_scan1w_kernel<0>, dim3((unsigned)total_slabs), dim3(RADIX), 0, c->stream, tile_hist, tb, (unsigned)TILE, slab_tot);
-            hipLaunchKernelGGL(radix_top_scan1w_kernel<0>, dim3(RADIX), dim3(RADIX), 0, c->stream, slab_tot, tb, base2);
-            PSACX_HIP(c, hipGetLastError());
-        }
-        ProfScope ps(c, TC_SORT_SCATTER2);
-        PSACX_HIP(c, hipMemsetAsync(scratch, 0, 256, c->stream));
-        if (!last || view_out)
-            hipLaunchKernelGGL((radix_scatter1w_kernel<BLOCK, ITEMS_B, 8>), dim3((unsigned)vtiles), dim3(BLOCK), 0, c->stream, (const uint64_t*)cur, oth, (uint64_t*)nullptr, shift,
-                               tb, base2, tile_hist, slab_tot, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(nrec, true), 0u,
-                               last ? tie_bytes : dig, last ? (int)sfield : shift + RADIX_BITS, j == 0 ? in_pad : (uint64_t)0);
+    bool first = true;            // the next pass is the first: it reads the padded layout
+    // tile histograms of the digit at `shift` and their scans inside the buckets of `t` (the 256 buckets, or the sub-buckets); dbase: start of every digit of every bucket
+    auto tables = [&](const OneWordTabs& t, int shift, bool from_bytes, unsigned long long* dbase) {
+        ProfScope ps(c, TC_SORT_TILEHIST);
+        const uint64_t nt = t.tile_sub ? lay.sub_tiles : vtiles;
+        if (from_bytes) hipLaunchKernelGGL((radix_tile_hist_bytes_kernel<BLOCK, ITEMS_B>), dim3((unsigned)((nt + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0, c->stream,
+                                           (const uint8_t*)dig, t, (unsigned)nt, tile_hist);
+        else
+        hipLaunchKernelGGL((radix_tile_hist1w_kernel<BLOCK, ITEMS_B>), dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, (const uint64_t*)cur, t, shift, tile_hist,
+                           first ? in_pad : (uint64_t)0);
+        if (t.tile_sub) hipLaunchKernelGGL(radix_sub_scan1w_kernel<0>, dim3(ONEW_SUB), dim3(RADIX), 0, c->stream, tile_hist, t, dbase);
         else {
-            // the last pass reads `cur` and writes word 1 into the other array and the suffixes into sa_out
-            hipLaunchKernelGGL((radix_scatter1w_kernel<BLOCK, ITEMS_B, 9>), dim3((unsigned)vtiles), dim3(BLOCK), 0, c->stream, (const uint64_t*)cur, oth, sa_out, shift,
-                               tb, base2, tile_hist, slab_tot, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(nrec, true), lo1 | (low << 8) | (sfield << 16),
-                               (uint8_t*)nullptr, 0, j == 0 ? in_pad : (uint64_t)0);
+            hipLaunchKernelGGL(radix_slab_scan1w_kernel<0>, dim3((unsigned)total_slabs), dim3(RADIX), 0, c->stream, tile_hist, t, (unsigned)TILE, slab_tot);
+            hipLaunchKernelGGL(radix_top_scan1w_kernel<0>, dim3(RADIX), dim3(RADIX), 0, c->stream, slab_tot, t, dbase);
         }
+    };
+    // the scatter of that pass: cur -> oth, swapped afterwards; widen: word 1 into oth and the suffixes as words into sa_out; dnext: see radix_scatter_tile
+    auto scatter = [&](const OneWordTabs& t, int shift, bool widen, const unsigned long long* dbase, uint8_t* dnext, int dnext_shift) -> int {
+        ProfScope ps(c, TC_SORT_SCATTER2);
+        const uint64_t nt = t.tile_sub ? lay.sub_tiles : vtiles;
+        PSACX_HIP(c, hipMemsetAsync(scratch, 0, 256, c->stream));
+        if (!widen)
+            hipLaunchKernelGGL((radix_scatter1w_kernel<BLOCK, ITEMS_B, 8>), dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, (const uint64_t*)cur, oth, (uint64_t*)nullptr, shift,
+                               t, dbase, tile_hist, slab_tot, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(nrec, true), 0u,
+                               dnext, dnext_shift, first ? in_pad : (uint64_t)0);
+        else
+            hipLaunchKernelGGL((radix_scatter1w_kernel<BLOCK, ITEMS_B, 9>), dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, (const uint64_t*)cur, oth, sa_out, shift,
+                               t, dbase, tile_hist, slab_tot, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(nrec, true), lo1 | (low << 8) | (sfield << 16),
+                               (uint8_t*)nullptr, 0, first ? in_pad : (uint64_t)0);
         PSACX_HIP(c, hipGetLastError());
-        c->stats.scatter_launches[2] += 1; c->stats.scatter_records[2] += nrec; c->stats.scatter_bytes[2] += ((last && !view_out ? 24ull : 16ull) + (((dig && !last) || (last && view_out && tie_bytes)) ? 1ull : 0ull)) * nrec;      // (+ the digit byte for the next pass's histograms)
+        c->stats.scatter_launches[2] += 1; c->stats.scatter_records[2] += nrec; c->stats.scatter_bytes[2] += ((widen ? 24ull : 16ull) + (dnext ? 1ull : 0ull)) * nrec;      // (+ the digit byte for the next pass's histograms)
         c->stats.onew_passes += 1;
         std::swap(cur, oth);
+        first = false;
+        return PSACX_OK;
+    };
+    // LSD passes on the nd lowest digits inside the buckets of `t`.  All but the last write the digit byte of the next; the last one writes the tie bytes,
+    // or (without view_out) reads `cur` and writes word 1 into the other array and the suffixes into sa_out
+    auto lsd = [&](const OneWordTabs& t, int nd, unsigned long long* dbase) -> int {
+        for (int j = 0; j < nd; ++j) {
+            const bool last = j + 1 == nd, widen = last && !view_out;
+            const int shift = (int)sfield + j * RADIX_BITS;
+            tables(t, shift, dig && j > 0, dbase);
+            PSACX_HIP(c, hipGetLastError());
+            PSACX_TRY(scatter(t, shift, widen, dbase, widen ? (uint8_t*)nullptr : last ? tie_bytes : dig, last ? (int)sfield : shift + RADIX_BITS));
+        }
+        return PSACX_OK;
+    };
+    if (!(lay.group && view_out && dig && tie_bytes && h_word)) {
+        PSACX_TRY(lsd(tb, npass, base2));
+        *s1 = cur;
+        return PSACX_OK;
     }
+    // Group form: the digits above the last 16 bits most significant first -- at 32 bits the pass on the top one of them inside the 256 buckets, whose
+    // digit starts are the starts of the 65 536 sub-buckets, then the tables of the sub-buckets from them -- the pass on the digit above the last 16 bits
+    // inside these, and the groups it leaves ordered on chip.  The largest group is known from the tables of that pass, before its scatter runs: with one
+    // longer than GROUP_CAP the digits left are sorted LSD inside the partition there is (at 24 bits: the passes above, as if nothing had happened).
+    const OneWordGroupScratch gs = onew_group_scratch(lay);
+    unsigned long long* const max_word = reinterpret_cast<unsigned long long*>(scratch + gs.max_word);
+    const int mid_shift = (int)sfield + 2 * RADIX_BITS;
+    OneWordTabs tg = tb;
+    unsigned long long* gbase = base2;
+    uint64_t ngroups = (uint64_t)RADIX * RADIX;
+    if (low == 32) {
+        unsigned long long* const sub_off = reinterpret_cast<unsigned long long*>(scratch + gs.sub_off);
+        unsigned long long* const zero_row = reinterpret_cast<unsigned long long*>(scratch + gs.zero_row);
+        unsigned* const first_tile = reinterpret_cast<unsigned*>(scratch + gs.first_tile);
+        unsigned* const tile_sub = reinterpret_cast<unsigned*>(scratch + gs.tile_sub);
+        tables(tb, mid_shift + RADIX_BITS, false, sub_off);
+        PSACX_HIP(c, hipGetLastError());
+        PSACX_TRY(scatter(tb, mid_shift + RADIX_BITS, false, sub_off, dig, mid_shift));
+        {
+            ProfScope ps(c, TC_SORT_TILEHIST);
+            PSACX_HIP(c, hipMemcpyAsync(sub_off + ONEW_SUB, h_tabs + RADIX, sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));     // (= nrec)
+            PSACX_HIP(c, hipMemsetAsync(zero_row, 0, (size_t)RADIX * 8, c->stream));
+            PSACX_HIP(c, hipMemsetAsync(tile_sub, 0xFF, (size_t)lay.sub_tiles * 4, c->stream));
+            hipLaunchKernelGGL(onew_sub_first_tile_kernel<1024>, dim3(1), dim3(1024), 0, c->stream, sub_off, ONEW_SUB, (unsigned)TILE, first_tile);
+            hipLaunchKernelGGL(onew_sub_tile_fill_kernel<256>, dim3(ONEW_SUB / (256 / WAVE)), dim3(256), 0, c->stream, first_tile, ONEW_SUB, (unsigned)lay.sub_tiles, tile_sub);
+            PSACX_HIP(c, hipGetLastError());
+        }
+        tg.bucket_off = sub_off; tg.tile_sub = tile_sub; tg.first_tile = first_tile; tg.zero_row = zero_row;
+        gbase = reinterpret_cast<unsigned long long*>(scratch + gs.group_base);
+        ngroups = (uint64_t)ONEW_SUB * RADIX;
+        tables(tg, mid_shift, true, gbase);
+    } else
+        tables(tb, mid_shift, false, gbase);
+    PSACX_HIP(c, hipMemsetAsync(max_word, 0, 16, c->stream));
+    hipLaunchKernelGGL(onew_max_group_kernel<256>, dim3((unsigned)grid_for(c, ngroups, 256, 8)), dim3(256), 0, c->stream, gbase, ngroups, nrec, max_word);
+    PSACX_HIP(c, hipGetLastError());
+    PSACX_HIP(c, hipMemcpyAsync(h_word, max_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (*h_word > (unsigned long long)GROUP_CAP) {
+        c->stats.group_sort = 2;
+        PSACX_TRY(lsd(tg, 3, gbase));
+        *s1 = cur;
+        return PSACX_OK;
+    }
+    PSACX_TRY(scatter(tg, mid_shift, false, gbase, (uint8_t*)nullptr, 0));
+    {
+        ProfScope ps(c, TC_SORT_SCATTER2);
+        // (persistent waves, five workgroups of 256 per CU -- 82 VGPRs: five waves per SIMD; 20 KB of LDS each)
+        hipLaunchKernelGGL(group_sort16_kernel<256>, dim3((unsigned)grid_for(c, ngroups, 256, 5)), dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
+        PSACX_HIP(c, hipGetLastError());
+        c->stats.scatter_launches[2] += 1; c->stats.scatter_records[2] += nrec; c->stats.scatter_bytes[2] += 17ull * nrec;      // (record read and written, tie byte)
+        c->stats.onew_passes += 1;
+    }
+    c->stats.group_sort = 1;
     *s1 = cur;
     return PSACX_OK;
 }
@@ -1171,8 +1285,11 @@ inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t*
     unsigned long long* h_tabs = sc.h_base + RADIX;             // pinned: bucket_off[257], slab_start[257]
     for (int d = 0; d < RADIX; ++d) h_tabs[d] = sc.h_base[d];
     h_tabs[RADIX] = n;
-    const OneWordLayout lay = onew_layout<TILE>(h_tabs, ntiles);
+    OneWordLayout lay = onew_layout<TILE>(h_tabs, ntiles);
     if (lay.need > sc.desc_bytes || lay.vtiles >= (1ull << 31)) return PSACX_RETRY_1W;
+    // (the group form where its tables fit too; PSACX_OPT_LSD_BUCKET_PASSES pins the LSD passes)
+    if (view_out && dig && tie_bytes && !c->knobs.lsd_bucket_passes) lay = onew_group_layout<TILE>(lay, n, low, sc.desc_bytes);
+    unsigned long long* const h_word = sc.h_base + 4 * RADIX;          // (pinned, behind h_tabs)
     {
         ProfScope ps(c, TC_KMER);           // (key generation and the partition by the top digit in one kernel: timed with the keys)
         PSACX_HIP(c, hipMemsetAsync(scratch, 0, 256, c->stream));
@@ -1183,8 +1300,8 @@ inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t*
     }
     // the buckets (the tables of the first pass in the scratch are dead once its scatter has run: same stream)
     uint64_t* cur = nullptr;
-    if (pad) PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, k0, a, sa_out, sfield, low, lo1, n, &cur, view_out, dig, pad, tie_bytes));
-    else PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, a, k0, sa_out, sfield, low, lo1, n, &cur, view_out, dig, 0, tie_bytes));
+    if (pad) PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, k0, a, sa_out, sfield, low, lo1, n, &cur, view_out, dig, pad, tie_bytes, h_word));
+    else PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, a, k0, sa_out, sfield, low, lo1, n, &cur, view_out, dig, 0, tie_bytes, h_word));
     *s1 = cur;          // (without pad: k0 after an odd number of bucket passes, `a` after an even number; with pad the other way round)
     if (rs) { rs->sort_passes = (uint32_t)((low + RADIX_BITS - 1) / RADIX_BITS + 1); rs->sort_passes_skipped = 0; }
     return PSACX_OK;

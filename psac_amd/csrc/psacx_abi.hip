@@ -132,6 +132,8 @@ int psacx_configure(psacx_ctx* c, int option, uint64_t value) {
     case PSACX_OPT_LOCATE_COUNT: k.locate_count = value != 0; return PSACX_OK;
     case PSACX_OPT_GENERIC_REBUCKET: k.generic_rebucket = value != 0; return PSACX_OK;
     case PSACX_OPT_PLAIN_SIDE_KERNELS: k.plain_side_kernels = value != 0; return PSACX_OK;
+    case PSACX_OPT_LSD_BUCKET_PASSES: k.lsd_bucket_passes = value != 0; return PSACX_OK;
+    case PSACX_OPT_FIRST_LEAD: if (value > 64) return PSACX_EINVAL; k.first_lead = (unsigned)value; return PSACX_OK;
     default: return PSACX_EINVAL;
     }
 }
@@ -147,10 +149,11 @@ int psacx_configure_from_env(psacx_ctx* c) {
         {"PSACX_NO_WHOLE", PSACX_OPT_NO_WHOLE}, {"PSACX_NO_LAZY_RANKS", PSACX_OPT_NO_LAZY_RANKS},
         {"PSACX_NO_EARLY_OUT", PSACX_OPT_NO_EARLY_OUT}, {"PSACX_NO_SPREAD_CURSORS", PSACX_OPT_NO_SPREAD_CURSORS},
         {"PSACX_LOCATE_COUNT", PSACX_OPT_LOCATE_COUNT}, {"PSACX_GENERIC_REBUCKET", PSACX_OPT_GENERIC_REBUCKET},
-        {"PSACX_PLAIN_SIDE_KERNELS", PSACX_OPT_PLAIN_SIDE_KERNELS}};
+        {"PSACX_PLAIN_SIDE_KERNELS", PSACX_OPT_PLAIN_SIDE_KERNELS}, {"PSACX_LSD_BUCKET_PASSES", PSACX_OPT_LSD_BUCKET_PASSES}};
     (void)psacx_configure(c, PSACX_OPT_RESET, 0);
     for (const auto& f : flags) if (psacx_debug_env(f.name)) (void)psacx_configure(c, f.option, 1);
     if (const char* e = psacx_debug_env("PSACX_DIET_CAP")) (void)psacx_configure(c, PSACX_OPT_DIET_CAP, strtoull(e, nullptr, 10));
+    if (const char* e = psacx_debug_env("PSACX_FIRST_LEAD")) (void)psacx_configure(c, PSACX_OPT_FIRST_LEAD, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_ONE_WORD_MIN")) (void)psacx_configure(c, PSACX_OPT_ONE_WORD_MIN, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_ISA_UPDATE")) (void)psacx_configure(c, PSACX_OPT_ISA_UPDATE, e[0] == 's' ? 1 : 2);
     if (const char* e = psacx_debug_env("PSACX_LOCATE_SHAPE")) (void)psacx_configure(c, PSACX_OPT_LOCATE_SHAPE, e[0] == 'g' ? 2 : 1);

@@ -654,7 +654,33 @@ struct OneWordTabs {
     const unsigned long long* slab_start;    // [257]
     const SlabInfo* slab_info;               // [slab_start[256]]
     unsigned slab;                           // tiles per slab
+    // Sub-bucket form (engine.hpp: onew_bucket_passes, group form at 32 prefix bits in the word): the buckets are the 65 536 sub-buckets
+    // (top digit, next digit); bucket_off has their 65 537 starts, a sub-bucket owns exactly ceil(size / tile) tiles from first_tile[s] on and
+    // is its own single slab: its scan runs over its tiles (radix_sub_scan1w_kernel) and there are no slab totals to add (zero_row).
+    const unsigned* tile_sub = nullptr;      // [tiles of the launch] sub-bucket of every tile, ~0u behind the last one; null: the 256-bucket form
+    const unsigned* first_tile = nullptr;    // [65537]
+    const unsigned long long* zero_row = nullptr;   // [RADIX] zeros: the slab row of every sub-bucket
 };
+// what tile vt of a launch works on: tile t of `bucket`, whose records lie at [off, end); the bucket's tile rows start at row0, its slab rows at srow
+struct OneWordTile { unsigned bucket, t, row0, srow, slab_tiles; uint64_t off, end; bool none; };
+template <int TILE>
+__device__ __forceinline__ OneWordTile onew_tile(const OneWordTabs& tb, unsigned vt) {
+    OneWordTile w;
+    if (tb.tile_sub) {
+        const unsigned s = tb.tile_sub[vt];
+        w.none = s == ~0u;
+        w.bucket = w.none ? 0u : s;
+        w.row0 = tb.first_tile[w.bucket]; w.t = vt - w.row0; w.srow = 0; w.slab_tiles = ~0u;
+        w.off = tb.bucket_off[w.bucket]; w.end = tb.bucket_off[w.bucket + 1];
+    } else {
+        const unsigned gs = vt / tb.slab;
+        const SlabInfo si = tb.slab_info[gs];
+        w.none = false;
+        w.bucket = si.bucket; w.srow = si.slab0; w.row0 = si.slab0 * tb.slab; w.t = vt - w.row0; w.slab_tiles = tb.slab;
+        w.off = si.first - (uint64_t)(gs - si.slab0) * tb.slab * TILE; w.end = si.end;
+    }
+    return w;
+}
 
 template <int TAG>
 __global__ void radix_slab_info_kernel(const unsigned long long* __restrict__ bucket_off, const unsigned long long* __restrict__ slab_start,
@@ -678,11 +704,10 @@ __global__ __launch_bounds__(BLOCK) void radix_tile_hist1w_kernel(const uint64_t
     constexpr int TILE = BLOCK * ITEMS;
     constexpr int PER = 2;
     const unsigned vt = blockIdx.x;
-    const unsigned gs = vt / tb.slab;
-    const SlabInfo si = tb.slab_info[gs];
+    const OneWordTile si = onew_tile<TILE>(tb, vt);
     in += (uint64_t)si.bucket * in_pad;
-    const uint64_t g0 = si.first + (uint64_t)(vt - gs * tb.slab) * TILE;      // global index of the tile's first record
-    if (g0 >= si.end) return;
+    const uint64_t g0 = si.off + (uint64_t)si.t * TILE;      // global index of the tile's first record
+    if (si.none || g0 >= si.end) return;
     const uint64_t g1 = si.end - g0 < (uint64_t)TILE ? si.end : g0 + TILE;
     __shared__ unsigned lh[4][RADIX];
     for (int i = threadIdx.x; i < 4 * RADIX; i += BLOCK) (&lh[0][0])[i] = 0;
@@ -737,10 +762,9 @@ __global__ __launch_bounds__(BLOCK) void radix_tile_hist_bytes_kernel(const uint
     const unsigned wave = threadIdx.x / WAVE, lane = lane_id();
     const unsigned vt = blockIdx.x * NW + wave;
     if (vt >= vtiles) return;
-    const unsigned gs = vt / tb.slab;
-    const SlabInfo si = tb.slab_info[gs];
-    const uint64_t g0 = si.first + (uint64_t)(vt - gs * tb.slab) * TILE;      // global index of the tile's first record
-    if (g0 >= si.end) return;
+    const OneWordTile si = onew_tile<TILE>(tb, vt);
+    const uint64_t g0 = si.off + (uint64_t)si.t * TILE;      // global index of the tile's first record
+    if (si.none || g0 >= si.end) return;
     const uint64_t g1 = si.end - g0 < (uint64_t)TILE ? si.end : g0 + TILE;
     unsigned* const my = lh[wave];
 #pragma unroll
@@ -880,25 +904,183 @@ __global__ __launch_bounds__(BLOCK, ITEMS <= 6 ? 8 : ITEMS <= 8 ? 6 : 4) void ra
     for (int i = threadIdx.x; i < NW * RADIX; i += BLOCK) sh.wcnt[i] = 0;
     __syncthreads();
     const unsigned vt = sh.s_tile;
-    const unsigned gs = vt / tb.slab;
-    const SlabInfo si = tb.slab_info[gs];
-    const unsigned b = si.bucket, s0 = si.slab0;
-    const unsigned t = vt - s0 * tb.slab;
-    const uint64_t off = si.first - (uint64_t)(gs - s0) * tb.slab * TILE, n = si.end - off;
+    if (vt >= gridDim.x) return;
+    const OneWordTile si = onew_tile<TILE>(tb, vt);
+    const unsigned b = si.bucket, t = si.t;
+    const uint64_t off = si.off, n = si.end - off;
     in += (uint64_t)b * in_pad;
-    if ((uint64_t)t * TILE >= n) return;
+    if (si.none || (uint64_t)t * TILE >= n) return;
     const uint64_t remain = n - (uint64_t)t * TILE;
-    const unsigned* te = tile_excl + (uint64_t)s0 * tb.slab * RADIX;
-    const unsigned long long* se = slab_excl + (uint64_t)s0 * RADIX;
+    const unsigned* te = tile_excl + (uint64_t)si.row0 * RADIX;
+    const unsigned long long* se = tb.tile_sub ? tb.zero_row : slab_excl + (uint64_t)si.srow * RADIX;
     const unsigned long long* db = digit_base + (uint64_t)b * RADIX;
     if (remain >= (uint64_t)TILE)
         radix_scatter_tile<uint64_t, unsigned, BLOCK, ITEMS, true, false, false, true, VN>(sh, t, (unsigned)TILE, in + off, nullptr, nullptr, out, nullptr, v_out,
-                                                                                          shift, db, nullptr, nullptr, nullptr, 0, 0, te, se, nullptr, tb.slab,
+                                                                                          shift, db, nullptr, nullptr, nullptr, 0, 0, te, se, nullptr, si.slab_tiles,
                                                                                           (uint64_t)b, pack, nullptr, dnext, dnext_shift);
     else
         radix_scatter_tile<uint64_t, unsigned, BLOCK, ITEMS, false, false, false, true, VN>(sh, t, (unsigned)remain, in + off, nullptr, nullptr, out, nullptr, v_out,
-                                                                                           shift, db, nullptr, nullptr, nullptr, 0, 0, te, se, nullptr, tb.slab,
+                                                                                           shift, db, nullptr, nullptr, nullptr, 0, 0, te, se, nullptr, si.slab_tiles,
                                                                                            (uint64_t)b, pack, nullptr, dnext, dnext_shift);
+}
+
+// ---------------------------------------------------------------------------
+// Sub-bucket tables (OneWordTabs: tile_sub, first_tile), built on the device from the 65 537 starts the pass on the digit below the
+// top one left as its digit_base.
+// ---------------------------------------------------------------------------
+// one workgroup: first_tile[s] = tiles of the sub-buckets before s, first_tile[nb] = tiles in all
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void onew_sub_first_tile_kernel(const unsigned long long* __restrict__ off, unsigned nb, unsigned tile_records,
+                                                                    unsigned* __restrict__ first_tile) {
+    __shared__ unsigned tmp[BLOCK / WAVE + 1];
+    const unsigned per = (nb + BLOCK - 1) / BLOCK, s0 = threadIdx.x * per, s1 = s0 + per < nb ? s0 + per : nb;
+    unsigned sum = 0;
+    for (unsigned s = s0; s < s1; ++s) sum += (unsigned)((off[s + 1] - off[s] + tile_records - 1) / tile_records);
+    unsigned total;
+    unsigned run = block_scan_exclusive<BLOCK, unsigned>(sum, OpSum(), 0u, tmp, &total);
+    for (unsigned s = s0; s < s1; ++s) {
+        first_tile[s] = run;
+        run += (unsigned)((off[s + 1] - off[s] + tile_records - 1) / tile_records);
+    }
+    if (threadIdx.x == 0) first_tile[nb] = total;
+}
+// a wave per sub-bucket: tile_sub[t] = s for its tiles (the array was filled with ~0u; cap: its entries)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void onew_sub_tile_fill_kernel(const unsigned* __restrict__ first_tile, unsigned nb, unsigned cap, unsigned* __restrict__ tile_sub) {
+    const unsigned s = blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE;
+    if (s >= nb) return;
+    const unsigned t1 = first_tile[s + 1] < cap ? first_tile[s + 1] : cap;
+    for (unsigned t = first_tile[s] + lane_id(); t < t1; t += WAVE) tile_sub[t] = s;
+}
+// one workgroup per sub-bucket (its own slab): exclusive scan of its tile counts per digit (in place) and the start of every digit of the sub-bucket
+template <int TAG>
+__global__ __launch_bounds__(RADIX) void radix_sub_scan1w_kernel(unsigned* __restrict__ tile_hist, OneWordTabs tb, unsigned long long* __restrict__ digit_base) {
+    __shared__ unsigned long long tmp[RADIX / WAVE + 1];
+    const unsigned s = blockIdx.x, d = threadIdx.x;
+    const unsigned t0 = tb.first_tile[s], nt = tb.first_tile[s + 1] - t0;
+    unsigned* __restrict__ rows = tile_hist + (uint64_t)t0 * RADIX;
+    unsigned long long run = 0;
+    constexpr int B = 16;
+    for (unsigned b0 = 0; b0 < nt; b0 += B) {
+        unsigned v[B];
+#pragma unroll
+        for (int j = 0; j < B; ++j) v[j] = b0 + j < nt ? rows[(uint64_t)(b0 + j) * RADIX + d] : 0u;
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            if (b0 + j < nt) rows[(uint64_t)(b0 + j) * RADIX + d] = (unsigned)run;
+            run += v[j];
+        }
+    }
+    unsigned long long total;
+    const unsigned long long start = block_scan_exclusive<RADIX, unsigned long long>(run, OpSum(), 0ull, tmp, &total);
+    digit_base[(uint64_t)s * RADIX + d] = tb.bucket_off[s] + start;
+}
+// the largest group of a monotone table of group starts (the last group ends at nrec), into *out (zeroed)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void onew_max_group_kernel(const unsigned long long* __restrict__ starts, uint64_t ngroups, uint64_t nrec,
+                                                               unsigned long long* __restrict__ out) {
+    unsigned long long m = 0;
+    for (uint64_t g = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; g < ngroups; g += (uint64_t)gridDim.x * BLOCK) {
+        const unsigned long long a = starts[g], b = g + 1 < ngroups ? starts[g + 1] : (unsigned long long)nrec;
+        const unsigned long long sz = b >= a ? b - a : ~0ull;
+        m = sz > m ? sz : m;
+    }
+    m = wave_reduce<uint64_t>((uint64_t)m, OpMax());
+    if (lane_id() == 0 && m) atomicMax(out, m);
+}
+
+// ---------------------------------------------------------------------------
+// The last 16 prefix bits on chip (engine.hpp: onew_bucket_passes, group form).  The records that agree in everything above their
+// low 16 prefix bits form a group, [starts[g], starts[g + 1]); groups hold n / 2^24 records at 32 prefix bits in the word -- 256 at
+// n = 2^32.  A wave owns whole groups: it takes 64 consecutive groups per trip (they lie in ONE bucket of the pass before: 256 groups
+// each, numbered from a multiple of 256), cuts them into batches of whole groups of at most GROUP_CAP records, reads a batch into
+// registers, orders it by stable 8-bit counting rounds through its own counters and stage in LDS -- two rounds for one group, a third
+// on the digit above for a batch of several groups (that digit numbers the groups of a bucket) -- and writes it back where it
+// came from, with the lowest prefix byte of every record beside it (tie_bytes).  In place is safe because the wave has read the whole
+// batch before it writes, and no other wave touches these groups.  No workgroup barrier.
+// A group longer than GROUP_CAP is left as it is: the caller checks the largest group before it launches.
+// ---------------------------------------------------------------------------
+constexpr int GROUP_CAP = 512;
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void group_sort16_kernel(uint64_t* __restrict__ recs, const unsigned long long* __restrict__ starts, uint64_t ngroups,
+                                                             uint64_t nrec, int sfield, uint8_t* __restrict__ tie_bytes) {
+    constexpr int NW = BLOCK / WAVE, ROWS = GROUP_CAP / WAVE;
+    __shared__ unsigned s_cnt[NW][RADIX];
+    __shared__ uint64_t s_stage[NW][GROUP_CAP];
+    const unsigned wave = threadIdx.x / WAVE, lane = lane_id();
+    unsigned* const cnt = s_cnt[wave];
+    uint64_t* const stage = s_stage[wave];
+    const uint64_t nchunks = (ngroups + WAVE - 1) / WAVE;
+    for (uint64_t ch = (uint64_t)blockIdx.x * NW + wave; ch < nchunks; ch += (uint64_t)gridDim.x * NW) {
+        const uint64_t g0 = ch * WAVE;
+        const uint64_t s = g0 + lane < ngroups ? (uint64_t)starts[g0 + lane] : nrec;
+        uint64_t snext = shfl<uint64_t>(s, (int)((lane + 1) & (WAVE - 1)));
+        if (lane == WAVE - 1) snext = g0 + WAVE < ngroups ? (uint64_t)starts[g0 + WAVE] : nrec;
+        if (__ballot(snext < s || snext > nrec)) continue;          // (tables that are not what they must be: nothing is touched)
+        unsigned g = 0;
+        while (g < (unsigned)WAVE) {
+            const uint64_t a = shfl<uint64_t>(s, (int)g);
+            // the groups g .. g + run - 1 end at most GROUP_CAP records behind a (the starts are monotone: the lanes that fit come first)
+            const uint64_t fit = __ballot(snext - a <= (uint64_t)GROUP_CAP) >> g;
+            const unsigned run = ~fit ? (unsigned)__builtin_ctzll(~fit) : (unsigned)WAVE;
+            if (run == 0) { ++g; continue; }
+            const unsigned count = (unsigned)(shfl<uint64_t>(snext, (int)(g + run - 1)) - a);
+            const unsigned filled = (unsigned)__builtin_popcountll(__ballot(lane >= g && lane < g + run && snext != s));
+            g += run;
+            if (count == 0) continue;
+            const int rounds = count == 1 ? 0 : filled > 1 ? 3 : 2;
+            const unsigned rows = (count + WAVE - 1) / WAVE;
+            uint64_t r[ROWS];
+#pragma unroll
+            for (int i = 0; i < ROWS; ++i) r[i] = (unsigned)(i * WAVE) + lane < count ? recs[a + (unsigned)(i * WAVE) + lane] : 0ull;
+            for (int rd = 0; rd < rounds; ++rd) {
+                const int shift = sfield + rd * RADIX_BITS;
+#pragma unroll
+                for (int i = 0; i < RADIX / WAVE; ++i) cnt[i * WAVE + lane] = 0;
+                xrun_order();
+                // rank inside the wave, row by row (radix_scatter_tile): stable in the order row * 64 + lane
+                unsigned rank[ROWS];
+#pragma unroll
+                for (int i = 0; i < ROWS; ++i) {
+                    if ((unsigned)i < rows) {
+                        const bool valid = (unsigned)(i * WAVE) + lane < count;
+                        const unsigned d = (unsigned)(r[i] >> shift) & (RADIX - 1);
+                        const uint64_t m = match_any8(d, valid);
+                        const unsigned prior = __hip_atomic_load(&cnt[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                        if (valid && below == 0)
+                            __hip_atomic_fetch_add(&cnt[d], (unsigned)__builtin_popcountll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        rank[i] = prior + below;
+                    }
+                }
+                xrun_order();
+                // exclusive scan of the 256 counters: four neighbours per lane
+                {
+                    uint4 c4 = reinterpret_cast<uint4*>(cnt)[lane];
+                    const unsigned sum = c4.x + c4.y + c4.z + c4.w;
+                    unsigned ex = wave_scan_inclusive<unsigned>(sum, OpSum()) - sum;
+                    uint4 e4;
+                    e4.x = ex; ex += c4.x; e4.y = ex; ex += c4.y; e4.z = ex; ex += c4.z; e4.w = ex;
+                    reinterpret_cast<uint4*>(cnt)[lane] = e4;
+                }
+                xrun_order();
+#pragma unroll
+                for (int i = 0; i < ROWS; ++i)
+                    if ((unsigned)i < rows && (unsigned)(i * WAVE) + lane < count) stage[cnt[(unsigned)(r[i] >> shift) & (RADIX - 1)] + rank[i]] = r[i];
+                xrun_order();
+#pragma unroll
+                for (int i = 0; i < ROWS; ++i)
+                    if ((unsigned)i < rows && (unsigned)(i * WAVE) + lane < count) r[i] = stage[(unsigned)(i * WAVE) + lane];
+                xrun_order();
+            }
+#pragma unroll
+            for (int i = 0; i < ROWS; ++i)
+                if ((unsigned)(i * WAVE) + lane < count) {
+                    recs[a + (unsigned)(i * WAVE) + lane] = r[i];
+                    tie_bytes[a + (unsigned)(i * WAVE) + lane] = (uint8_t)(r[i] >> sfield);
+                }
+        }
+    }
 }
 
 } // namespace psacx
