@@ -116,16 +116,8 @@ size_t carve(Arena& a, Work<T>& w, uint64_t n, bool with_lcp, T* d_lcp, bool die
     w.d_gwin = a.take<uint64_t>((size_t)(n >> ISA_NARROW_WB) + 2);
     w.d_heavy = a.take<uint64_t>(HeavyTabs::words(HEAVY_MAXB));
     w.d_htile = a.take<ulonglong2>((n + SCAN_TILE_MIN - 1) / SCAN_TILE_MIN + 1);
-    w.sc.d_hist = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-    w.sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-    w.sc.desc_bytes = sort_desc_bytes(n);
-    // (PSACX_OPT_FIRST_LEAD: a small text sorted on 40 leading bits needs the sub-bucket tables of a large one -- engine.hpp: onew_group_layout)
-    if (sizeof(T) == 8 && kn.first_lead == 32 + RADIX_BITS && n < (1ull << 30))
-        w.sc.desc_bytes += (size_t)(n / SORT_TILE_MIN + ONEW_SUB) * RADIX * sizeof(unsigned) + (size_t)ONEW_SUB * RADIX * 8 + (8u << 20);
-    w.sc.d_desc = a.take<char>(w.sc.desc_bytes);
-    w.sc.d_err = a.take<unsigned>(64);
-    w.sc.d_summary = a.take<unsigned long long>(8);
-    w.sc.d_partials = a.take<unsigned long long>(((size_t)(n / 2048) + 8192) * 4);
+    // (PSACX_OPT_FIRST_LEAD: a small text sorted on 40 leading bits needs the sub-bucket tables of a large one -- sort_scratch.hpp: onew_group_layout)
+    w.sc.take(a, n, false, (sizeof(T) == 8 && kn.first_lead == 32 + RADIX_BITS && n < (1ull << 30)) ? onew_sub_bucket_supplement(n) : 0);
     // digit bytes between the three-kernel passes of the sorts of 64-bit words (engine.hpp: dispatch_pass3): one byte per record of the largest sort
     // that has no such array of its own -- the first sort of a repetitive text, the sorts of the refinement rounds: n records
     w.sc.d_dig = nullptr; w.sc.dig_cap = 0;
@@ -494,7 +486,7 @@ int gather_heavy_by_levels(psacx_ctx* c, Work<T>& w, uint64_t n, uint64_t h, con
                        (const uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, (const ulonglong2*)nullptr, 0u, stripes);
     hipLaunchKernelGGL((window_gather_heavy_kernel<T, 1024, WB>), dim3((unsigned)nwin), dim3(1024), (size_t)nb * 2 * sizeof(uint32_t), c->stream, (const uint64_t*)lvl_b,
                        (const unsigned*)c1, n, h, d_isa, kb2, (uint32_t)nb, ht, LK, LV, HB, w.sc.d_partials);
-    uint64_t* const h_light = reinterpret_cast<uint64_t*>(c->pinned + 112);
+    uint64_t* const h_light = reinterpret_cast<uint64_t*>(c->pinned + PIN_LIGHT);
     PSACX_HIP(c, hipGetLastError());
     PSACX_HIP(c, hipMemcpyAsync(h_light, ht.light, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -564,7 +556,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
     const bool no_fast = (flags & PSACX_NO_FAST) != 0;
     const Knobs kn = c->knobs;
     psacx_stats& st = c->stats;
-    PSACX_TRY(ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 4096));
+    PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
 
     if (n == 1) {
         PSACX_HIP(c, hipMemsetAsync(d_sa, 0, sizeof(T), c->stream));
@@ -617,9 +609,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
     Arena ar(c->slab);
     carve<T>(ar, w, n, WITH_LCP, d_lcp, diet, cap, d_sa, d_isa, kn);
     st.workspace_bytes = c->slab_bytes;
-    w.sc.h_hist = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
-    w.sc.h_base = w.sc.h_hist + (size_t)MAX_PASSES * RADIX;
-    w.sc.h_summary = reinterpret_cast<unsigned long long*>(c->pinned + 256);
+    w.sc.bind_pinned(c);
     PSACX_HIP(c, hipMemsetAsync(w.sc.d_err, 0, 64 * sizeof(unsigned), c->stream));
 
     ProfScope* total = new ProfScope(c, TC_TOTAL);
@@ -634,7 +624,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
                            d_text, n, w.d_hist256);
         PSACX_HIP(c, hipGetLastError());
     }
-    unsigned long long* h_hist = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
+    unsigned long long* h_hist = w.sc.h_hist;          // (free until the first sort)
     PSACX_HIP(c, hipMemcpyAsync(h_hist, w.d_hist256, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
     uint32_t lc = 1;
@@ -716,7 +706,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
             nb = (n + HB * HI - 1) / (HB * HI);
             hipLaunchKernelGGL((key_pairs_kernel<T, HB, HI, false, true>), dim3((unsigned)nb), dim3(HB), 0, c->stream, d_text, n, n,
                                tab, ks, first_in.k1, k2rec, w.sc.d_partials, (const T*)nullptr,
-                               reinterpret_cast<unsigned*>(w.sc.d_desc + 256), (int)lo1);
+                               pass_scratch(w.sc.d_desc, nb).tile_hist, (int)lo1);
         } else
             hipLaunchKernelGGL((key_pairs_kernel<T, KB, KI>), dim3((unsigned)nb), dim3(KB), 0, c->stream, d_text, n, n,
                                tab, ks, first_in.k1, k2rec, w.sc.d_partials, (const T*)nullptr);
@@ -773,7 +763,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
         //  32-bit words 256 x 16: 1.2-1.3 ms at 2^28, 128 x 32: 1.4)
         constexpr int TB = 256, TI = sizeof(T) == 8 ? 32 : 16, TG = 8;
         unsigned long long* d_big = reinterpret_cast<unsigned long long*>(w.d_totals + 2);
-        unsigned long long* h_big = reinterpret_cast<unsigned long long*>(c->pinned + 64);
+        unsigned long long* h_big = reinterpret_cast<unsigned long long*>(c->pinned + PIN_TIE_BIG);
         {
             ProfScope ps(c, TC_GATHER);
             PSACX_HIP(c, hipMemsetAsync(d_big, 0, sizeof(unsigned long long), c->stream));
@@ -892,7 +882,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
         T* const pyr1 = (WITH_LCP && w.pyr.nlev > 1) ? w.pyr.lvl[1] : (T*)nullptr;   // level 1 comes out of the rebucket kernel
         // ... and so do the tile histograms of the inversion's first radix level when the tiles agree
         isa_hist_ready = !fuse32 && isa_radix_levels<T>(n, kn) && (uint64_t)ScanCfg<T>::TILE == (uint64_t)ScatterCfg<T>::TILE;
-        unsigned* const sa_hist = isa_hist_ready ? reinterpret_cast<unsigned*>(w.sc.d_desc + 256) : (unsigned*)nullptr;
+        unsigned* const sa_hist = isa_hist_ready ? pass_scratch(w.sc.d_desc, ntiles).tile_hist : (unsigned*)nullptr;
         if (gsa) {
             PSACX_TRY((run_carries<T, false, true>(c, w, sorted.k1, sorted.k2, nullptr, n, d_sa, ks)));
             hipLaunchKernelGGL((rebucket_first_kernel<T, ScanCfg<T>::BLOCK, SCAN_ITEMS, WITH_LCP, true>), dim3((unsigned)ntiles),
@@ -1112,10 +1102,10 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
             if (lds_sort_possible) {
                 // (wide windows first; both questions are asked before the one synchronisation)
                 const uint64_t nt_wide = (cnt + BSORT_W_WIDE - 1) / BSORT_W_WIDE, nt_narrow = (cnt + BSORT_W_NARROW - 1) / BSORT_W_NARROW;
-                uint64_t* const st_wide = reinterpret_cast<uint64_t*>(w.sc.d_desc + 256);
+                uint64_t* const st_wide = reinterpret_cast<uint64_t*>(w.sc.d_desc + SCRATCH_COUNTER_BYTES);          // (behind the tile counter, where a pass keeps its histograms)
                 uint64_t* const st_narrow = st_wide + nt_wide + 1;
                 unsigned long long* d_over = reinterpret_cast<unsigned long long*>(w.d_over);
-                unsigned long long* h_over = reinterpret_cast<unsigned long long*>(c->pinned + 96);
+                unsigned long long* h_over = reinterpret_cast<unsigned long long*>(c->pinned + PIN_OVER);
                 {
                     ProfScope ps(c, TC_SORT_HIST);
                     PSACX_HIP(c, hipMemsetAsync(d_over, 0, 2 * sizeof(unsigned long long), c->stream));
@@ -1227,7 +1217,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
             // ... unless SA order is nearly text order (sa_locality_kernel): 2^27 equal characters take 9.2 ms per round through
             // the list and 12.0 ms as whole rounds, a period-1024 tandem repeat 18.0 against 14.7 (profiles/r03g_*)
             unsigned long long* d_near = reinterpret_cast<unsigned long long*>(w.d_totals + 2);
-            unsigned long long* h_near = reinterpret_cast<unsigned long long*>(c->pinned + 64);
+            unsigned long long* h_near = reinterpret_cast<unsigned long long*>(c->pinned + PIN_TIE_BIG);
             const uint64_t samples = 1u << 16;
             PSACX_HIP(c, hipMemsetAsync(d_near, 0, sizeof(unsigned long long), c->stream));
             hipLaunchKernelGGL((sa_locality_kernel<T>), dim3(64), dim3(256), 0, c->stream, d_sa, n, samples, d_near);
@@ -1259,7 +1249,7 @@ int construct_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, uint32_t k_re
             PSACX_HIP(c, hipStreamSynchronize(c->stream));
             const uint64_t room = w.cap_active > 2ull * ScanCfg<T>::TILE ? w.cap_active - 2ull * ScanCfg<T>::TILE : 0;
             uint64_t sum_act = 0, sum_unf = 0, s0 = 0;
-            T* h_id = reinterpret_cast<T*>(c->pinned + 128);
+            T* h_id = reinterpret_cast<T*>(c->pinned + PIN_ID);
             // (64-bit words, at most 2^32 characters: the slabs' ISA entries are collected by destination class and stored at the end of the round)
             const bool collect = sizeof(T) == 8 && n <= (1ull << 32) && isa_narrow_levels<T>(n, kn) > 0 && room >= SMALL_SORT_MAX &&
                                  (kn.isa_update == 2 || (kn.isa_update == 0 && n >= (1ull << 31)));
@@ -1359,7 +1349,7 @@ int construct_gsa_dispatch(psacx_ctx* c, const uint8_t* d_text, uint64_t n, cons
     // the offsets must describe m non-empty strings covering [0, n) (stringset.hpp:53-72); a malformed array would
     // send the window kernels out of bounds
     {
-        PSACX_TRY(ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 4096));
+        PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
         PSACX_TRY(ensure_slab(c, 4096));
         unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(c->slab);
         PSACX_HIP(c, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream));
@@ -1519,26 +1509,18 @@ int pair_sort_dev(psacx_ctx* c, T* d_b1, T* d_b2, T* d_idx, uint64_t n, uint32_t
     if (!c || !d_b1 || !d_b2 || !d_idx || n == 0) return PSACX_EINVAL;
     if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
     PSACX_HIP(c, hipSetDevice(c->device));
-    PSACX_TRY(ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 4096));
+    PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
     Arena dry(nullptr);
     auto layout = [&](Arena& a, SortBufs<T>& alt, SortScratch& sc, T*& vtmp) {
         alt.k1 = a.take<T>(n); alt.k2 = a.take<T>(n); alt.v = a.take<T>(n); vtmp = a.take<T>(n);
-        sc.d_hist = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-        sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-        sc.desc_bytes = sort_desc_bytes(n);
-        sc.d_desc = a.take<char>(sc.desc_bytes);
-        sc.d_err = a.take<unsigned>(64);
-        sc.d_summary = a.take<unsigned long long>(8);
-        sc.d_partials = a.take<unsigned long long>(((size_t)(n / 2048) + 8192) * 4);
+        sc.take(a, n);
     };
     SortBufs<T> alt; SortScratch sc; T* vtmp;
     layout(dry, alt, sc, vtmp);
     PSACX_TRY(ensure_slab(c, dry.off + 4096));
     Arena ar(c->slab);
     layout(ar, alt, sc, vtmp);
-    sc.h_hist = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
-    sc.h_base = sc.h_hist + (size_t)MAX_PASSES * RADIX;
-    sc.h_summary = reinterpret_cast<unsigned long long*>(c->pinned + 256);
+    sc.bind_pinned(c);
     PSACX_HIP(c, hipMemsetAsync(sc.d_err, 0, 64 * sizeof(unsigned), c->stream));
     std::memset(&c->stats, 0, sizeof(c->stats));
     c->profile = true; c->ev_used = 0;

@@ -220,23 +220,12 @@ int op_pair_sort(psacx_ctx* c, T* k1, T* k2, T* v, T* a1, T* a2, T* av, uint64_t
     *where = 0;
     if (n < 2 && !iota && !v32_in) return PSACX_OK;      // (a made-up or 32-bit payload still has to be written out in full words)
     if (n == 0) return PSACX_OK;
-    PSACX_TRY(ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 4096));
+    PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
     SortScratch sc;
-    auto layout = [&](Arena& a) {
-        sc.d_hist = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-        sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-        sc.desc_bytes = sort_desc_bytes(n);
-        sc.d_desc = a.take<char>(sc.desc_bytes);
-        sc.d_err = a.take<unsigned>(64);
-        sc.d_summary = a.take<unsigned long long>(8);
-        sc.d_partials = a.take<unsigned long long>(((size_t)(n / 2048) + 8192) * 4);
-    };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
+    { Arena dry(nullptr); sc.take(dry, n); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
     Arena ar(c->slab);
-    layout(ar);
-    sc.h_hist = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
-    sc.h_base = sc.h_hist + (size_t)MAX_PASSES * RADIX;
-    sc.h_summary = reinterpret_cast<unsigned long long*>(c->pinned + 256);
+    sc.take(ar, n);
+    sc.bind_pinned(c);
     PSACX_HIP(c, hipMemsetAsync(sc.d_err, 0, 64 * sizeof(unsigned), c->stream));
     c->profile = c->profile_ops; c->ev_used = 0;
     SortBufs<T> in{k1, k2, v}, alt{a1, a2, av}, res;
@@ -260,15 +249,10 @@ int op_split_by(psacx_ctx* c, const T* k1, const T* k2, const T* v, uint64_t n, 
     if (nsplit > 63) return PSACX_EINVAL;
     for (uint32_t i = 0; i <= nsplit + 1; ++i) class_start[i] = 0;
     if (n == 0) return PSACX_OK;
-    PSACX_TRY(ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 4096));
+    PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
     SortScratch sc;
     T* cls = nullptr;
-    auto layout = [&](Arena& a) {
-        cls = a.take<T>(n);
-        sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-        sc.desc_bytes = sort_desc_bytes(n);
-        sc.d_desc = a.take<char>(sc.desc_bytes);
-    };
+    auto layout = [&](Arena& a) { cls = a.take<T>(n); sc.take(a, n, /*base_desc_only=*/true); };
     { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
     Arena ar(c->slab);
     layout(ar);
@@ -279,7 +263,7 @@ int op_split_by(psacx_ctx* c, const T* k1, const T* k2, const T* v, uint64_t n, 
                        (unsigned long long)my_rank, cls);
     PSACX_HIP(c, hipGetLastError());
     SortBufs<T> in{const_cast<T*>(k1), const_cast<T*>(k2), const_cast<T*>(v)}, out{o1, o2, ov};
-    unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
+    unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + PIN_HIST);
     PSACX_TRY(class_partition<T>(c, sc, in, out, cls, n, starts));
     for (uint32_t i = 0; i <= nsplit; ++i) class_start[i] = starts[i];
     class_start[nsplit + 1] = n;
@@ -301,7 +285,7 @@ int op_pair_bounds(psacx_ctx* c, const T* s1, const T* s2, uint64_t n, const uin
                    int use_second, uint64_t* lb, uint64_t* ub) {
     OP_PROLOGUE(c);
     if (nq == 0) return PSACX_OK;
-    PSACX_TRY(ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 4096));
+    PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
     Arena dry(nullptr); dry.take<unsigned long long>((size_t)nq * 4);
     PSACX_TRY(ensure_slab(c, dry.off + 4096));
     Arena ar(c->slab);

@@ -628,19 +628,26 @@ struct SortScratch {
     unsigned long long* d_partials;// per-workgroup key summaries of the producer kernel
     uint8_t* d_dig = nullptr;      // digit bytes between the three-kernel passes of a sort of 64-bit words with 32-bit payloads (dispatch_pass3), or null
     uint64_t dig_cap = 0;          // ... records it has room for (the array 16-byte aligned and readable up to the next multiple of 16 beyond them: the histograms read 16-byte pieces)
+
+    // The device arrays of a sort of n records out of `a`: d_hist, d_base and d_desc back to back (pair_sort's device-side scan asks for that), then d_err, d_summary,
+    // d_partials.  base_desc_only: d_base and d_desc alone (class_partition reads nothing else); desc_extra: more room in d_desc (sort_scratch.hpp: onew_sub_bucket_supplement).
+    void take(Arena& a, uint64_t n, bool base_desc_only = false, size_t desc_extra = 0) {
+        if (!base_desc_only) d_hist = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
+        d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
+        desc_bytes = sort_desc_bytes(n) + desc_extra;
+        d_desc = a.take<char>(desc_bytes);
+        if (base_desc_only) return;
+        d_err = a.take<unsigned>(64);
+        d_summary = a.take<unsigned long long>(8);
+        d_partials = a.take<unsigned long long>(((size_t)(n / 2048) + 8192) * 4);
+    }
+    // the pinned words (sort_scratch.hpp: PIN_*); the ctx's pinned memory holds PINNED_SORT_BYTES + 4096 at least
+    void bind_pinned(const psacx_ctx* c) {
+        h_hist = reinterpret_cast<unsigned long long*>(c->pinned + PIN_HIST);
+        h_base = reinterpret_cast<unsigned long long*>(c->pinned + PIN_BASE);
+        h_summary = reinterpret_cast<unsigned long long*>(c->pinned + PIN_SUMMARY);
+    }
 };
-
-constexpr int SORT_TILE_MIN = 2048;   // smallest tile of any scatter configuration
-constexpr uint64_t SMALL_SORT_MAX = 1ull << 21;   // below: single-sweep scatter passes with decoupled look-back
-
-inline size_t sort_desc_bytes(uint64_t n) {
-    const uint64_t nt = (n + SORT_TILE_MIN - 1) / SORT_TILE_MIN + 1;
-    // look-back descriptors, or (three-kernel form) per-tile counters + per-slab totals
-    size_t b = 1024 + nt * RADIX * sizeof(uint64_t) + (nt / SLAB_TILES + 2) * RADIX * sizeof(uint64_t);
-    // small sorts (look-back form): one descriptor region per pass, so that one memset serves the whole sort
-    if (n < SMALL_SORT_MAX) b = std::max<size_t>(b, (size_t)MAX_PASSES * (512 + nt * RADIX * sizeof(uint32_t)));
-    return b;
-}
 
 // tiles per XCD-local chunk of the tile queue (dev_common.hpp: claim_tile; 0 = plain ticket order)
 inline unsigned sort_chunk_for(uint64_t n, bool three) {
@@ -671,6 +678,28 @@ inline void dispatch_scatter(psacx_ctx* c, const T* kd_in, const T* ko_in, const
     launch_scatter<T, D, ScatterCfg<T>::BLOCK, ScatterCfg<T>::ITEMS>(c, kd_in, ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, desc, err, nullptr, spec, spec_n);
 }
 
+// The tables of a three-kernel pass from its tile histograms: the scan inside the slabs, then over the slab totals (the digit starts into `base`).
+inline void launch_pass_scans(psacx_ctx* c, const PassScratch& ps, unsigned long long* base) {
+    hipLaunchKernelGGL(radix_slab_scan_kernel<0>, dim3((unsigned)ps.nslabs), dim3(RADIX), 0, c->stream, ps.tile_hist, ps.ntiles, ps.slab_tot, ps.slab_tiles);
+    hipLaunchKernelGGL(radix_top_scan_kernel<0>, dim3(1), dim3(RADIX), 0, c->stream, ps.slab_tot, ps.nslabs, base);
+}
+
+// What every launch of radix_scatter3_kernel is given (radix.hpp: radix_scatter3_kernel, radix_scatter_tile); the callers choose the template arguments.
+template <typename T>
+struct Scatter3Args {
+    const T* kd_in; const T* ko_in; const T* v_in; T* kd_out; T* ko_out; T* v_out;
+    uint64_t n; int shift; const unsigned long long* base; PassScratch ps;
+    uint64_t spec, spec_n; unsigned chunk;
+    const T* dsrc; uint64_t voff;                          // EXT: the digits come from this array; offset of a made-up payload
+    uint8_t* dnext; int dnext_shift, dnext_ko;             // DNEXT3: the digit byte of the next pass
+};
+template <typename T, int BLOCK, int ITEMS, bool EXT, int MINW = 1, bool NOKO = false, int VN = 0, int CLSB = sizeof(T), bool DNEXT3 = false>
+inline void launch_scatter3(psacx_ctx* c, const Scatter3Args<T>& a) {
+    hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, EXT, MINW, NOKO, VN, CLSB, DNEXT3>), dim3((unsigned)a.ps.ntiles), dim3(BLOCK), 0, c->stream,
+                       a.kd_in, a.ko_in, a.v_in, a.kd_out, a.ko_out, a.v_out, a.n, a.shift, a.base, a.ps.tile_hist, a.ps.slab_tot, (unsigned long long*)nullptr,
+                       a.spec, a.spec_n, a.ps.counter, a.chunk, a.dsrc, a.ps.slab_tiles, a.voff, 0u, a.dnext, a.dnext_shift, a.dnext_ko);
+}
+
 // One pass of the three-kernel form: tile histograms (unless the producer of the keys left them), slab / top scans, scatter.
 // vn (64-bit words, two-word records): 0 = word payloads, 1 = 32-bit payload entries on both sides, 2 = 32-bit entries in and
 // words out (radix.hpp: VN).
@@ -682,77 +711,33 @@ inline void dispatch_pass3(psacx_ctx* c, const T* kd_in, const T* ko_in, const T
     // the records (8 bytes per record less); dig_out (vn == 1 only): this pass leaves the byte of the NEXT pass (bits dig_shift .. + 7 of the digit
     // word, or of the other key word when dig_ko) beside its records.  One array serves both: the histograms are done when the scatter starts.
     constexpr int BLOCK = ScatterCfg<T>::BLOCK, ITEMS = ScatterCfg<T>::ITEMS, TILE = BLOCK * ITEMS;
-    const uint64_t ntiles = (n + TILE - 1) / TILE;
-    const unsigned slab_tiles = slab_tiles_for(ntiles);
-    const uint64_t nslabs = (ntiles + slab_tiles - 1) / slab_tiles;
-    unsigned* tile_hist = reinterpret_cast<unsigned*>(scratch + 256);
-    unsigned long long* slab_tot = reinterpret_cast<unsigned long long*>(scratch + 256 + ((ntiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255));
+    const PassScratch pl = pass_scratch(scratch, (n + TILE - 1) / TILE);
     {
         ProfScope ps(c, TC_SORT_TILEHIST);
         if (have_hist) {       // (the producer of the keys may have left this pass's tile histograms in place)
         } else if (dig_in)
-            hipLaunchKernelGGL((radix_tile_hist_bytes_flat_kernel<BLOCK, TILE>), dim3((unsigned)((ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0, c->stream,
-                               dig_in, n, ntiles, tile_hist);
+            hipLaunchKernelGGL((radix_tile_hist_bytes_flat_kernel<BLOCK, TILE>), dim3((unsigned)((pl.ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0, c->stream,
+                               dig_in, n, pl.ntiles, pl.tile_hist);
         else
-            hipLaunchKernelGGL((radix_tile_hist_kernel<T, BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in, n,
-                               shift, tile_hist);
-        hipLaunchKernelGGL(radix_slab_scan_kernel<0>, dim3((unsigned)nslabs), dim3(RADIX), 0, c->stream, tile_hist, ntiles, slab_tot, slab_tiles);
-        hipLaunchKernelGGL(radix_top_scan_kernel<0>, dim3(1), dim3(RADIX), 0, c->stream, slab_tot, nslabs,
-                           const_cast<unsigned long long*>(base));
+            hipLaunchKernelGGL((radix_tile_hist_kernel<T, BLOCK, ITEMS>), dim3((unsigned)pl.ntiles), dim3(BLOCK), 0, c->stream, kd_in, n,
+                               shift, pl.tile_hist);
+        launch_pass_scans(c, pl, const_cast<unsigned long long*>(base));
     }
     ProfScope ps(c, ko_in ? TC_SORT_SCATTER3 : TC_SORT_SCATTER2);
-    unsigned* const counter = reinterpret_cast<unsigned*>(scratch);
-    const unsigned chunk = sort_chunk_for(n, true);
+    // (two-word records have no other key word to take the digit byte of the next pass from)
+    const Scatter3Args<T> a{kd_in, ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, pl, spec, spec_n, sort_chunk_for(n, true),
+                            (const T*)nullptr, 0, dig_out, dig_shift, ko_in ? dig_ko : 0};
     if constexpr (sizeof(T) == 8) {
-        // 32-bit payload arrays: registers capped for six waves per SIMD = three workgroups per CU: the narrow forms need 82, the cap
-        // costs them a few spilled registers and gains a third tile in flight (the pass is bound by the latency chain of a tile)
-        if (vn == 1 && !ko_in && dig_out) {
-            hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 6, true, 1, sizeof(T), true>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in, ko_in, v_in, kd_out,
-                               ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n, counter, chunk, (const T*)nullptr, slab_tiles,
-                               (uint64_t)0, 0u, dig_out, dig_shift, 0);
-            return;
-        }
-        if (vn == 1 && !ko_in) {
-            hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 6, true, 1>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in, ko_in, v_in, kd_out,
-                               ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n, counter, chunk, (const T*)nullptr, slab_tiles);
-            return;
-        }
-        if (vn == 2 && !ko_in) {
-            hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 6, true, 2>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in, ko_in, v_in, kd_out,
-                               ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n, counter, chunk, (const T*)nullptr, slab_tiles);
-            return;
-        }
+        // 32-bit payload arrays.  Two-word records: registers capped for six waves per SIMD = three workgroups per CU: the narrow forms need 82, the cap
+        // costs them a few spilled registers and gains a third tile in flight (the pass is bound by the latency chain of a tile).  Three-word records whose
+        // payload stays below 2^32 (the one-stage first round of repetitive texts): 40 instead of 48 bytes per record and pass
+        if (vn == 1 && dig_out) return ko_in ? launch_scatter3<T, BLOCK, ITEMS, false, 1, false, 1, sizeof(T), true>(c, a)
+                                             : launch_scatter3<T, BLOCK, ITEMS, false, 6, true, 1, sizeof(T), true>(c, a);
+        if (vn == 1) return ko_in ? launch_scatter3<T, BLOCK, ITEMS, false, 1, false, 1>(c, a) : launch_scatter3<T, BLOCK, ITEMS, false, 6, true, 1>(c, a);
+        if (vn == 2) return ko_in ? launch_scatter3<T, BLOCK, ITEMS, false, 1, false, 2>(c, a) : launch_scatter3<T, BLOCK, ITEMS, false, 6, true, 2>(c, a);
     }
-    if constexpr (sizeof(T) == 8) {
-        // three-word records whose payload stays below 2^32 (the suffixes of a text of at most 2^32 characters): 32-bit payload entries
-        // between the passes here too -- 40 instead of 48 bytes per record and pass (the one-stage first round of repetitive texts)
-        if (ko_in && vn == 1 && dig_out) {
-            hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 1, false, 1, sizeof(T), true>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in,
-                               ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n,
-                               counter, chunk, (const T*)nullptr, slab_tiles, (uint64_t)0, 0u, dig_out, dig_shift, dig_ko);
-            return;
-        }
-        if (ko_in && vn == 1) {
-            hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 1, false, 1>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in,
-                               ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n,
-                               counter, chunk, (const T*)nullptr, slab_tiles);
-            return;
-        }
-        if (ko_in && vn == 2) {
-            hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 1, false, 2>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in,
-                               ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n,
-                               counter, chunk, (const T*)nullptr, slab_tiles);
-            return;
-        }
-    }
-    if (ko_in)
-        hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 1>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in,
-                           ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n,
-                           counter, chunk, (const T*)nullptr, slab_tiles);
-    else            // two-word records (k1, v): the prefix sort of the first round
-        hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, false, 1, true>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, kd_in,
-                           ko_in, v_in, kd_out, ko_out, v_out, n, shift, base, tile_hist, slab_tot, (unsigned long long*)nullptr, spec, spec_n,
-                           counter, chunk, (const T*)nullptr, slab_tiles);
+    if (ko_in) launch_scatter3<T, BLOCK, ITEMS, false, 1>(c, a);
+    else launch_scatter3<T, BLOCK, ITEMS, false, 1, true>(c, a);            // two-word records (k1, v): the prefix sort of the first round
 }
 
 // One pass that groups records by an externally supplied 8-bit class (cls[i] < 256), stable.
@@ -761,26 +746,13 @@ template <typename T>
 int class_partition(psacx_ctx* c, SortScratch& sc, SortBufs<T> in, SortBufs<T> out, const T* cls, uint64_t n,
                     unsigned long long* class_start_host) {
     constexpr int BLOCK = 512, ITEMS = 12, TILE = BLOCK * ITEMS;
-    const uint64_t ntiles = (n + TILE - 1) / TILE;
-    const unsigned slab_tiles = slab_tiles_for(ntiles);
-    const uint64_t nslabs = (ntiles + slab_tiles - 1) / slab_tiles;
-    char* scratch = sc.d_desc;
-    unsigned* tile_hist = reinterpret_cast<unsigned*>(scratch + 256);
-    unsigned long long* slab_tot = reinterpret_cast<unsigned long long*>(scratch + 256 + ((ntiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255));
-    PSACX_HIP(c, hipMemsetAsync(scratch, 0, 256, c->stream));
-    hipLaunchKernelGGL((radix_tile_hist_kernel<T, BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, cls, n, 0, tile_hist);
-    hipLaunchKernelGGL(radix_slab_scan_kernel<0>, dim3((unsigned)nslabs), dim3(RADIX), 0, c->stream, tile_hist, ntiles, slab_tot, slab_tiles);
-    hipLaunchKernelGGL(radix_top_scan_kernel<0>, dim3(1), dim3(RADIX), 0, c->stream, slab_tot, nslabs, sc.d_base);
-    if (in.k2)
-        hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, true>), dim3((unsigned)ntiles), dim3(BLOCK), 0,
-                           c->stream, in.k1, in.k2, in.v, out.k1, out.k2, out.v, n, 0, sc.d_base, tile_hist, slab_tot,
-                           (unsigned long long*)nullptr, (uint64_t)0, (uint64_t)0, reinterpret_cast<unsigned*>(scratch),
-                           sort_chunk_for(n, true), cls, slab_tiles);
-    else            // two-word records (k1, v): routing (position, value) pairs to their owners
-        hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, true, 1, true>), dim3((unsigned)ntiles), dim3(BLOCK), 0,
-                           c->stream, in.k1, in.k2, in.v, out.k1, out.k2, out.v, n, 0, sc.d_base, tile_hist, slab_tot,
-                           (unsigned long long*)nullptr, (uint64_t)0, (uint64_t)0, reinterpret_cast<unsigned*>(scratch),
-                           sort_chunk_for(n, true), cls, slab_tiles);
+    const PassScratch pl = pass_scratch(sc.d_desc, (n + TILE - 1) / TILE);
+    PSACX_HIP(c, hipMemsetAsync(pl.counter, 0, 256, c->stream));
+    hipLaunchKernelGGL((radix_tile_hist_kernel<T, BLOCK, ITEMS>), dim3((unsigned)pl.ntiles), dim3(BLOCK), 0, c->stream, cls, n, 0, pl.tile_hist);
+    launch_pass_scans(c, pl, sc.d_base);
+    const Scatter3Args<T> a{in.k1, in.k2, in.v, out.k1, out.k2, out.v, n, 0, sc.d_base, pl, 0, 0, sort_chunk_for(n, true), cls, 0, nullptr, 0, 0};
+    if (in.k2) launch_scatter3<T, BLOCK, ITEMS, true>(c, a);
+    else launch_scatter3<T, BLOCK, ITEMS, true, 1, true>(c, a);            // two-word records (k1, v): routing (position, value) pairs to their owners
     PSACX_HIP(c, hipGetLastError());
     PSACX_HIP(c, hipMemcpyAsync(class_start_host, sc.d_base, RADIX * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -797,24 +769,14 @@ int piece_partition(psacx_ctx* c, char* scratch, unsigned long long* d_base, con
                     bool v32, uint64_t spec, uint64_t spec_n, uint64_t voff) {
     constexpr int BLOCK = ScatterCfg<T>::BLOCK, ITEMS = ScatterCfg<T>::ITEMS, TILE = BLOCK * ITEMS;
     if (n == 0) return PSACX_OK;
-    const uint64_t ntiles = (n + TILE - 1) / TILE;
-    const unsigned slab_tiles = slab_tiles_for(ntiles);
-    const uint64_t nslabs = (ntiles + slab_tiles - 1) / slab_tiles;
-    unsigned* tile_hist = reinterpret_cast<unsigned*>(scratch + 256);
-    unsigned long long* slab_tot = reinterpret_cast<unsigned long long*>(scratch + 256 + ((ntiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255));
-    PSACX_HIP(c, hipMemsetAsync(scratch, 0, 256, c->stream));
-    hipLaunchKernelGGL((class_tile_hist_kernel<BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, cls, n, tile_hist);
-    hipLaunchKernelGGL(radix_slab_scan_kernel<0>, dim3((unsigned)nslabs), dim3(RADIX), 0, c->stream, tile_hist, ntiles, slab_tot, slab_tiles);
-    hipLaunchKernelGGL(radix_top_scan_kernel<0>, dim3(1), dim3(RADIX), 0, c->stream, slab_tot, nslabs, d_base);
-    const T* dsrc = reinterpret_cast<const T*>(cls);
-    if (sizeof(T) == 8 && v32)
-        hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, true, 1, true, (sizeof(T) == 8 ? 1 : 0), 1>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, k1,
-                           (const T*)nullptr, (const T*)nullptr, k1_out, (T*)nullptr, static_cast<T*>(v_out), n, 0, d_base, tile_hist, slab_tot,
-                           (unsigned long long*)nullptr, spec, spec_n, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(n, true), dsrc, slab_tiles, voff);
-    else
-        hipLaunchKernelGGL((radix_scatter3_kernel<T, BLOCK, ITEMS, true, 1, true, 0, 1>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, k1,
-                           (const T*)nullptr, (const T*)nullptr, k1_out, (T*)nullptr, static_cast<T*>(v_out), n, 0, d_base, tile_hist, slab_tot,
-                           (unsigned long long*)nullptr, spec, spec_n, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(n, true), dsrc, slab_tiles, voff);
+    const PassScratch pl = pass_scratch(scratch, (n + TILE - 1) / TILE);
+    PSACX_HIP(c, hipMemsetAsync(pl.counter, 0, 256, c->stream));
+    hipLaunchKernelGGL((class_tile_hist_kernel<BLOCK, ITEMS>), dim3((unsigned)pl.ntiles), dim3(BLOCK), 0, c->stream, cls, n, pl.tile_hist);
+    launch_pass_scans(c, pl, d_base);
+    const Scatter3Args<T> a{k1, nullptr, nullptr, k1_out, nullptr, static_cast<T*>(v_out), n, 0, d_base, pl, spec, spec_n, sort_chunk_for(n, true),
+                            reinterpret_cast<const T*>(cls), voff, nullptr, 0, 0};
+    if (sizeof(T) == 8 && v32) launch_scatter3<T, BLOCK, ITEMS, true, 1, true, (sizeof(T) == 8 ? 1 : 0), 1>(c, a);
+    else launch_scatter3<T, BLOCK, ITEMS, true, 1, true, 0, 1>(c, a);
     PSACX_HIP(c, hipGetLastError());
     return PSACX_OK;
 }
@@ -860,7 +822,7 @@ int pair_sort(psacx_ctx* c, SortScratch& sc, SortBufs<T> in, SortBufs<T> alt, ui
     int n_exec = 0;
     // look-back form: digit starts scanned on the device, one descriptor region per pass (zeroed by one memset together
     // with the histograms); the host only learns which passes have a constant digit (flags the scan kernel stores into
-    // pinned host memory).  Needs the scratch laid out as carve() lays it out.
+    // pinned host memory).  Needs d_hist, d_base and d_desc back to back, as SortScratch::take lays them out (tested here: a caller may fill one by hand).
     // (2048-record tiles for the small sorts were measured: three times the look-back chain, 0.27 -> 0.29 ms per round at 2^20)
     constexpr uint64_t TILE = ScatterCfg<T>::TILE;
     const bool small_desc = n < (1ull << 30);
@@ -898,11 +860,11 @@ int pair_sort(psacx_ctx* c, SortScratch& sc, SortBufs<T> in, SortBufs<T> alt, ui
                 const int grid = grid_for(c, (n + 3) / 4, 256, 8);
                 hipLaunchKernelGGL((radix_hist_kernel<T, 256>), dim3(grid), dim3(256), 0, c->stream, in.k1, in.k2, n, ha, sc.d_hist);
                 hipLaunchKernelGGL(radix_hist_scan_kernel<0>, dim3(plan.n_pass), dim3(RADIX), 0, c->stream, sc.d_hist, sc.d_base,
-                                   (unsigned long long)n, reinterpret_cast<unsigned*>(c->pinned_dev + 384));
+                                   (unsigned long long)n, reinterpret_cast<unsigned*>(c->pinned_dev + PIN_CONST_DIGITS));
                 PSACX_HIP(c, hipGetLastError());
             }
             PSACX_HIP(c, hipStreamSynchronize(c->stream));
-            const unsigned* constant = reinterpret_cast<const unsigned*>(c->pinned + 384);
+            const unsigned* constant = reinterpret_cast<const unsigned*>(c->pinned + PIN_CONST_DIGITS);
             for (int p = 0; p < plan.n_pass; ++p) { skip[p] = constant[p] != 0; if (!skip[p]) ++n_exec; }
         } else {
             // (the scratch is not laid out for the device-side scan, or the device cannot store into the pinned words: digit starts on the host)
@@ -1028,61 +990,7 @@ constexpr int PSACX_RETRY_1STAGE = 1002;
 #ifndef PSACX_1W_ITEMS
 #define PSACX_1W_ITEMS 8
 #endif
-// Scratch layout of the bucket passes over one-word records.  h_tabs: bucket_off[0 .. 256] filled in (start of every bucket's records;
-// buckets without records own nothing), slab_start[0 .. 256] behind it is written here.
-// group: the group form of onew_bucket_passes may run (onew_group_layout); sub_tiles: rows of the tile tables its sub-bucket passes need (0: none)
-struct OneWordLayout { unsigned slab; uint64_t total_slabs, vtiles; size_t hist_bytes, slab_bytes, tabs_bytes, need; bool group = false; uint64_t sub_tiles = 0; };
-template <int TILE>
-inline OneWordLayout onew_layout(unsigned long long* h_tabs, uint64_t ntiles_hint) {
-    OneWordLayout lay;
-    lay.slab = ntiles_hint >= (1u << 16) ? 64u : 16u;
-    uint64_t total_slabs = 0;
-    for (int d = 0; d < RADIX; ++d) {
-        const uint64_t cnt = h_tabs[d + 1] - h_tabs[d];
-        h_tabs[RADIX + 1 + d] = total_slabs;
-        total_slabs += ((cnt + TILE - 1) / TILE + lay.slab - 1) / lay.slab;
-    }
-    h_tabs[2 * RADIX + 1] = total_slabs;
-    lay.total_slabs = total_slabs;
-    lay.vtiles = total_slabs * lay.slab;
-    lay.hist_bytes = ((size_t)lay.vtiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255;
-    lay.slab_bytes = ((size_t)total_slabs * RADIX * sizeof(unsigned long long) + 255) & ~(size_t)255;
-    lay.tabs_bytes = (2 * (RADIX + 1) * sizeof(unsigned long long) + 64 + total_slabs * sizeof(SlabInfo) + 255) & ~(size_t)255;
-    lay.need = 256 + lay.hist_bytes + lay.slab_bytes + (size_t)RADIX * RADIX * 8 + lay.tabs_bytes;
-    return lay;
-}
-// The group form of the bucket passes (onew_bucket_passes): the upper digits of the rest most significant digit first, the last 16 prefix bits
-// ordered on chip inside the groups that agree in everything above them (radix.hpp: group_sort16_kernel).  It runs for 24 or 32 prefix bits in
-// the word when a group is expected to hold at most half of GROUP_CAP records (texts of 2^22 .. 2^24 and of 2^30 .. 2^32 characters), and when the
-// scratch has room for its tables behind those of the 256-bucket form: a word for the largest group, and at 32 bits the tables of the 65 536
-// sub-buckets (radix.hpp: OneWordTabs) -- their starts, first tiles, the sub-bucket of every tile, a row of zeros, the 2^24 group starts -- and
-// tile histograms of n / tile + 65 536 rows.  Returns `lay` with the form switched on, or `lay` as it is.
-constexpr unsigned ONEW_SUB = RADIX * RADIX;
-struct OneWordGroupScratch { size_t max_word, zero_row, sub_off, first_tile, tile_sub, group_base, end; };
-inline OneWordGroupScratch onew_group_scratch(const OneWordLayout& lay) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    OneWordGroupScratch g;
-    g.max_word = 256 + lay.hist_bytes + lay.slab_bytes + (size_t)RADIX * RADIX * 8 + lay.tabs_bytes;
-    g.zero_row = g.max_word + 256;
-    g.sub_off = g.zero_row + (size_t)RADIX * 8;
-    g.first_tile = lay.sub_tiles ? g.sub_off + up((size_t)(ONEW_SUB + 1) * 8) : g.sub_off;
-    g.tile_sub = lay.sub_tiles ? g.first_tile + up((size_t)(ONEW_SUB + 1) * 4) : g.sub_off;
-    g.group_base = lay.sub_tiles ? g.tile_sub + up((size_t)lay.sub_tiles * 4) : g.sub_off;
-    g.end = lay.sub_tiles ? g.group_base + (size_t)ONEW_SUB * RADIX * 8 : g.sub_off;
-    return g;
-}
-template <int TILE>
-inline OneWordLayout onew_group_layout(OneWordLayout lay, uint64_t nrec, unsigned low, size_t scratch_bytes) {
-    if ((low != 24 && low != 32) || (nrec >> (low - 16 + 8)) > (uint64_t)GROUP_CAP / 2) return lay;
-    OneWordLayout g = lay;
-    g.group = true;
-    if (low == 32) {
-        g.sub_tiles = nrec / TILE + ONEW_SUB;            // (every sub-bucket owns ceil(size / tile) tiles)
-        g.hist_bytes = std::max(lay.hist_bytes, ((size_t)g.sub_tiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255);
-    }
-    g.need = onew_group_scratch(g).end;
-    return (g.need > scratch_bytes || g.sub_tiles >= (1ull << 31)) ? lay : g;
-}
+// (the scratch of the bucket passes -- OneWordLayout, onew_layout, onew_group_layout -- is laid out in sort_scratch.hpp)
 // The LSD passes inside the buckets: one-word records (rest of the prefix << sfield | suffix) of bucket b at [bucket_off[b], bucket_off[b + 1]) of `cur`,
 // `low` prefix bits in the word.  All but the last pass ping-pong between cur and oth; the last one writes word 1 ((b << low | rest) << lo1) into the
 // array it does not read (*s1 tells which) and the suffixes as words into sa_out.  h_tabs must stay untouched until the stream has passed the copy.
@@ -1098,13 +1006,13 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
     // in_pad: in the input of the FIRST pass the records of bucket b lie b * in_pad places further than bucket_off says (prefix_sort_1w)
     // h_word (pinned, with lay.group, view_out, dig and tie_bytes): the group form runs (onew_group_layout) and reads the largest group back here
     constexpr int BLOCK = 512, ITEMS_B = PSACX_1W_ITEMS, TILE = BLOCK * ITEMS_B;
-    unsigned* tile_hist = reinterpret_cast<unsigned*>(scratch + 256);
-    unsigned long long* slab_tot = reinterpret_cast<unsigned long long*>(scratch + 256 + lay.hist_bytes);
-    unsigned long long* base2 = reinterpret_cast<unsigned long long*>(scratch + 256 + lay.hist_bytes + lay.slab_bytes);
-    unsigned long long* d_tabs = base2 + (size_t)RADIX * RADIX;
+    unsigned* tile_hist = reinterpret_cast<unsigned*>(scratch + lay.tile_hist);
+    unsigned long long* slab_tot = reinterpret_cast<unsigned long long*>(scratch + lay.slab_tot);
+    unsigned long long* base2 = reinterpret_cast<unsigned long long*>(scratch + lay.base2);
+    unsigned long long* d_tabs = reinterpret_cast<unsigned long long*>(scratch + lay.tabs);
     OneWordTabs tb;
     tb.bucket_off = d_tabs; tb.slab_start = d_tabs + RADIX + 1; tb.slab = lay.slab;
-    SlabInfo* slab_info = reinterpret_cast<SlabInfo*>((reinterpret_cast<uintptr_t>(d_tabs + 2 * (RADIX + 1)) + 31) & ~(uintptr_t)31);
+    SlabInfo* slab_info = reinterpret_cast<SlabInfo*>(scratch + lay.slab_info);
     tb.slab_info = slab_info;
     *s1 = cur;
     if (view_out) { view_out->off = d_tabs; view_out->low = low; view_out->sfield = sfield; view_out->lo1 = lo1; }
@@ -1172,17 +1080,16 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
     // digit starts are the starts of the 65 536 sub-buckets, then the tables of the sub-buckets from them -- the pass on the digit above the last 16 bits
     // inside these, and the groups it leaves ordered on chip.  The largest group is known from the tables of that pass, before its scatter runs: with one
     // longer than GROUP_CAP the digits left are sorted LSD inside the partition there is (at 24 bits: the passes above, as if nothing had happened).
-    const OneWordGroupScratch gs = onew_group_scratch(lay);
-    unsigned long long* const max_word = reinterpret_cast<unsigned long long*>(scratch + gs.max_word);
+    unsigned long long* const max_word = reinterpret_cast<unsigned long long*>(scratch + lay.max_word);
     const int mid_shift = (int)sfield + 2 * RADIX_BITS;
     OneWordTabs tg = tb;
     unsigned long long* gbase = base2;
     uint64_t ngroups = (uint64_t)RADIX * RADIX;
     if (low == 32) {
-        unsigned long long* const sub_off = reinterpret_cast<unsigned long long*>(scratch + gs.sub_off);
-        unsigned long long* const zero_row = reinterpret_cast<unsigned long long*>(scratch + gs.zero_row);
-        unsigned* const first_tile = reinterpret_cast<unsigned*>(scratch + gs.first_tile);
-        unsigned* const tile_sub = reinterpret_cast<unsigned*>(scratch + gs.tile_sub);
+        unsigned long long* const sub_off = reinterpret_cast<unsigned long long*>(scratch + lay.sub_off);
+        unsigned long long* const zero_row = reinterpret_cast<unsigned long long*>(scratch + lay.zero_row);
+        unsigned* const first_tile = reinterpret_cast<unsigned*>(scratch + lay.first_tile);
+        unsigned* const tile_sub = reinterpret_cast<unsigned*>(scratch + lay.tile_sub);
         tables(tb, mid_shift + RADIX_BITS, false, sub_off);
         PSACX_HIP(c, hipGetLastError());
         PSACX_TRY(scatter(tb, mid_shift + RADIX_BITS, false, sub_off, dig, mid_shift));
@@ -1196,7 +1103,7 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
             PSACX_HIP(c, hipGetLastError());
         }
         tg.bucket_off = sub_off; tg.tile_sub = tile_sub; tg.first_tile = first_tile; tg.zero_row = zero_row;
-        gbase = reinterpret_cast<unsigned long long*>(scratch + gs.group_base);
+        gbase = reinterpret_cast<unsigned long long*>(scratch + lay.group_base);
         ngroups = (uint64_t)ONEW_SUB * RADIX;
         tables(tg, mid_shift, true, gbase);
     } else
@@ -1242,10 +1149,7 @@ inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t*
     const unsigned sfield = 64 - low;                  // the payload field takes the rest (32 bits when lead = 40)
     const uint64_t ntiles = (n + TILE0 - 1) / TILE0;
     char* const scratch = sc.d_desc;
-    const unsigned slab0 = slab_tiles_for(ntiles);
-    const uint64_t nslabs0 = (ntiles + slab0 - 1) / slab0;
-    unsigned* tile_hist0 = reinterpret_cast<unsigned*>(scratch + 256);
-    unsigned long long* slab_tot0 = reinterpret_cast<unsigned long long*>(scratch + 256 + ((ntiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255));
+    const PassScratch p0 = pass_scratch(scratch, ntiles);          // the pass on the top digit
     unsigned long long* base0 = sc.d_base;
     {
         // a text that repeats itself massively (every sampled prefix seen before) keeps the two-array passes: see prefix_dup_probe_kernel
@@ -1266,35 +1170,34 @@ inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t*
         }
         // (persistent waves, a tile each per trip, five workgroups of 256 per CU -- 82 VGPRs: five waves per SIMD; four measured the same: sa_kernels.hpp; PSACX_OPT_PLAIN_SIDE_KERNELS pins the workgroup-per-tile form)
         static_assert(TILE0 == 64 * WAVE, "top_digit_hist_waves_kernel: a wave takes a tile of 64 records per lane");
-        if (c->knobs.plain_side_kernels || (reinterpret_cast<uintptr_t>(tile_hist0) & 15u))
-            hipLaunchKernelGGL((top_digit_hist_kernel<uint64_t, BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, text, n, n_text, tab, ks, tile_hist0);
+        if (c->knobs.plain_side_kernels || (reinterpret_cast<uintptr_t>(p0.tile_hist) & 15u))
+            hipLaunchKernelGGL((top_digit_hist_kernel<uint64_t, BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, text, n, n_text, tab, ks, p0.tile_hist);
         else
             hipLaunchKernelGGL((top_digit_hist_waves_kernel<256>), dim3((unsigned)grid_for(c, ntiles * WAVE, 256, 5)), dim3(256), 0, c->stream, text, n, n_text, tab, ks,
-                               ntiles, tile_hist0);
+                               ntiles, p0.tile_hist);
         PSACX_HIP(c, hipGetLastError());
     }
     {
         ProfScope ps(c, TC_SORT_TILEHIST);
-        hipLaunchKernelGGL(radix_slab_scan_kernel<0>, dim3((unsigned)nslabs0), dim3(RADIX), 0, c->stream, tile_hist0, ntiles, slab_tot0, slab0);
-        hipLaunchKernelGGL(radix_top_scan_kernel<0>, dim3(1), dim3(RADIX), 0, c->stream, slab_tot0, nslabs0, base0);
+        launch_pass_scans(c, p0, base0);
         PSACX_HIP(c, hipGetLastError());
     }
     PSACX_HIP(c, hipMemcpyAsync(sc.h_base, base0, RADIX * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
     // tables of the buckets: every bucket owns whole slabs of tiles (radix.hpp: OneWordTabs)
-    unsigned long long* h_tabs = sc.h_base + RADIX;             // pinned: bucket_off[257], slab_start[257]
+    unsigned long long* h_tabs = sc.h_base + (PIN_TABS - PIN_BASE) / sizeof(unsigned long long);             // pinned: bucket_off[257], slab_start[257]
     for (int d = 0; d < RADIX; ++d) h_tabs[d] = sc.h_base[d];
     h_tabs[RADIX] = n;
     OneWordLayout lay = onew_layout<TILE>(h_tabs, ntiles);
     if (lay.need > sc.desc_bytes || lay.vtiles >= (1ull << 31)) return PSACX_RETRY_1W;
     // (the group form where its tables fit too; PSACX_OPT_LSD_BUCKET_PASSES pins the LSD passes)
     if (view_out && dig && tie_bytes && !c->knobs.lsd_bucket_passes) lay = onew_group_layout<TILE>(lay, n, low, sc.desc_bytes);
-    unsigned long long* const h_word = sc.h_base + 4 * RADIX;          // (pinned, behind h_tabs)
+    unsigned long long* const h_word = sc.h_base + (PIN_GROUP_WORD - PIN_BASE) / sizeof(unsigned long long);          // (pinned, behind h_tabs)
     {
         ProfScope ps(c, TC_KMER);           // (key generation and the partition by the top digit in one kernel: timed with the keys)
         PSACX_HIP(c, hipMemsetAsync(scratch, 0, 256, c->stream));
         hipLaunchKernelGGL((key_scatter1w_kernel<BLOCK, ITEMS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, c->stream, text, n, n_text, tab, ks, pad ? k0 : a, (int)(lo1 + low),
-                           base0, tile_hist0, slab_tot0, reinterpret_cast<unsigned*>(scratch), sort_chunk_for(n, true), slab0, lo1 | (sfield << 16), (uint64_t)0,
+                           base0, p0.tile_hist, p0.slab_tot, p0.counter, sort_chunk_for(n, true), p0.slab_tiles, lo1 | (sfield << 16), (uint64_t)0,
                            (uint8_t*)nullptr, 0, pad);  // (no digit bytes out of this pass: their stores cost it 4.9 ms -- also at the padded places -- and save the first bucket pass's histogram 4.6)
         PSACX_HIP(c, hipGetLastError());
     }

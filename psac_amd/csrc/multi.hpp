@@ -447,7 +447,7 @@ struct MultiRun {
                 MG_HIP(g, hipMalloc((void**)&R.d_scal, R.scal_words * 8));
             }
             MG_OP(g, R.ctx, ensure_pinned(R.ctx, (size_t)(P + 1) * k * 8 + 65536));
-            uint64_t* h = reinterpret_cast<uint64_t*>(R.ctx->pinned + 32768);
+            uint64_t* h = reinterpret_cast<uint64_t*>(R.ctx->pinned + PIN_MULTI);
             std::memcpy(h, mine[i].data(), (size_t)k * 8);
             MG_HIP(g, hipMemcpyAsync(R.d_scal, h, (size_t)k * 8, hipMemcpyHostToDevice, R.ctx->stream));
         }
@@ -466,7 +466,7 @@ struct MultiRun {
         for (int i = 0; i < L; ++i) {
             MRank& R = g->R[i];
             MG_HIP(g, hipSetDevice(R.ctx->device));
-            uint64_t* h = reinterpret_cast<uint64_t*>(R.ctx->pinned + 32768);
+            uint64_t* h = reinterpret_cast<uint64_t*>(R.ctx->pinned + PIN_MULTI);
             MG_HIP(g, hipMemcpyAsync(h + k, R.d_scal + k, (size_t)P * k * 8, hipMemcpyDeviceToHost, R.ctx->stream));
             MG_HIP(g, hipStreamSynchronize(R.ctx->stream));
             if (i == 0) std::memcpy(all.data(), h + k, (size_t)P * k * 8);
@@ -850,7 +850,7 @@ struct MultiRun {
         const size_t k = idx.size();
         MG_OP(g, c, ensure_pinned(c, 2 * k * 8 + 65536));
         DBuf<uint64_t> d; MG_OP(g, c, d.alloc(c, 2 * k));
-        uint64_t* h = reinterpret_cast<uint64_t*>(c->pinned + 32768);
+        uint64_t* h = reinterpret_cast<uint64_t*>(c->pinned + PIN_MULTI);
         std::memcpy(h, idx.data(), k * 8);
         MG_HIP(g, hipMemcpyAsync(d.p, h, k * 8, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL((gather_at_kernel<T>), dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, a, d.p, (unsigned)k, d.p + k);
@@ -903,9 +903,9 @@ struct MultiRun {
         hipLaunchKernelGGL((tie_resolve_kernel<T, TB_, TI_, TG_, true>), dim3((unsigned)nb), dim3(TB_), 0, c->stream, rec.k1.p, rec.v.p, rec.k2.p,
                            rec.cnt, lo1, (const uint8_t*)nullptr, (uint64_t)0, tab, ks, big.p);
         MG_HIP(g, hipGetLastError());
-        MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, big.p, 8, hipMemcpyDeviceToHost, c->stream));
+        MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, big.p, 8, hipMemcpyDeviceToHost, c->stream));
         MG_HIP(g, hipStreamSynchronize(c->stream));
-        if (*reinterpret_cast<unsigned long long*>(c->pinned + 32768)) return local_sort(i, rec, bits1, bits2);
+        if (*reinterpret_cast<unsigned long long*>(c->pinned + PIN_MULTI)) return local_sort(i, rec, bits1, bits2);
         return PSACX_OK;
     }
 
@@ -1090,21 +1090,16 @@ struct MultiRun {
         bounds.assign(P + 1, cnt);
         bounds[0] = 0;
         if (cnt == 0) return PSACX_OK;
-        MG_OP(g, c, ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+        MG_OP(g, c, ensure_pinned(c, PINNED_SORT_BYTES + 65536 + 32768));
         SortScratch sc;
         T* cls = nullptr;
-        auto layout = [&](Arena& a) {
-            cls = a.take<T>(cnt);
-            sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-            sc.desc_bytes = sort_desc_bytes(cnt);
-            sc.d_desc = a.take<char>(sc.desc_bytes);
-        };
+        auto layout = [&](Arena& a) { cls = a.take<T>(cnt); sc.take(a, cnt, /*base_desc_only=*/true); };
         { Arena dry(nullptr); layout(dry); MG_OP(g, c, ensure_slab(c, dry.off + 4096)); }
         Arena ar(c->slab);
         layout(ar);
         MG_OP(g, c, psacx_op_owners(c, gidx, cnt, n, (uint32_t)P, cls));
         SortBufs<T> in{const_cast<T*>(gidx), nullptr, const_cast<T*>(payload)}, o{out.k2.p, nullptr, out.v.p};
-        unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
+        unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + PIN_HIST);
         MG_OP(g, c, class_partition<T>(c, sc, in, o, cls, cnt, starts));
         for (int d = 0; d < P; ++d) bounds[d] = starts[d];
         return PSACX_OK;
@@ -1117,18 +1112,13 @@ struct MultiRun {
         bounds.assign(P + 1, cnt);
         bounds[0] = 0;
         if (cnt == 0) return PSACX_OK;
-        MG_OP(g, c, ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+        MG_OP(g, c, ensure_pinned(c, PINNED_SORT_BYTES + 65536 + 32768));
         SortScratch sc;
-        auto layout = [&](Arena& a) {
-            sc.d_base = a.take<unsigned long long>((size_t)MAX_PASSES * RADIX);
-            sc.desc_bytes = sort_desc_bytes(cnt);
-            sc.d_desc = a.take<char>(sc.desc_bytes);
-        };
-        { Arena dry(nullptr); layout(dry); MG_OP(g, c, ensure_slab(c, dry.off + 4096)); }
+        { Arena dry(nullptr); sc.take(dry, cnt, /*base_desc_only=*/true); MG_OP(g, c, ensure_slab(c, dry.off + 4096)); }
         Arena ar(c->slab);
-        layout(ar);
+        sc.take(ar, cnt, /*base_desc_only=*/true);
         SortBufs<T> in{const_cast<T*>(key), nullptr, const_cast<T*>(payload)}, o{out.k2.p, nullptr, out.v.p};
-        unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + 1024);
+        unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + PIN_HIST);
         MG_OP(g, c, class_partition<T>(c, sc, in, o, cls, cnt, starts));
         for (int d = 0; d <= P; ++d) bounds[d] = starts[d];       // bounds[P]: start of class P ("to nobody"), cnt if there is none
         return PSACX_OK;
@@ -1221,9 +1211,9 @@ struct MultiRun {
                 hipLaunchKernelGGL((slice_hist_kernel<T>), dim3(grid_for(c, S[i].m, 512, 8)), dim3(512), 0, c->stream, (const T*)S[i].SA, S[i].m, map, d_cnt[i].p);
                 MG_HIP(g, hipGetLastError());
             }
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, d_cnt[i].p, (size_t)C * 8, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, d_cnt[i].p, (size_t)C * 8, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
-            std::memcpy(counts[i].data(), c->pinned + 32768, (size_t)C * 8);
+            std::memcpy(counts[i].data(), c->pinned + PIN_MULTI, (size_t)C * 8);
             return PSACX_OK;
         }));
         std::vector<uint64_t> table;
@@ -1293,9 +1283,9 @@ struct MultiRun {
             if (rc_a != PSACX_OK) return rc_a;
             if (!m) return PSACX_OK;
             MG_HIP(g, hipSetDevice(c->device));
-            std::memset(c->pinned + 32768, 0, SLICE_MAX_CLASSES * 8);
-            std::memcpy(c->pinned + 32768, cstart[i].data(), (size_t)C * 8);
-            MG_HIP(g, hipMemcpyAsync(d_cnt[i].p, c->pinned + 32768, SLICE_MAX_CLASSES * 8, hipMemcpyHostToDevice, c->stream));
+            std::memset(c->pinned + PIN_MULTI, 0, SLICE_MAX_CLASSES * 8);
+            std::memcpy(c->pinned + PIN_MULTI, cstart[i].data(), (size_t)C * 8);
+            MG_HIP(g, hipMemcpyAsync(d_cnt[i].p, c->pinned + PIN_MULTI, SLICE_MAX_CLASSES * 8, hipMemcpyHostToDevice, c->stream));
             if (pack || wpack)
                 hipLaunchKernelGGL((slice_partition_packed_kernel<T, PB, 8>), dim3((unsigned)((m + PB * 8 - 1) / (PB * 8))), dim3(PB), 0, c->stream, (const T*)S[i].SA,
                                    ids_in_isa ? (const T*)S[i].ISA : (const T*)S[i].Bsa.p, m, map, d_cnt[i].p,
@@ -1521,9 +1511,9 @@ struct MultiRun {
         unsigned long long* d = reinterpret_cast<unsigned long long*>(lcp_pyr_mem_[i].p + (lcp_pyr_mem_[i].n - 64));      // 64 spare entries at the end
         hipLaunchKernelGGL((top_min_kernel<T>), dim3(1), dim3(256), 0, c->stream, Pm.lvl[Pm.nlev - 1], Pm.len[Pm.nlev - 1], d);
         MG_HIP(g, hipGetLastError());
-        MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, d, 8, hipMemcpyDeviceToHost, c->stream));
+        MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, d, 8, hipMemcpyDeviceToHost, c->stream));
         MG_HIP(g, hipStreamSynchronize(c->stream));
-        *block_min = *reinterpret_cast<uint64_t*>(c->pinned + 32768);
+        *block_min = *reinterpret_cast<uint64_t*>(c->pinned + PIN_MULTI);
         return PSACX_OK;
     }
     // the pyramid of rank i's LCP block if the run keeps one (else one of level 0 only): for the kernels that lower LCP entries
@@ -1652,9 +1642,9 @@ struct MultiRun {
             MG_HIP(g, hipSetDevice(c->device));
             hipLaunchKernelGGL((upper_bound_kernel<T>), dim3(1), dim3(1), 0, c->stream, S[i].Bsa.p, m, id[0], d.p);
             MG_HIP(g, hipGetLastError());
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, d.p, 8, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, d.p, 8, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
-            lead = std::min<uint64_t>(*reinterpret_cast<uint64_t*>(c->pinned + 32768), a);
+            lead = std::min<uint64_t>(*reinterpret_cast<uint64_t*>(c->pinned + PIN_MULTI), a);
         }
         // a bucket that covers this whole block would need three ranks' pieces in one step: the round then runs unsliced
         if (lead == a && p[steps] == m - 1 && P > 1) *whole = 1;
@@ -1689,7 +1679,7 @@ struct MultiRun {
             S[i].SA = d_sa[i]; S[i].ISA = d_isa[i]; S[i].LCP = want_lcp ? d_lcp[i] : nullptr;
             S[i].out_cap = m_local[i] + g->out_slack; S[i].out_busy = false;
             S[i].c->pool_peak = S[i].c->pool_live;
-            MG_OP(g, S[i].c, ensure_pinned(S[i].c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+            MG_OP(g, S[i].c, ensure_pinned(S[i].c, PINNED_SORT_BYTES + 65536 + 32768));
             return PSACX_OK;
         }));
         diet = false; slab_cap = 0; first_round_ = true;
@@ -1713,10 +1703,10 @@ struct MultiRun {
                 psacx_ctx* c = ctx(i);
                 DBuf<uint64_t> h; MG_OP(g, c, h.alloc(c, 256));
                 MG_OP(g, c, psacx_op_char_hist(c, text[i], S[i].m, h.p));
-                MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, h.p, 256 * 8, hipMemcpyDeviceToHost, c->stream));
+                MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, h.p, 256 * 8, hipMemcpyDeviceToHost, c->stream));
                 MG_HIP(g, hipStreamSynchronize(c->stream));
                 mine[i][0] = S[i].m;
-                std::memcpy(&mine[i][1], c->pinned + 32768, 256 * 8);
+                std::memcpy(&mine[i][1], c->pinned + PIN_MULTI, 256 * 8);
                 return PSACX_OK;
             }));
             std::vector<uint64_t> all;

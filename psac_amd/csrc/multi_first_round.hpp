@@ -168,9 +168,9 @@ int MultiRun<T>::sort_first_two_word(std::vector<Rec<T>>& rec, const std::vector
                 MG_HIP(g, hipGetLastError());
             }
             MG_OP(g, c, ensure_pinned(c, 64 * 8 + 65536 + 32768));
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, d_counts.p, 64 * 8, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, d_counts.p, 64 * 8, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
-            const unsigned long long* h = reinterpret_cast<const unsigned long long*>(c->pinned + 32768);
+            const unsigned long long* h = reinterpret_cast<const unsigned long long*>(c->pinned + PIN_MULTI);
             for (int cc = 0; cc < NC; ++cc) cnt_c[i][cc] = h[cc];
             return PSACX_OK;
         }));
@@ -329,9 +329,9 @@ int MultiRun<T>::first_sort_ties(std::vector<Rec<T>>& rec, const std::vector<uin
             hipLaunchKernelGGL((tie_resolve_kernel<T, TB, TI, TG>), dim3((unsigned)nb), dim3(TB), 0, c->stream, rec[i].k1.p, rec[i].v.p, rec[i].k2.p, rec[i].cnt, lo1,
                                (const uint8_t*)tbuf[i].p, S[i].m + two_k, tab, ks, big.p, solo_packed);
             MG_HIP(g, hipGetLastError());
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, big.p, 8, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, big.p, 8, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
-            if (*reinterpret_cast<unsigned long long*>(c->pinned + 32768)) general_ties = true;
+            if (*reinterpret_cast<unsigned long long*>(c->pinned + PIN_MULTI)) general_ties = true;
         }
         if (general_ties) MG_OP(g, c, op_compact_ties<T>(c, rec[i].k1.p, rec[i].v.p, rec[i].cnt, lo1, (T*)nullptr, (T*)nullptr, (T*)nullptr, &ties[i]));
         return PSACX_OK;
@@ -359,7 +359,7 @@ int MultiRun<T>::first_sort_ties(std::vector<Rec<T>>& rec, const std::vector<uin
             if (at[i] >= cnt) return PSACX_OK;
             if (cnt - at[i] > cap) {
                 DBuf<unsigned long long> cut; MG_OP(g, c, cut.alloc(c, 2));
-                unsigned long long* h = reinterpret_cast<unsigned long long*>(c->pinned + 32768);
+                unsigned long long* h = reinterpret_cast<unsigned long long*>(c->pinned + PIN_MULTI);
                 MG_HIP(g, hipSetDevice(c->device));
                 auto ask = [&](uint64_t lo, uint64_t hi) -> int {
                     h[0] = 0; h[1] = ~0ull;
@@ -405,11 +405,11 @@ int MultiRun<T>::first_sort_ties(std::vector<Rec<T>>& rec, const std::vector<uin
             hipLaunchKernelGGL((tie_resolve_kernel<T, TB_, TI_, TG_, true>), dim3((unsigned)nb), dim3(TB_), 0, c->stream, w1[i].p, tv[i].p, w2[i].p, n_t, lo1,
                                (const uint8_t*)nullptr, (uint64_t)0, tab, ks, big.p);
             MG_HIP(g, hipGetLastError());
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, big.p, 8, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, big.p, 8, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
             const T *s1 = w1[i].p, *s2 = w2[i].p, *sv = tv[i].p;
             DBuf<T> b1, b2, bv;
-            if (*reinterpret_cast<unsigned long long*>(c->pinned + 32768)) {
+            if (*reinterpret_cast<unsigned long long*>(c->pinned + PIN_MULTI)) {
                 // some group is long (repetitive text): a stable sort of all tied records by the full window; the groups come in
                 // ascending order of their prefix, so the sorted records go back to the same positions in order
                 tk1[i].release();                                    // (word 1 of the ties came back with the windows)
@@ -481,7 +481,7 @@ int MultiRun<T>::sort_first_one_word(std::vector<Rec<T>>& rec, const std::vector
     // ---- 1. top digits of every block
     std::vector<uint64_t> nrec(L), short_n(L);
     std::vector<std::vector<uint64_t>> mine(L, std::vector<uint64_t>(RADIX + 2 + TAILB / 8, 0));
-    struct Scr { unsigned long long* base0; char* desc; unsigned* tile_hist0; unsigned long long* slab_tot0; uint64_t ntiles; unsigned slab0; size_t desc_bytes; };
+    struct Scr { unsigned long long* base0; char* desc; PassScratch p0; size_t desc_bytes; };          // p0: the pass on the top digit
     std::vector<Scr> scr(L);
     PSACX_TRY(par([&](int i) -> int {
         psacx_ctx* c = ctx(i);
@@ -489,26 +489,19 @@ int MultiRun<T>::sort_first_one_word(std::vector<Rec<T>>& rec, const std::vector
         short_n[i] = solo_ ? 0 : std::min<uint64_t>(m, end > first_short ? end - first_short : 0);
         nrec[i] = m - short_n[i];
         Scr& q = scr[i];
-        q.ntiles = (nrec[i] + TILE0 - 1) / TILE0;
-        q.slab0 = slab_tiles_for(q.ntiles);
-        // the scratch of the bucket passes on the receiving side lives in the same slab: sized now for the largest share a rank may accept
-        const uint64_t cap_rec = m + m / 8 + 256 + (uint64_t)TILE;
-        const uint64_t vt_ub = (cap_rec + TILE - 1) / TILE + (uint64_t)RADIX * 64 + 64;
-        const size_t need_b = 256 + (((size_t)vt_ub * RADIX * sizeof(unsigned) + 255) & ~(size_t)255) + (((size_t)(vt_ub / 16 + RADIX) * RADIX * 8 + 255) & ~(size_t)255) +
-                              (size_t)RADIX * RADIX * 8 + 2 * (RADIX + 1) * 8 + 64 + (size_t)(vt_ub / 16 + RADIX) * sizeof(SlabInfo) + 4096;
+        const uint64_t ntiles0 = (nrec[i] + TILE0 - 1) / TILE0;
         const uint64_t stride = std::max<uint64_t>(64, m >> 20), samples = m / stride;
         uint64_t slots = 1; while (slots < 4 * samples) slots <<= 1;
-        const size_t need_a = 256 + std::max<size_t>((((size_t)q.ntiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255) + (q.ntiles / q.slab0 + 2) * RADIX * 8, slots * 8) + 4096;
-        q.desc_bytes = std::max(need_a, need_b);
+        // the scratch of the bucket passes on the receiving side lives in the same slab: sized now for the largest share a rank may accept (sort_scratch.hpp)
+        q.desc_bytes = std::max(multi_top_digit_bound(ntiles0, slots), multi_bucket_bound<TILE>(m));
         MG_OP(g, c, ensure_slab(c, q.desc_bytes + (size_t)RADIX * 8 + 8192));
-        MG_OP(g, c, ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+        MG_OP(g, c, ensure_pinned(c, PINNED_SORT_BYTES + 65536 + 32768));
         Arena ar(c->slab);
         q.base0 = ar.take<unsigned long long>((size_t)RADIX);
         q.desc = ar.take<char>(q.desc_bytes);
-        q.tile_hist0 = reinterpret_cast<unsigned*>(q.desc + 256);
-        q.slab_tot0 = reinterpret_cast<unsigned long long*>(q.desc + 256 + (((size_t)q.ntiles * RADIX * sizeof(unsigned) + 255) & ~(size_t)255));
+        q.p0 = pass_scratch(q.desc, ntiles0);
         MG_HIP(g, hipSetDevice(c->device));
-        unsigned long long* h = reinterpret_cast<unsigned long long*>(c->pinned + 32768);
+        unsigned long long* h = reinterpret_cast<unsigned long long*>(c->pinned + PIN_MULTI);
         h[RADIX] = 0; h[RADIX + 1] = 0;
         if (samples >= 1024 && !ties_ok) {
             // does the block repeat itself massively?  (prefix_dup_probe_kernel, sa_kernels.hpp: such a text keeps the two-word path)
@@ -522,12 +515,10 @@ int MultiRun<T>::sort_first_one_word(std::vector<Rec<T>>& rec, const std::vector
             MG_HIP(g, hipStreamSynchronize(c->stream));
             h[RADIX + 1] = samples;
         }
-        if (q.ntiles) {
-            hipLaunchKernelGGL((top_digit_hist_kernel<uint64_t, BLOCK, ITEMS>), dim3((unsigned)q.ntiles), dim3(BLOCK), 0, c->stream, (const uint8_t*)tbuf[i].p, solo_ ? m : nrec[i],
-                               m + two_k, tab, ks0, q.tile_hist0);
-            const uint64_t nslabs0 = (q.ntiles + q.slab0 - 1) / q.slab0;
-            hipLaunchKernelGGL(radix_slab_scan_kernel<0>, dim3((unsigned)nslabs0), dim3(RADIX), 0, c->stream, q.tile_hist0, q.ntiles, q.slab_tot0, q.slab0);
-            hipLaunchKernelGGL(radix_top_scan_kernel<0>, dim3(1), dim3(RADIX), 0, c->stream, q.slab_tot0, nslabs0, q.base0);
+        if (q.p0.ntiles) {
+            hipLaunchKernelGGL((top_digit_hist_kernel<uint64_t, BLOCK, ITEMS>), dim3((unsigned)q.p0.ntiles), dim3(BLOCK), 0, c->stream, (const uint8_t*)tbuf[i].p, solo_ ? m : nrec[i],
+                               m + two_k, tab, ks0, q.p0.tile_hist);
+            launch_pass_scans(c, q.p0, q.base0);
             MG_HIP(g, hipGetLastError());
             MG_HIP(g, hipMemcpyAsync(h, q.base0, RADIX * 8, hipMemcpyDeviceToHost, c->stream));
         } else std::memset(h, 0, RADIX * 8);
@@ -616,13 +607,13 @@ int MultiRun<T>::sort_first_one_word(std::vector<Rec<T>>& rec, const std::vector
     PSACX_TRY(par([&](int i) -> int {
         psacx_ctx* c = ctx(i);
         Scr& q = scr[i];
-        if (!q.ntiles) return PSACX_OK;
+        if (!q.p0.ntiles) return PSACX_OK;
         MG_HIP(g, hipSetDevice(c->device));
         MG_HIP(g, hipMemsetAsync(q.desc, 0, 256, c->stream));
         const uint64_t cnt = solo_ ? S[i].m : nrec[i];
-        hipLaunchKernelGGL((key_scatter1w_kernel<BLOCK, ITEMS>), dim3((unsigned)q.ntiles), dim3(BLOCK), 0, c->stream, (const uint8_t*)tbuf[i].p, cnt, S[i].m + two_k, tab, ks0,
-                           reinterpret_cast<uint64_t*>(solo_ ? A[i].p : grp[i].p), (int)(lo1 + low), q.base0, q.tile_hist0, q.slab_tot0, reinterpret_cast<unsigned*>(q.desc),
-                           sort_chunk_for(cnt, true), q.slab0, lo1 | (sfield << 16), solo_ ? (uint64_t)0 : S[i].off);
+        hipLaunchKernelGGL((key_scatter1w_kernel<BLOCK, ITEMS>), dim3((unsigned)q.p0.ntiles), dim3(BLOCK), 0, c->stream, (const uint8_t*)tbuf[i].p, cnt, S[i].m + two_k, tab, ks0,
+                           reinterpret_cast<uint64_t*>(solo_ ? A[i].p : grp[i].p), (int)(lo1 + low), q.base0, q.p0.tile_hist, q.p0.slab_tot, q.p0.counter,
+                           sort_chunk_for(cnt, true), q.p0.slab_tiles, lo1 | (sfield << 16), solo_ ? (uint64_t)0 : S[i].off);
         MG_HIP(g, hipGetLastError());
         return PSACX_OK;
     }));

@@ -37,9 +37,9 @@ int MultiRun<T>::ansv_pyramid(int i, const T* block, uint64_t m, Pyramid<T>& Pm,
     unsigned long long* d = reinterpret_cast<unsigned long long*>(mem.p + at);
     hipLaunchKernelGGL((top_min_kernel<T>), dim3(1), dim3(256), 0, c->stream, Pm.lvl[Pm.nlev - 1], Pm.len[Pm.nlev - 1], d);
     MG_HIP(g, hipGetLastError());
-    MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, d, 8, hipMemcpyDeviceToHost, c->stream));
+    MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, d, 8, hipMemcpyDeviceToHost, c->stream));
     MG_HIP(g, hipStreamSynchronize(c->stream));
-    *block_min = *reinterpret_cast<uint64_t*>(c->pinned + 32768);
+    *block_min = *reinterpret_cast<uint64_t*>(c->pinned + PIN_MULTI);
     return PSACX_OK;
 }
 
@@ -144,7 +144,7 @@ int MultiRun<T>::ansv(const std::vector<const T*>& block, const std::vector<uint
     A.block = block; A.m = m_local; A.pyr.resize(L); A.pyr_mem.resize(L);
     PSACX_TRY(par([&](int i) -> int {
         S[i].c = ctx(i); S[i].r = rank(i); S[i].m = m_local[i];
-        MG_OP(g, S[i].c, ensure_pinned(S[i].c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+        MG_OP(g, S[i].c, ensure_pinned(S[i].c, PINNED_SORT_BYTES + 65536 + 32768));
         return PSACX_OK;
     }));
     {
@@ -250,7 +250,7 @@ int MultiRun<T>::left_chars(const std::vector<const uint8_t*>& text, const std::
     PSACX_TRY(par([&](int i) -> int {
         S[i].c = ctx(i); S[i].r = rank(i); S[i].m = m_local[i]; S[i].text = text[i];
         S[i].SA = d_sa[i]; S[i].ISA = nullptr; S[i].LCP = d_lcp[i];
-        MG_OP(g, S[i].c, ensure_pinned(S[i].c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+        MG_OP(g, S[i].c, ensure_pinned(S[i].c, PINNED_SORT_BYTES + 65536 + 32768));
         return PSACX_OK;
     }));
     uint64_t chunks = 1;
@@ -342,7 +342,7 @@ int MultiRun<T>::suffix_tree(const std::vector<const uint8_t*>& text, const std:
         std::vector<std::vector<uint64_t>> mine(L, std::vector<uint64_t>(256, 0));
         PSACX_TRY(par([&](int i) -> int {
             psacx_ctx* c = ctx(i);
-            MG_OP(g, c, ensure_pinned(c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+            MG_OP(g, c, ensure_pinned(c, PINNED_SORT_BYTES + 65536 + 32768));
             DBuf<unsigned long long> h; MG_OP(g, c, h.alloc(c, 256));
             MG_HIP(g, hipSetDevice(c->device));
             MG_HIP(g, hipMemsetAsync(h.p, 0, 256 * 8, c->stream));
@@ -350,9 +350,9 @@ int MultiRun<T>::suffix_tree(const std::vector<const uint8_t*>& text, const std:
                 hipLaunchKernelGGL((char_hist_kernel<256>), dim3(grid_for(c, m_local[i] / 16 + 1, 256, 8)), dim3(256), 0, c->stream, text[i], m_local[i], h.p);
                 MG_HIP(g, hipGetLastError());
             }
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, h.p, 256 * 8, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, h.p, 256 * 8, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
-            std::memcpy(mine[i].data(), c->pinned + 32768, 256 * 8);
+            std::memcpy(mine[i].data(), c->pinned + PIN_MULTI, 256 * 8);
             return PSACX_OK;
         }));
         std::vector<uint64_t> all;
@@ -496,7 +496,7 @@ int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vecto
     PSACX_TRY(par([&](int i) -> int {
         S[i].c = ctx(i); S[i].r = rank(i); S[i].m = m_local[i]; S[i].text = text[i];
         S[i].SA = d_sa[i]; S[i].ISA = d_isa[i]; S[i].LCP = with_lcp ? d_lcp[i] : nullptr;
-        MG_OP(g, S[i].c, ensure_pinned(S[i].c, 2 * sizeof(unsigned long long) * MAX_PASSES * RADIX + 65536 + 32768));
+        MG_OP(g, S[i].c, ensure_pinned(S[i].c, PINNED_SORT_BYTES + 65536 + 32768));
         return PSACX_OK;
     }));
     // The block is verified in `chunks` pieces of consecutive SA positions (every test is local to an entry and its
@@ -632,9 +632,9 @@ int MultiRun<T>::check(const std::vector<const uint8_t*>& text, const std::vecto
                                    bd[i].has_prev, (T)bd[i].prev[0], (T)bd[i].prev[1], (T)bd[i].prev[2], e.p);
             else SIMPLE_LAUNCH(c, (check_verdict_kernel<T>), cnt[i], S[i].SA + from[i], back[i].p, ch[i].p, nx[i].p, lcp_i, mins_i, cnt[i], S[i].off + from[i], n,
                                bd[i].has_prev, (T)bd[i].prev[0], (T)bd[i].prev[1], (T)bd[i].prev[2], e.p);
-            MG_HIP(g, hipMemcpyAsync(c->pinned + 32768, e.p, 32, hipMemcpyDeviceToHost, c->stream));
+            MG_HIP(g, hipMemcpyAsync(c->pinned + PIN_MULTI, e.p, 32, hipMemcpyDeviceToHost, c->stream));
             MG_HIP(g, hipStreamSynchronize(c->stream));
-            const uint64_t* h = reinterpret_cast<const uint64_t*>(c->pinned + 32768);
+            const uint64_t* h = reinterpret_cast<const uint64_t*>(c->pinned + PIN_MULTI);
             for (int w = 0; w < 4; ++w) mine[i][w] += h[w];
             return PSACX_OK;
         }));

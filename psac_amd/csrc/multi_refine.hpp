@@ -41,7 +41,7 @@ int MultiRun<T>::refine_sort(std::vector<Rec<T>>& rec, const std::vector<const T
         const bool goes_on = next_first != 0 && next_first == mine[i][2];
         MG_HIP(g, hipSetDevice(c->device));
         DBuf<uint64_t> d; MG_OP(g, c, d.alloc(c, 4));
-        uint64_t* h = reinterpret_cast<uint64_t*>(c->pinned + 32768);
+        uint64_t* h = reinterpret_cast<uint64_t*>(c->pinned + PIN_MULTI);
         h[0] = S[i].off + 1; h[1] = mine[i][2];
         MG_HIP(g, hipMemcpyAsync(d.p, h, 16, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL((lower_bound_kernel<T>), dim3(1), dim3(64), 0, c->stream, (const T*)rec[i].k1.p, cn, (const uint64_t*)d.p, 2u, d.p + 2);

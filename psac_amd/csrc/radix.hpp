@@ -14,20 +14,11 @@
 #pragma once
 #include <type_traits>
 #include "dev_common.hpp"
+#include "sort_scratch.hpp"
 
 namespace psacx {
 
-constexpr int RADIX_BITS = 8;
-constexpr int RADIX = 1 << RADIX_BITS;
-constexpr int MAX_PASSES = 2 * (64 / RADIX_BITS);   // two 64-bit key words
-constexpr int SLAB_TILES = 64;                       // tiles per slab of the three-kernel offset scan (smallest slab)
-// Very long inputs use longer slabs: the scan over the slab totals is one workgroup walking them one after the other
-// (1.7 ms per pass at 2^20 tiles with 64-tile slabs, 2 % of a 4 GiB construction), the scan inside a slab runs in
-// parallel over slabs.
-// (a slab is one workgroup walking its tiles one after the other, the slab totals one workgroup walking the slabs: measured with
-//  both sizes in one process, 2^29 64-bit records (2^17 tiles): 4.3 ms of histogram + scans per sort with slabs of 1024 tiles,
-//  3.2 with 256 or 128; 2^32 records (2^20 tiles): 29.1 with 1024, 28.1 with 512, 31.3 with 128)
-inline unsigned slab_tiles_for(uint64_t ntiles) { return ntiles > (1u << 19) ? 512u : ntiles > (1u << 16) ? 256u : (unsigned)SLAB_TILES; }
+// RADIX_BITS, RADIX, MAX_PASSES, SLAB_TILES and slab_tiles_for: sort_scratch.hpp (with the layouts of the tables the kernels below read)
 
 // pass p < passes_lo reads key2 (low word), the rest read key1
 struct PassPlan {
@@ -649,6 +640,7 @@ struct __attribute__((aligned(32))) SlabInfo {      // what a workgroup needs to
     unsigned bucket, slab0;                  // the bucket and its first slab
     unsigned pad[2];
 };
+static_assert(sizeof(SlabInfo) == SLAB_INFO_BYTES, "sort_scratch.hpp sizes the slab_info table");
 struct OneWordTabs {
     const unsigned long long* bucket_off;    // [257]
     const unsigned long long* slab_start;    // [257]
@@ -1000,7 +992,7 @@ __global__ __launch_bounds__(BLOCK) void onew_max_group_kernel(const unsigned lo
 // batch before it writes, and no other wave touches these groups.  No workgroup barrier.
 // A group longer than GROUP_CAP is left as it is: the caller checks the largest group before it launches.
 // ---------------------------------------------------------------------------
-constexpr int GROUP_CAP = 512;
+// (GROUP_CAP: sort_scratch.hpp -- the layouts of the group form depend on it)
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void group_sort16_kernel(uint64_t* __restrict__ recs, const unsigned long long* __restrict__ starts, uint64_t ngroups,
                                                              uint64_t nrec, int sfield, uint8_t* __restrict__ tie_bytes) {

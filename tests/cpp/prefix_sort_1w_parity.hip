@@ -66,7 +66,6 @@ static std::vector<uint8_t> short_tail_pairs(uint64_t n, uint64_t seed) {       
 struct Case { std::string name; std::vector<uint8_t> text; unsigned lc, lead; int expect; };
 
 static bool run_case(const Case& cs, uint64_t pad) {
-    constexpr uint64_t ONEW_SUB_TILES = 2048;          // tile of the smallest sort configuration (engine.hpp: SORT_TILE_MIN)
     const uint64_t n = cs.text.size();
     psacx_ctx ctx;
     std::memset(&ctx.stats, 0, sizeof(ctx.stats));
@@ -86,7 +85,7 @@ static bool run_case(const Case& cs, uint64_t pad) {
     uint8_t *d_dig = nullptr, *d_tie = nullptr;
     SortScratch sc;
     std::memset(&sc, 0, sizeof(sc));
-    sc.desc_bytes = sort_desc_bytes(n) + (size_t)(n / ONEW_SUB_TILES + ONEW_SUB) * RADIX * sizeof(unsigned) + (size_t)ONEW_SUB * RADIX * 8 + (8u << 20);
+    sc.desc_bytes = sort_desc_bytes(n) + onew_sub_bucket_supplement(n);
     HIP_OK(hipMalloc(&d_text, n + 64));
     HIP_OK(hipMemset(d_text, 0, n + 64));
     HIP_OK(hipMemcpy(d_text, cs.text.data(), n, hipMemcpyHostToDevice));
