@@ -147,13 +147,15 @@ int psacx_trim(psacx_ctx* ctx);
  *   LSD_BUCKET_PASSES the one-word prefix sort of the first round sorts every digit below the top one by LSD passes inside the 256 buckets, not the
  *                     upper digits most significant first and the last 16 bits on chip (psacx_stats.group_sort; parity tests, A/B runs)
  *   FIRST_LEAD        test option: leading bits the two-stage first round sorts on; honoured when a multiple of 8, at least bits(n - 1) + 3, at most 40
- *                     and at most the bits of the first key word, ignored otherwise (40 reaches the sub-bucket passes on small texts)          */
+ *                     and at most the bits of the first key word, ignored otherwise (40 reaches the sub-bucket passes on small texts)
+ *   LZ_SMALL_TILES    test option: psacx_lz77_dev_* parses on tiles of 64 positions in groups of 4 tiles, not 1024 in groups of 128, so that every
+ *                     level of the parse, the walk over the groups included, is taken at a few hundred positions; the parse is the same     */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
-    PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD,
+    PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD, PSACX_OPT_LZ_SMALL_TILES,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
@@ -779,6 +781,73 @@ int psacx_overlaps_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint
                        const uint32_t* LCP, uint64_t min_len, uint32_t flags, uint32_t* lb, uint32_t* ub);
 int psacx_overlaps_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA, const uint64_t* ISA,
                        const uint64_t* LCP, uint64_t min_len, uint32_t flags, uint64_t* lb, uint64_t* ub);
+
+/* LZ77 factorization ------------------------------------------------------------------
+ * The first question asked of the index about the text itself: the longest previous factor of every position and the greedy
+ * Lempel-Ziv parse cut from it -- for compression, for the repetitiveness measure z, as input to an LZ-index.  The reference has
+ * no counterpart.  One text, one GPU.  The text is no argument of the two building calls: SA, LCP and the range-minimum index of
+ * LCP (psacx_rmq_index_dev_*) answer them.
+ *
+ * Definitions.  Text S[0..n), "all ones" the largest value of the index type.  SA and LCP as psacx_construct_dev_* leaves them,
+ * LCP[r] the common prefix of the suffixes of ranks r - 1 and r.  For rank r with i = SA[r]:
+ *
+ *     p = the largest rank below r with SA[p] < i          (none: lp = 0)
+ *     q = the smallest rank above r with SA[q] < i         (none: lq = 0)
+ *     lp = min LCP[p+1 .. r+1)        lq = min LCP[r+1 .. q+1)
+ *     if lp >= lq and lp > 0:   LPF[i] = lp,  SRC[i] = SA[p]
+ *     else if lq > 0:           LPF[i] = lq,  SRC[i] = SA[q]
+ *     else:                     LPF[i] = 0,   SRC[i] = all ones
+ *
+ *  - On the arrays of one text LPF[i] = max over j < i of lcp(S[i..), S[j..)): the longest previous factor.  The predecessor
+ *    wins ties, which pins SRC.
+ *  - p and q are nearest smaller values of SA itself, on both sides; lp and lq are two range minima.
+ *
+ * Parse.  s_0 = 0; len_k = min(max(1, LPF[s_k]), n - s_k); s_{k+1} = s_k + len_k, until s_z = n.  A phrase with LPF[s_k] = 0 is a
+ * literal of one byte and its source is all ones; every other phrase copies len_k bytes from SRC[s_k].  A source may overlap its
+ * phrase (src + len > start), as in LZ77: a decoder copies byte by byte.
+ *
+ * Totality.  Whatever SA, LCP and index hold, nothing is read or written out of range; SA entries >= n write nothing; both
+ * outputs are cleared first, to 0 and to all ones; every slot ends as either (LPF = 0, SRC = all ones) or (SRC < i and
+ * 1 <= LPF <= n - i).  The parse takes any n values as LPF, clamps them as above and always ends with s_z = n.
+ *
+ * psacx_lpf_dev_*: d_lpf and d_src receive n entries each.  n == 0 is legal; n beyond the index type returns PSACX_ERANGE; a NULL
+ * output PSACX_EINVAL.  Scratch: 16 n bytes of device memory for the two neighbour arrays, allocated for the time of the call
+ * beside the ctx slab (which holds the search pyramid over SA); where that fails the call returns PSACX_ENOMEM and the outputs are
+ * as they were.  Sixteen lanes per rank; no input is written.
+ * psacx_lz77_dev_*: d_start receives z + 1 entries, start[z] = n; d_psrc receives z entries, all ones for a literal.  *z is
+ * always set.  d_start == NULL is the count query.  z + 1 > cap returns PSACX_ERANGE with *z valid and nothing written to the two
+ * lists (the convention of psacx_occurrences_dev_*).  d_src may be NULL (any n values as LPF, no sources); d_psrc must then be
+ * NULL too.  Scratch in the ctx slab: n entries of the index type, n bytes, and a word per 1024 positions.  No kernel of the parse
+ * follows a chain of dependent loads that grows with n beyond one load per 2^17 positions.
+ * psacx_check_lz77_dev_*: the round-trip verdict -- the parse decodes to the text.  *errors counts
+ *   - start[0] != 0, and start[z] != n                                         (one each);
+ *   - per phrase k: start[k+1] <= start[k]; else a literal (source all ones) longer than 1; and a source >= start[k];
+ *   - per text position x, whose phrase k is found by a bisection of start: x outside [start[k], start[k+1]); else, for a phrase
+ *     with a source below its start, S[src + x - start[k]] != S[x].
+ * 0 means that start / psrc decode to S byte by byte.  It does not prove the parse greedy: any parse into literals and earlier
+ * copies passes.  (Greediness is held by the host model of the tests at small sizes.)  z > n returns PSACX_EINVAL.  Nothing is
+ * read out of range whatever the lists hold.
+ * psacx_lpf_* / psacx_lz77_*: the host-pointer forms.  They stage SA and LCP, build the index, and free what they allocated on
+ * every path.  psacx_lz77_* returns start (z + 1 entries) and src (z entries) without handing out LPF; start == NULL and
+ * src == NULL is the count query, z + 1 > cap returns PSACX_ERANGE with *z valid. */
+int psacx_lpf_dev_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* d_SA, const uint32_t* d_LCP, const uint32_t* d_index, uint32_t* d_lpf,
+                      uint32_t* d_src);
+int psacx_lpf_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_SA, const uint64_t* d_LCP, const uint64_t* d_index, uint64_t* d_lpf,
+                      uint64_t* d_src);
+int psacx_lz77_dev_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* d_lpf, const uint32_t* d_src, uint32_t* d_start, uint32_t* d_psrc,
+                       uint64_t cap, uint64_t* z);
+int psacx_lz77_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_lpf, const uint64_t* d_src, uint64_t* d_start, uint64_t* d_psrc,
+                       uint64_t cap, uint64_t* z);
+int psacx_check_lz77_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_start, const uint32_t* d_psrc, uint64_t z,
+                             uint64_t* errors);
+int psacx_check_lz77_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint64_t* d_start, const uint64_t* d_psrc, uint64_t z,
+                             uint64_t* errors);
+int psacx_lpf_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* SA, const uint32_t* LCP, uint32_t* lpf, uint32_t* src);
+int psacx_lpf_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* SA, const uint64_t* LCP, uint64_t* lpf, uint64_t* src);
+int psacx_lz77_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* SA, const uint32_t* LCP, uint32_t* start, uint32_t* src, uint64_t cap,
+                   uint64_t* z);
+int psacx_lz77_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* SA, const uint64_t* LCP, uint64_t* start, uint64_t* src, uint64_t cap,
+                   uint64_t* z);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

@@ -890,4 +890,40 @@ overlap_intervals<index_t> overlaps(suffix_array<char, index_t, true, false>& sa
     return out;
 }
 
+// The greedy LZ77 parse of the text (psacx.h: "LZ77 factorization"): phrase k is the text from start[k] to start[k + 1], a copy of
+// as many bytes from src[k] -- which may run into the phrase itself -- or one literal byte where src[k] is all ones of index_t.
+// start has z + 1 entries and ends with n, src has z.  The suffix array must have been constructed from one text with its LCP.
+// One rank only, as overlaps.
+template <typename index_t>
+struct lz_factors {
+    std::vector<index_t> start, src;
+};
+
+template <typename index_t>
+lz_factors<index_t> lz77(suffix_array<char, index_t, true, false>& sa) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, uint64_t n, const uint32_t* s, const uint32_t* lcp, uint32_t* start, uint32_t* src, uint64_t cap, uint64_t* z) {
+            return psacx_lz77_u32(c, n, s, lcp, start, src, cap, z);
+        }
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* s, const uint64_t* lcp, uint64_t* start, uint64_t* src, uint64_t cap, uint64_t* z) {
+            return psacx_lz77_u64(c, n, s, lcp, start, src, cap, z);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: lz77 needs a single-rank communicator (the parse runs on one GPU)");
+    if (sa.n == 0 || sa.local_SA.size() != sa.n || sa.local_LCP.size() != sa.n)
+        throw std::runtime_error("lz77: the suffix array holds no SA and LCP of a text");
+    const W* s = reinterpret_cast<const W*>(sa.local_SA.data());
+    const W* l = reinterpret_cast<const W*>(sa.local_LCP.data());
+    uint64_t z = 0;
+    psacx::check(sa.context(), Call::run(sa.context(), sa.n, s, l, (W*)0, (W*)0, 0, &z));
+    std::vector<W> start(z + 1), src(z + 1);
+    psacx::check(sa.context(), Call::run(sa.context(), sa.n, s, l, start.data(), src.data(), z + 1, &z));
+    lz_factors<index_t> out;
+    out.start.assign(start.begin(), start.end());
+    out.src.assign(src.begin(), src.begin() + z);
+    return out;
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -22,7 +22,7 @@ PSACX_OVERLAP_WHOLE = 1
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
            "widen_last": 8, "no_digit_bytes": 9, "no_bucket_sort": 10, "isa_update": 11, "gather": 12, "no_heavy": 13, "no_whole": 14, "no_lazy_ranks": 15, "no_early_out": 16,
            "no_spread_cursors": 17, "locate_shape": 18, "locate_count": 19, "generic_rebucket": 20,
-           "plain_side_kernels": 21, "lsd_bucket_passes": 22, "first_lead": 23}
+           "plain_side_kernels": 21, "lsd_bucket_passes": 22, "first_lead": 23, "lz_small_tiles": 24}
 MULTI_OPTIONS = {"layout": 1, "slab": 2, "output_slack": 3, "trace": 4, "wire_piece": 5, "pieces": 6, "check_chunks": 7, "global_refine_sort": 8,
                  "one_stage": 9, "two_word": 10, "one_word": 11, "no_slices": 12, "slice_wide": 13, "slice_shape": 14}
 MULTI_FORCE_WIRE, MULTI_NO_RCCL, MULTI_SHM = 1, 2, 4
@@ -52,6 +52,8 @@ EXPORTS = [
     "psacx_rmq_index_dev_u32", "psacx_rmq_index_dev_u64", "psacx_rmq_dev_u32", "psacx_rmq_dev_u64", "psacx_lce_dev_u32", "psacx_lce_dev_u64",
     "psacx_rmq_u32", "psacx_rmq_u64", "psacx_lce_u32", "psacx_lce_u64",
     "psacx_overlaps_dev_u32", "psacx_overlaps_dev_u64", "psacx_overlaps_u32", "psacx_overlaps_u64",
+    "psacx_lpf_dev_u32", "psacx_lpf_dev_u64", "psacx_lz77_dev_u32", "psacx_lz77_dev_u64", "psacx_check_lz77_dev_u32", "psacx_check_lz77_dev_u64",
+    "psacx_lpf_u32", "psacx_lpf_u64", "psacx_lz77_u32", "psacx_lz77_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -158,6 +160,11 @@ def load():
         getattr(lib, "psacx_lce_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, u64, u64, vp]
         getattr(lib, "psacx_overlaps_dev_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, u32, vp, vp]
         getattr(lib, "psacx_overlaps_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, u32, vp, vp]
+        getattr(lib, "psacx_lpf_dev_" + suf).argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        getattr(lib, "psacx_lz77_dev_" + suf).argtypes = [vp, u64, vp, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_check_lz77_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_lpf_" + suf).argtypes = [vp, u64, vp, vp, vp, vp]
+        getattr(lib, "psacx_lz77_" + suf).argtypes = [vp, u64, vp, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

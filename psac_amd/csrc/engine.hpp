@@ -70,6 +70,7 @@ struct Knobs {
                                   // (onew_bucket_passes: upper digits most significant first, the last 16 bits on chip; parity tests and A/B runs)
     unsigned first_lead = 0;      // PSACX_OPT_FIRST_LEAD: leading bits the two-stage first round sorts on (tests: 40 reaches the sub-bucket form of the group
                                   // form at sizes a test can afford); honoured when a multiple of 8, >= bits_for(n - 1) + 3, <= 40 and <= the bits of word 1
+    bool lz_small_tiles = false;  // PSACX_OPT_LZ_SMALL_TILES: the LZ77 parse works on tiles of 64 positions in groups of 4 (tests: every level of lz.hpp at a few hundred positions)
     int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (search.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
 };

@@ -272,6 +272,13 @@ int occurrences_dev(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_o
     return PSACX_OK;
 }
 
+// the scan for callers outside this file (lz.hip): a caller that keeps scratch of its own in the slab leaves the first
+// exclusive_scan_slab_bytes(len) bytes to the scan and sizes the slab before it places anything
+int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len) { return exclusive_scan_dev<uint64_t>(c, d_a, len); }
+uint64_t exclusive_scan_slab_bytes(uint64_t len) {
+    return (len + 256 * LOCATE_SCAN_ITEMS - 1) / (256 * LOCATE_SCAN_ITEMS) * sizeof(unsigned long long) + 4096;
+}
+
 } // namespace psacx
 
 using namespace psacx;

@@ -232,6 +232,14 @@ class SuffixArray(object):
             raise ValueError("overlaps needs construct_ss with lcp=True first")
         return overlaps(self.n, self.string_offsets, self.local_SA, self.local_B, self.local_LCP, min_len, whole, ctx=self.ctx)
 
+    def lz77(self):
+        """The greedy LZ77 parse (start, src) of the text of the last construct (which needs lcp=True): lz77() over its arrays."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("lz77 needs a single-rank context (the parse runs on one GPU)")
+        if getattr(self, "string_offsets", None) is not None or not self.lcp or self.n == 0 or self.local_LCP.size != self.n:
+            raise ValueError("lz77 needs construct of one text with lcp=True first")
+        return lz77(self.local_SA, self.local_LCP, ctx=self.ctx)
+
     def construct_device(self, d_text, n, d_sa, d_isa, d_lcp=None, fast_resolval=True, k=0, profile=False, d_lc=None):
         """Same with every buffer already resident in HBM (raw device addresses)."""
         args = [self.ctx.handle, C.c_void_p(d_text), int(n), int(k), self._flags(fast_resolval, profile),
@@ -628,6 +636,91 @@ def overlaps(text_len_or_text, offsets, SA, ISA, LCP, min_len, whole=False, ctx=
     ctx.check(fn(ctx.handle, n, _ptr(so), max(0, so.size - 1), _ptr(sa), _ptr(isa), _ptr(lcp), int(min_len), OVERLAP_WHOLE if whole else 0,
                  _ptr(lb), _ptr(ub)))
     return lb, ub
+
+
+def lpf_device(ctx, n, d_sa, d_lcp, d_index, d_lpf, d_src, index_bits):
+    """psacx_lpf_dev_*: the longest previous factor of every position and a source for each, from SA, LCP and the index of
+    rmq_index_device over d_lcp, all resident in HBM (include/psacx.h: "LZ77 factorization").  d_lpf / d_src receive n entries of the
+    index type each: src < i and 1 <= lpf <= n - i, or 0 and all ones."""
+    fn = getattr(ctx._lib, "psacx_lpf_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(fn(ctx.handle, int(n), opt(d_sa), opt(d_lcp), opt(d_index), opt(d_lpf), opt(d_src)))
+
+
+def lz77_device(ctx, n, d_lpf, d_src, d_start, d_psrc, cap, index_bits):
+    """psacx_lz77_dev_*: the greedy parse cut from an LPF array in HBM.  d_start receives z + 1 entries (start[z] = n), d_psrc z
+    entries (all ones for a literal); d_start=None is the count query; d_src=None parses any n values without sources.  Returns z;
+    raises PsacxError -2 where z + 1 exceeds cap, with the lists untouched and z in the error's attribute z."""
+    fn = getattr(ctx._lib, "psacx_lz77_dev_u%d" % index_bits)
+    z = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, int(n), opt(d_lpf), opt(d_src), opt(d_start), opt(d_psrc), int(cap), C.byref(z)))
+    except PsacxError as e:
+        e.z = z.value
+        raise
+    return z.value
+
+
+def check_lz77_device(ctx, d_text, n, d_start, d_psrc, z, index_bits):
+    """psacx_check_lz77_dev_*: the number of violations of "start / psrc decode to the text"; 0 means the parse round-trips.  It does
+    not prove the parse greedy."""
+    fn = getattr(ctx._lib, "psacx_check_lz77_dev_u%d" % index_bits)
+    errors = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(fn(ctx.handle, opt(d_text), int(n), opt(d_start), opt(d_psrc), int(z), C.byref(errors)))
+    return errors.value
+
+
+def _sa_lcp(SA, LCP, what):
+    sa, lcp = np.ascontiguousarray(SA), np.ascontiguousarray(LCP)
+    if sa.dtype not in (np.uint32, np.uint64) or lcp.dtype != sa.dtype:
+        raise TypeError(what + " needs SA and LCP both uint32 or both uint64")
+    if sa.size != lcp.size:
+        raise ValueError("SA and LCP must have n entries each")
+    return sa, lcp
+
+
+def lpf(SA, LCP, ctx=None):
+    """psacx_lpf_*: (lpf, src) of the text whose suffix array and LCP array these are -- lpf[i] the length of the longest factor at i
+    that also starts before i, src[i] where (all ones where lpf[i] is 0).  Host arrays; everything is staged for the call."""
+    sa, lcp = _sa_lcp(SA, LCP, "lpf")
+    out, src = np.zeros(sa.size, sa.dtype), np.zeros(sa.size, sa.dtype)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_lpf_u%d" % (sa.dtype.itemsize * 8))
+    ctx.check(fn(ctx.handle, sa.size, _ptr(sa), _ptr(lcp), _ptr(out), _ptr(src)))
+    return out, src
+
+
+def lz77(SA, LCP, ctx=None):
+    """psacx_lz77_*: (start, src) of the greedy LZ77 parse -- phrase k is text[start[k]:start[k + 1]], a copy from src[k], or one
+    literal byte where src[k] is all ones; start has z + 1 entries and ends with n.  A copy may overlap its phrase."""
+    sa, lcp = _sa_lcp(SA, LCP, "lz77")
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_lz77_u%d" % (sa.dtype.itemsize * 8))
+    z = C.c_uint64(0)
+    ctx._pre()
+    ctx.check(fn(ctx.handle, sa.size, _ptr(sa), _ptr(lcp), None, None, 0, C.byref(z)))
+    start, src = np.zeros(z.value + 1, sa.dtype), np.zeros(z.value, sa.dtype)
+    ctx.check(fn(ctx.handle, sa.size, _ptr(sa), _ptr(lcp), _ptr(start), _ptr(src) if z.value else _ptr(start), z.value + 1, C.byref(z)))
+    return start, src
+
+
+def lz77_decode(start, src, text):
+    """The text a parse stands for, as bytes: copies are made byte by byte (a source may overlap its phrase), and `text` is read at
+    the literal phrases only."""
+    st = np.asarray(start)
+    ones = int(np.iinfo(np.asarray(src).dtype).max)
+    out = bytearray()
+    for k in range(st.size - 1):
+        a, b, s = int(st[k]), int(st[k + 1]), int(src[k])
+        if s == ones:
+            out.append(int(text[a]) if not isinstance(text, str) else ord(text[a]))
+        else:
+            for t in range(b - a):
+                out.append(out[s + t])
+    return bytes(out)
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
