@@ -849,6 +849,104 @@ int psacx_lz77_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* SA, const uint32_
 int psacx_lz77_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* SA, const uint64_t* LCP, uint64_t* start, uint64_t* src, uint64_t cap,
                    uint64_t* z);
 
+/* BWT and repeats ---------------------------------------------------------------------
+ * The Burrows-Wheeler transform of the text, and the repeats of a text or a read set as the inner nodes of its suffix tree
+ * filtered by what stands to their left: right-maximal, maximal and supermaximal repeats from SA + LCP + BWT (Abouelhoda, Kurtz,
+ * Ohlebusch 2004).  psacx_suffix_tree_dev_* reaches the same nodes through a table of n x (sigma + 1) words; nothing here needs
+ * it, and no ANSV is used.  The reference has no counterpart.  One GPU.
+ *
+ * Setting.  One text S[0..n), or a string set as for psacx_locate_gsa_dev_*: the m strings lie back to back and d_ends is the
+ * bitmap of psacx_string_ends_dev (bit p = "a string starts at p, or p == n").  SA and LCP as psacx_construct_dev_* /
+ * psacx_construct_gsa_dev_* leave them.  L[r] = LCP[r], with L[0] read as 0 whatever is stored.  Ranks are SA indices.  "All ones"
+ * is the largest value of the index type.
+ *
+ * BWT.
+ *     bwt[r]   = S[SA[r] - 1] if SA[r] is not the start of a string; otherwise the last byte of that string (S[n-1] for one text):
+ *                the cyclic convention per string.  The array is aligned with SA.  It is NOT libdivsufsort's divbwt layout, which
+ *                drops the primary entry and shifts the entries in front of it.
+ *     first    = a bitmap of (n >> 5) + 1 words of 32: bit r is set iff SA[r] starts a string (one text: iff SA[r] == 0).  Bits at
+ *                and beyond n are 0.
+ *     *primary = the rank r with SA[r] == 0; all ones of 64 bits if no entry is 0; any one of them if several are.
+ *  - d_ends == NULL: one text.  d_first and primary may each be NULL; d_bwt may be NULL if d_first is not.
+ *  - Totality: an SA entry >= n gives bwt 0 and a clear bit.  Nothing is read outside the text [0, n) and the bitmap [0, n].  No
+ *    input is written.  n == 0 is PSACX_OK; n beyond the index type returns PSACX_ERANGE.
+ *  - One rank per lane, one gathered byte per rank.  A wave owns 64 consecutive ranks and its two words of `first` come from one
+ *    ballot, stored by two of its lanes: no atomics and no read-modify-write of bitmap words.  The primary is written by the lane
+ *    that sees it.  A rank that starts a string of a set needs the end of that string; the wave scans d_ends for it 64 words a step,
+ *    n / 32 words over all strings.  Scratch: 8 bytes of the ctx slab.
+ *
+ * Repeats.  A repeat is named by its LCP-interval.  Rank j >= 1 with l = L[j] > 0 is a HEAD iff the largest h < j with L[h] <= l
+ * has L[h] < l: the head(x) == x of the suffix-tree checker above, one head per inner node.  Its interval is lb = h and ub = the
+ * smallest e > j with L[e] < l, or n.  The repeat is S[SA[lb] .. SA[lb] + l); it has ub - lb >= 2 occurrences, exactly SA[lb..ub).
+ * In a set a string end counts as a right character different from everything and a string start as a left character different
+ * from everything: one unique sentinel on each side of each string.
+ *
+ * Three bit arrays over the ranks 1 .. n - 1:
+ *     D[x]  = first[x] or first[x-1] or bwt[x] != bwt[x-1]
+ *     F[x]  = first[x]                                                    (also at rank 0)
+ *     St[x] = L[x] != L[x-1]
+ * The kinds:
+ *     PSACX_REPEATS_RIGHT         every head: the right-maximal repeats, all inner nodes below the root.
+ *     PSACX_REPEATS_MAXIMAL       heads whose interval is left-diverse: D[x] == 1 for some lb < x < ub.
+ *     PSACX_REPEATS_SUPERMAXIMAL  heads whose interval is flat (no x in [lb + 2, ub) has St[x] == 1: all children are leaves), holds
+ *                                 at most 256 ranks that do not start a string, and whose bwt bytes of those ranks are pairwise
+ *                                 different.  The same as "a maximal repeat that is a substring of no other maximal repeat".
+ * Filters, applied after the kind: l >= min_len (0 and 1 mean the same); ub - lb >= min_occ (values below 2 mean 2); with
+ * max_occ > 0, ub - lb <= max_occ.
+ *
+ * psacx_repeats_dev_*: d_index is the index of psacx_rmq_index_dev_* over d_LCP; d_bwt and d_first are the outputs of
+ * psacx_bwt_dev_*.
+ *  - Output: z triples (lb, ub, len = l) in ascending order of the head j, which is pinned.  d_len may be NULL.
+ *  - d_lb == NULL (then d_ub and d_len must be NULL too, PSACX_EINVAL otherwise) is the count query.
+ *  - z > cap returns PSACX_ERANGE with *z valid and nothing written to the lists (the convention of psacx_lz77_dev_* and
+ *    psacx_occurrences_dev_*).  *z is always set.
+ *  - Kind 0 reads neither d_bwt nor d_first, and both may be NULL.  Kinds 1 and 2 need both (PSACX_EINVAL otherwise).  An unknown
+ *    kind returns PSACX_EINVAL.  n <= 1 gives z = 0.  n beyond the index type, or beyond 2^48, returns PSACX_ERANGE.
+ *  - d_lb and d_ub are, as they are, the interval lists psacx_occurrences_dev_* takes (q = z): pos lists where each repeat occurs,
+ *    sid in which string.
+ *  - Totality, whatever LCP, index, bwt and first hold: nothing is read or written out of range (first inside its (n >> 5) + 1
+ *    words and below bit n), every search ends, every triple has 0 <= lb < ub <= n, ub - lb >= 2 and len >= 1, rank 0 is never a
+ *    head, and a left search that finds nothing means lb = 0.  No input is written.
+ *  - Sixteen lanes per rank.  A rank costs one search to the left (one or two groups of 64 LCP entries where the answer is near) and
+ *    one fetch of L[h]; most ranks end there.  A head adds one search to the right and, per kind, two directory entries and two
+ *    bitmap words for each of its tests.  The supermaximal kind then walks the bwt bytes of its interval, 16 per step, and leaves at
+ *    the first collision.  Flat intervals are disjoint, so the walks of a whole call touch at most n ranks; only a run of identical
+ *    whole strings makes a single walk long.
+ *  - Scratch.  In the ctx slab, with c = (n >> 6) + 1 and t = ceil(n / 1024): for kinds 1 and 2 the bit arrays D and F with their
+ *    directories, 2 * (8 c + 8 c) bytes; for kind 2 the same for St, 16 c bytes; the select bytes, 1024 t; the tile counts,
+ *    8 (t + 1); the block sums of the scans, 8 bytes per 4096 of max(c, t + 1) beyond 4 KiB; each part rounded up to 256 bytes.
+ *    Kind 1 scans D alone and kind 2 F and St.  A call that writes lists also allocates 2 n entries of the index type for the
+ *    candidate intervals, beside the slab and for the time of the call; where that fails it returns PSACX_ENOMEM and the outputs
+ *    are untouched.  The count query allocates nothing.  It runs everything but the last kernel, so a caller that counts first and
+ *    asks for the lists afterwards pays the walk over the ranks twice.
+ * psacx_bwt_* / psacx_repeats_*: the host-pointer forms.  offsets == NULL means one text (m is ignored); otherwise the m + 1
+ * offsets of the strings, which must start at 0, end at n and ascend strictly (PSACX_EINVAL).  They stage the arrays, build the
+ * bitmap of the string ends, the index and the BWT, and free what they allocated on every path.  psacx_bwt_* needs bwt;
+ * psacx_repeats_* with lb == NULL is the count query, z > cap returns PSACX_ERANGE with *z valid; kind 0 reads neither text nor SA. */
+#define PSACX_REPEATS_RIGHT 0u
+#define PSACX_REPEATS_MAXIMAL 1u
+#define PSACX_REPEATS_SUPERMAXIMAL 2u
+int psacx_bwt_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint32_t* d_SA, uint8_t* d_bwt,
+                      uint32_t* d_first, uint64_t* primary);
+int psacx_bwt_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint64_t* d_SA, uint8_t* d_bwt,
+                      uint32_t* d_first, uint64_t* primary);
+int psacx_repeats_dev_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* d_LCP, const uint32_t* d_index, const uint8_t* d_bwt,
+                          const uint32_t* d_first, uint32_t kind, uint64_t min_len, uint64_t min_occ, uint64_t max_occ, uint32_t* d_lb,
+                          uint32_t* d_ub, uint32_t* d_len, uint64_t cap, uint64_t* z);
+int psacx_repeats_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_LCP, const uint64_t* d_index, const uint8_t* d_bwt,
+                          const uint32_t* d_first, uint32_t kind, uint64_t min_len, uint64_t min_occ, uint64_t max_occ, uint64_t* d_lb,
+                          uint64_t* d_ub, uint64_t* d_len, uint64_t cap, uint64_t* z);
+int psacx_bwt_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA, uint8_t* bwt,
+                  uint64_t* primary);
+int psacx_bwt_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA, uint8_t* bwt,
+                  uint64_t* primary);
+int psacx_repeats_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                      const uint32_t* LCP, uint32_t kind, uint64_t min_len, uint64_t min_occ, uint64_t max_occ, uint32_t* lb, uint32_t* ub,
+                      uint32_t* len, uint64_t cap, uint64_t* z);
+int psacx_repeats_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                      const uint64_t* LCP, uint32_t kind, uint64_t min_len, uint64_t min_occ, uint64_t max_occ, uint64_t* lb, uint64_t* ub,
+                      uint64_t* len, uint64_t cap, uint64_t* z);
+
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP
  * (suffix_array.hpp:183-194, :217-228; src/psac.cpp:85-93 block-decomposes the input).  A psacx_multi stands for the

@@ -926,4 +926,119 @@ lz_factors<index_t> lz77(suffix_array<char, index_t, true, false>& sa) {
     return out;
 }
 
+// The Burrows-Wheeler transform aligned with local_SA (psacx.h: "BWT and repeats"): bwt[r] is the byte in front of suffix local_SA[r],
+// and where that suffix starts a string (the text) the last byte of that string -- not libdivsufsort's divbwt layout.  primary is
+// the rank of position 0.  The text [begin, end) must be the bytes `sa` was constructed from (the object does not keep them), `ss`
+// the set of construct_ss.  One rank only, as lz77.
+struct bwt_result {
+    std::string bwt;
+    std::size_t primary;
+};
+
+// The repeats of one kind as LCP-intervals: repeat k is the len[k] bytes at local_SA[lb[k]] and occurs exactly at
+// local_SA[lb[k] .. ub[k]), in ascending order of the interval heads.  occurrences(sa, lb, ub) / occurrences(sa, ss, lb, ub) list
+// positions and strings.  The suffix array must have been constructed with its LCP.
+template <typename index_t>
+struct repeat_intervals {
+    std::vector<index_t> lb, ub, len;
+};
+
+enum repeat_kind { repeats_right = 0, repeats_maximal = 1, repeats_supermaximal = 2 };
+
+namespace psacx {
+
+inline void flatten_set(simple_dstringset& ss, std::vector<uint8_t>& text, std::vector<uint64_t>& soff) {
+    text.clear(); soff.assign(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) {
+        text.insert(text.end(), reinterpret_cast<const uint8_t*>(ss.str_begins[s]), reinterpret_cast<const uint8_t*>(ss.str_begins[s]) + ss.sizes[s]);
+        soff.push_back(text.size());
+    }
+}
+
+template <typename index_t, bool LCP, bool LC>
+bwt_result bwt_of(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, uint8_t* b, uint64_t* p) {
+            return psacx_bwt_u32(c, t, n, o, m, s, b, p);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, uint8_t* b, uint64_t* p) {
+            return psacx_bwt_u64(c, t, n, o, m, s, b, p);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: bwt needs a single-rank communicator (the transform runs on one GPU)");
+    if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n) throw std::runtime_error("bwt: text does not match the suffix array");
+    std::vector<uint8_t> out(sa.n);
+    uint64_t primary = 0;
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, soff ? soff->data() : (const uint64_t*)0, soff ? (uint64_t)soff->size() - 1 : 0,
+                                  reinterpret_cast<const W*>(sa.local_SA.data()), out.data(), &primary));
+    bwt_result r;
+    r.bwt.assign(out.begin(), out.end());
+    r.primary = (std::size_t)primary;
+    return r;
+}
+
+template <typename index_t>
+repeat_intervals<index_t> repeats_of(suffix_array<char, index_t, true, false>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff,
+                                     repeat_kind kind, std::size_t min_len, std::size_t min_occ, std::size_t max_occ) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, const uint32_t* l, uint32_t k,
+                       uint64_t a, uint64_t b, uint64_t d, uint32_t* lb, uint32_t* ub, uint32_t* len, uint64_t cap, uint64_t* z) {
+            return psacx_repeats_u32(c, t, n, o, m, s, l, k, a, b, d, lb, ub, len, cap, z);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, const uint64_t* l, uint32_t k,
+                       uint64_t a, uint64_t b, uint64_t d, uint64_t* lb, uint64_t* ub, uint64_t* len, uint64_t cap, uint64_t* z) {
+            return psacx_repeats_u64(c, t, n, o, m, s, l, k, a, b, d, lb, ub, len, cap, z);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: repeats needs a single-rank communicator (the enumeration runs on one GPU)");
+    if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n || sa.local_LCP.size() != sa.n)
+        throw std::runtime_error("repeats: the suffix array holds no SA and LCP of this text");
+    const W* s = reinterpret_cast<const W*>(sa.local_SA.data());
+    const W* l = reinterpret_cast<const W*>(sa.local_LCP.data());
+    const uint64_t* o = soff ? soff->data() : (const uint64_t*)0;
+    const uint64_t m = soff ? (uint64_t)soff->size() - 1 : 0;
+    uint64_t z = 0;
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, l, (uint32_t)kind, min_len, min_occ, max_occ, (W*)0, (W*)0, (W*)0, 0, &z));
+    std::vector<W> lb(z + 1), ub(z + 1), len(z + 1);
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, l, (uint32_t)kind, min_len, min_occ, max_occ, lb.data(), ub.data(),
+                                  len.data(), z, &z));
+    repeat_intervals<index_t> out;
+    out.lb.assign(lb.begin(), lb.begin() + z);
+    out.ub.assign(ub.begin(), ub.begin() + z);
+    out.len.assign(len.begin(), len.begin() + z);
+    return out;
+}
+
+} // namespace psacx
+
+template <typename index_t, bool LCP, bool LC, typename Iterator>
+bwt_result bwt(suffix_array<char, index_t, LCP, LC>& sa, Iterator begin, Iterator end) {
+    return psacx::bwt_of(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0);
+}
+
+template <typename index_t, bool LCP>
+bwt_result bwt(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss) {
+    std::vector<uint8_t> text; std::vector<uint64_t> soff;
+    psacx::flatten_set(ss, text, soff);
+    return psacx::bwt_of(sa, text, &soff);
+}
+
+template <typename index_t, typename Iterator>
+repeat_intervals<index_t> repeats(suffix_array<char, index_t, true, false>& sa, Iterator begin, Iterator end, repeat_kind kind = repeats_maximal,
+                                  std::size_t min_len = 1, std::size_t min_occ = 2, std::size_t max_occ = 0) {
+    return psacx::repeats_of(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, kind, min_len, min_occ, max_occ);
+}
+
+template <typename index_t>
+repeat_intervals<index_t> repeats(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, repeat_kind kind = repeats_maximal,
+                                  std::size_t min_len = 1, std::size_t min_occ = 2, std::size_t max_occ = 0) {
+    std::vector<uint8_t> text; std::vector<uint64_t> soff;
+    psacx::flatten_set(ss, text, soff);
+    return psacx::repeats_of(sa, text, &soff, kind, min_len, min_occ, max_occ);
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -17,6 +17,7 @@ PSACX_PROFILE = 4
 PSACX_MAX_ROUNDS = 72
 PSACX_MATCH_SUFFIXES = 1
 PSACX_OVERLAP_WHOLE = 1
+PSACX_REPEATS_RIGHT, PSACX_REPEATS_MAXIMAL, PSACX_REPEATS_SUPERMAXIMAL = 0, 1, 2
 
 # psacx_configure options (include/psacx.h); Context.configure(force_diet=1, ...) takes them by name
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
@@ -54,6 +55,8 @@ EXPORTS = [
     "psacx_overlaps_dev_u32", "psacx_overlaps_dev_u64", "psacx_overlaps_u32", "psacx_overlaps_u64",
     "psacx_lpf_dev_u32", "psacx_lpf_dev_u64", "psacx_lz77_dev_u32", "psacx_lz77_dev_u64", "psacx_check_lz77_dev_u32", "psacx_check_lz77_dev_u64",
     "psacx_lpf_u32", "psacx_lpf_u64", "psacx_lz77_u32", "psacx_lz77_u64",
+    "psacx_bwt_dev_u32", "psacx_bwt_dev_u64", "psacx_repeats_dev_u32", "psacx_repeats_dev_u64",
+    "psacx_bwt_u32", "psacx_bwt_u64", "psacx_repeats_u32", "psacx_repeats_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -165,6 +168,10 @@ def load():
         getattr(lib, "psacx_check_lz77_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_lpf_" + suf).argtypes = [vp, u64, vp, vp, vp, vp]
         getattr(lib, "psacx_lz77_" + suf).argtypes = [vp, u64, vp, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_bwt_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_repeats_dev_" + suf).argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_bwt_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_repeats_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, u32, u64, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

@@ -184,6 +184,7 @@ class SuffixArray(object):
             fn = getattr(self.ctx._lib, "psacx_construct_u%d" % self.index_bits)
         self.ctx._pre()
         self.ctx.check(fn(*args))
+        self._text, self._text_off = t, None
         return self._after()
 
     def construct_into(self, text, SA, B, LCP=None, fast_resolval=True, k=0):
@@ -224,6 +225,7 @@ class SuffixArray(object):
         self.ctx.check(fn(self.ctx.handle, _ptr(text), n, _ptr(off), int(off.size - 1), int(k), self._flags(True, profile),
                           _ptr(self.local_SA), _ptr(self.local_B), _ptr(self.local_LCP) if self.lcp else None))
         self.string_offsets = off
+        self._text, self._text_off = text, off
         return self._after()
 
     def overlaps(self, min_len, whole=False):
@@ -239,6 +241,23 @@ class SuffixArray(object):
         if getattr(self, "string_offsets", None) is not None or not self.lcp or self.n == 0 or self.local_LCP.size != self.n:
             raise ValueError("lz77 needs construct of one text with lcp=True first")
         return lz77(self.local_SA, self.local_LCP, ctx=self.ctx)
+
+    def bwt(self):
+        """(bwt, primary) of the text or string set of the last construct / construct_ss: bwt() over its arrays."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("bwt needs a single-rank context (the transform runs on one GPU)")
+        if getattr(self, "_text", None) is None or self._text.size != self.n or self.local_SA.size != self.n:
+            raise ValueError("bwt needs construct or construct_ss first")
+        return bwt(self._text, self.local_SA, offsets=self._text_off, ctx=self.ctx)
+
+    def repeats(self, kind="maximal", min_len=1, min_occ=2, max_occ=0):
+        """(lb, ub, length) of the repeats of the text or string set of the last construct / construct_ss (which needs lcp=True):
+        repeats() over its arrays."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("repeats needs a single-rank context (the enumeration runs on one GPU)")
+        if getattr(self, "_text", None) is None or self._text.size != self.n or not self.lcp or self.local_LCP.size != self.n:
+            raise ValueError("repeats needs construct or construct_ss with lcp=True first")
+        return repeats(self._text, self.local_SA, self.local_LCP, kind, min_len, min_occ, max_occ, offsets=self._text_off, ctx=self.ctx)
 
     def construct_device(self, d_text, n, d_sa, d_isa, d_lcp=None, fast_resolval=True, k=0, profile=False, d_lc=None):
         """Same with every buffer already resident in HBM (raw device addresses)."""
@@ -721,6 +740,107 @@ def lz77_decode(start, src, text):
             for t in range(b - a):
                 out.append(out[s + t])
     return bytes(out)
+
+
+REPEATS_KINDS = {"right": _lib.PSACX_REPEATS_RIGHT, "maximal": _lib.PSACX_REPEATS_MAXIMAL, "super": _lib.PSACX_REPEATS_SUPERMAXIMAL,
+                 "supermaximal": _lib.PSACX_REPEATS_SUPERMAXIMAL}
+
+
+def bwt_device(ctx, d_text, n, d_ends, d_sa, d_bwt, d_first, index_bits, want_primary=True):
+    """psacx_bwt_dev_*: the Burrows-Wheeler transform aligned with SA, bwt[r] = text[SA[r] - 1], cyclic per string (include/psacx.h:
+    "BWT and repeats").  d_ends is the bitmap of string_ends_device, or None for one text.  d_bwt receives n bytes, d_first the
+    bitmap ((n >> 5) + 1 words of 32) of the ranks that start a string; either may be None.  Returns the rank of position 0 (all ones
+    of 64 bits where no SA entry is 0), or None with want_primary=False."""
+    fn = getattr(ctx._lib, "psacx_bwt_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    primary = C.c_uint64(0)
+    ctx.check(fn(ctx.handle, opt(d_text), int(n), opt(d_ends), opt(d_sa), opt(d_bwt), opt(d_first), C.byref(primary) if want_primary else None))
+    return primary.value if want_primary else None
+
+
+def repeats_device(ctx, n, d_lcp, d_index, d_bwt, d_first, kind, min_len, min_occ, max_occ, d_lb, d_ub, d_len, cap, index_bits):
+    """psacx_repeats_dev_*: the repeats of one kind (0 right-maximal, 1 maximal, 2 supermaximal) as LCP-intervals, from LCP, the index
+    of rmq_index_device over it, and the two outputs of bwt_device (not read by kind 0).  d_lb / d_ub / d_len receive z entries each in
+    the order of the interval heads; d_lb=None is the count query; d_len may be None.  Returns z; raises PsacxError -2 where z exceeds
+    cap, with the lists untouched and z in the error's attribute z.  occurrences_device takes d_lb and d_ub as they are."""
+    fn = getattr(ctx._lib, "psacx_repeats_dev_u%d" % index_bits)
+    z = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    try:
+        ctx.check(fn(ctx.handle, int(n), opt(d_lcp), opt(d_index), opt(d_bwt), opt(d_first), int(kind), int(min_len), int(min_occ), int(max_occ),
+                     opt(d_lb), opt(d_ub), opt(d_len), int(cap), C.byref(z)))
+    except PsacxError as e:
+        e.z = z.value
+        raise
+    return z.value
+
+
+def _text_bytes(text):
+    if isinstance(text, str):
+        text = text.encode("latin-1")
+    return np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+
+
+def bwt(text, SA, offsets=None, ctx=None):
+    """psacx_bwt_*: (bwt, primary) -- bwt[r] = text[SA[r] - 1] as uint8, aligned with SA; where SA[r] starts a string (with
+    offsets=None: where it is 0) the last byte of that string.  primary is the rank of position 0.  This is not libdivsufsort's divbwt
+    layout.  Host arrays; everything is staged for the call."""
+    t, sa = _text_bytes(text), np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("bwt needs SA as uint32 or uint64")
+    if sa.size != t.size:
+        raise ValueError("SA must have one entry per byte of the text")
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    out = np.zeros(t.size, np.uint8)
+    primary = C.c_uint64(0)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_bwt_u%d" % (sa.dtype.itemsize * 8))
+    ctx.check(fn(ctx.handle, _ptr(t), t.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(sa), _ptr(out),
+                 C.byref(primary)))
+    return out, primary.value
+
+
+def bwt_decode(bwt, primary):
+    """The text of an SA-aligned BWT of one text, as bytes: the row of the end marker goes back in at primary + 1, then one LF walk.
+    Host only."""
+    b = np.asarray(bwt, np.uint8)
+    n = int(b.size)
+    if n == 0:
+        return b""
+    if not 0 <= int(primary) < n:
+        raise ValueError("primary must be a rank of the text")
+    col = np.concatenate(([int(b[primary]) + 1], b.astype(np.int64) + 1))
+    col[int(primary) + 1] = 0
+    lf = np.empty(n + 1, np.int64)
+    lf[np.argsort(col, kind="stable")] = np.arange(n + 1)
+    out = np.empty(n, np.uint8)
+    r = 0
+    for k in range(n - 1, -1, -1):
+        out[k] = col[r] - 1
+        r = lf[r]
+    return out.tobytes()
+
+
+def repeats(text, SA, LCP, kind="maximal", min_len=1, min_occ=2, max_occ=0, offsets=None, ctx=None):
+    """psacx_repeats_*: (lb, ub, length) of the repeats of one kind ("right", "maximal", "super"): repeat k is
+    text[SA[lb[k]]:SA[lb[k]] + length[k]] and occurs exactly at SA[lb[k]:ub[k]].  Filters: length >= min_len, min_occ <= occurrences,
+    and occurrences <= max_occ where max_occ > 0.  With offsets the text is a string set, whose string ends and starts differ from
+    every character.  occurrences(SA, lb, ub, offsets=offsets) lists positions and strings.  Host arrays; everything is staged."""
+    k = REPEATS_KINDS[kind] if isinstance(kind, str) else int(kind)
+    sa, lcp = _sa_lcp(SA, LCP, "repeats")
+    t = _text_bytes(text)
+    if t.size != sa.size:
+        raise ValueError("SA and LCP must have one entry per byte of the text")
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_repeats_u%d" % (sa.dtype.itemsize * 8))
+    z = C.c_uint64(0)
+    head = [ctx.handle, _ptr(t), t.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(sa), _ptr(lcp), k,
+            int(min_len), int(min_occ), int(max_occ)]
+    ctx.check(fn(*(head + [None, None, None, 0, C.byref(z)])))
+    lb, ub, ln = (np.zeros(max(1, z.value), sa.dtype) for _ in range(3))
+    ctx.check(fn(*(head + [_ptr(lb), _ptr(ub), _ptr(ln), z.value, C.byref(z)])))
+    return lb[:z.value], ub[:z.value], ln[:z.value]
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
