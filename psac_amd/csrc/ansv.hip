@@ -9,6 +9,7 @@
 // minima held in registers and LDS, and the few searches that leave a tile share one walk of a
 // global 64-ary min-pyramid per distinct value (ansv_tile.hpp).
 #include "engine.hpp"
+#include "query_calls.hpp"
 #include "nsv.hpp"
 #include "ansv_wave.hpp"
 
@@ -244,11 +245,6 @@ int suffix_tree_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_
     if (edges) *edges = cnt;
     return PSACX_OK;
 }
-
-// check.hip: PSACX_EINVAL unless the m + 1 offsets on the device start at 0, end at n and ascend strictly (uses the first bytes of the
-// slab and waits); and the bitmap of the string ends into bits[(n >> 5) + 1], queued on the ctx stream
-int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n);
-int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits);
 
 template <typename T>
 __global__ void gst_clear_first_kernel(T* lcp) { lcp[0] = 0; }

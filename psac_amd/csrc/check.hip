@@ -4,7 +4,8 @@
 // further) and d_check_sa's idea of a scalable checker (:207-267).  LCP entries are verified by
 // direct character comparison, which is linear in sum(LCP): meant for texts with short repeats.
 #include "engine.hpp"
-#include "nsv.hpp"      // nsv_pyramid_layout only: the suffix-tree checker below must not use the searches declared there
+#include "query_calls.hpp"
+#include "nsv.hpp"     // nsv_pyramid_layout only: the suffix-tree checker below must not use the searches declared there
 
 namespace psacx {
 

@@ -14,7 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/psacx.h"
+#include "query_cli.hpp"
+
+using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: lce -f <text> -p <pairs, \"a b\" per line> [-e E] [--set] [--index 32|64|auto] [--device N] [-o <file>]\n"
@@ -22,30 +24,10 @@ static void usage() {
                  "--set: the strings of -f are its lines, an extension ends with either string, and a position may be string:offset.\n";
 }
 
-static void must(psacx_ctx* c, int rc) {
-    if (rc == PSACX_OK) return;
-    std::string msg = std::string("psacx: ") + psacx_strerror(rc);
-    const char* detail = c ? psacx_last_hip_error(c) : "";
-    if (detail && detail[0]) msg += std::string(" [") + detail + "]";
-    throw std::runtime_error(msg);
-}
-
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint32_t* sa, uint32_t* isa, uint32_t* lcp) {
-    return off ? psacx_construct_gsa_dev_u32(c, t, n, off, m, 0, PSACX_LCP, sa, isa, lcp) : psacx_construct_dev_u32(c, t, n, 0, PSACX_LCP, sa, isa, lcp);
-}
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint64_t* sa, uint64_t* isa, uint64_t* lcp) {
-    return off ? psacx_construct_gsa_dev_u64(c, t, n, off, m, 0, PSACX_LCP, sa, isa, lcp) : psacx_construct_dev_u64(c, t, n, 0, PSACX_LCP, sa, isa, lcp);
-}
-static int rmq_index(psacx_ctx* c, const uint32_t* v, uint64_t n, uint32_t* index, uint64_t* e) { return psacx_rmq_index_dev_u32(c, v, n, index, e); }
-static int rmq_index(psacx_ctx* c, const uint64_t* v, uint64_t n, uint64_t* index, uint64_t* e) { return psacx_rmq_index_dev_u64(c, v, n, index, e); }
 static int lce(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* isa, const uint32_t* lcp, const uint32_t* index, const uint32_t* a,
                const uint32_t* b, uint64_t q, uint64_t e, uint32_t* len) { return psacx_lce_dev_u32(c, n, off, m, isa, lcp, index, a, b, q, e, len); }
 static int lce(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* isa, const uint64_t* lcp, const uint64_t* index, const uint64_t* a,
                const uint64_t* b, uint64_t q, uint64_t e, uint64_t* len) { return psacx_lce_dev_u64(c, n, off, m, isa, lcp, index, a, b, q, e, len); }
-
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 template <typename IT>
 static int run(const std::string& text, const std::vector<uint64_t>& soff, const std::vector<uint64_t>& pa, const std::vector<uint64_t>& pb, uint64_t e,
@@ -55,56 +37,36 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
     const uint64_t top = (uint64_t)(IT)~(IT)0;
     std::vector<IT> a(q), b(q), len(q);
     for (uint64_t i = 0; i < q; ++i) { a[i] = (IT)(pa[i] < top ? pa[i] : top); b[i] = (IT)(pb[i] < top ? pb[i] : top); }     // (beyond n is beyond n)
-    psacx_ctx* c = nullptr;
-    must(nullptr, psacx_create(&c, device, nullptr));
-    std::vector<void*> held;
-    auto dev = [&](uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1)); held.push_back(p); return p; };
-    auto release = [&]() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); };
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        uint8_t* d_text = (uint8_t*)dev(n);
-        IT* d_sa = (IT*)dev(n * sizeof(IT));
-        IT* d_isa = (IT*)dev(n * sizeof(IT));
-        IT* d_lcp = (IT*)dev(n * sizeof(IT));
-        uint64_t* d_soff = set ? (uint64_t*)dev((m + 1) * sizeof(uint64_t)) : nullptr;
-        must(c, psacx_copy_h2d(c, d_text, text.data(), n));
-        if (set) must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
-        must(c, construct(c, d_text, n, d_soff, m, d_sa, d_isa, d_lcp));
-        std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
-        auto t1 = std::chrono::steady_clock::now();
-        uint64_t entries = 0;
-        must(c, rmq_index(c, (const IT*)nullptr, n, (IT*)nullptr, &entries));
-        IT* d_index = (IT*)dev(entries * sizeof(IT));
-        must(c, rmq_index(c, d_lcp, n, d_index, &entries));
-        std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
-        std::cerr << "Index entries: " << entries << std::endl;
-        if (q) {
-            IT* d_a = (IT*)dev(q * sizeof(IT));
-            IT* d_b = (IT*)dev(q * sizeof(IT));
-            IT* d_len = (IT*)dev(q * sizeof(IT));
-            must(c, psacx_copy_h2d(c, d_a, a.data(), q * sizeof(IT)));
-            must(c, psacx_copy_h2d(c, d_b, b.data(), q * sizeof(IT)));
-            auto t2 = std::chrono::steady_clock::now();
-            must(c, lce(c, n, d_soff, m, d_isa, d_lcp, d_index, d_a, d_b, q, e, d_len));
-            std::cerr << "LCE time: " << ms_since(t2) << " ms" << std::endl;
-            must(c, psacx_copy_d2h(c, len.data(), d_len, q * sizeof(IT)));
-        }
-        for (uint64_t i = 0; i < q; ++i) out << (uint64_t)len[i] << '\n';
-    } catch (...) {
-        release();
-        throw;
+    Session s(device);
+    psacx_ctx* const c = s.c;
+    auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d_text = (uint8_t*)s.dev(n);
+    IT* d_sa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_isa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_lcp = (IT*)s.dev(n * sizeof(IT));
+    uint64_t* d_soff = set ? (uint64_t*)s.dev((m + 1) * sizeof(uint64_t)) : nullptr;
+    must(c, psacx_copy_h2d(c, d_text, text.data(), n));
+    if (set) must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
+    must(c, construct(c, d_text, n, d_soff, m, PSACX_LCP, d_sa, d_isa, d_lcp));
+    std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+    auto t1 = std::chrono::steady_clock::now();
+    uint64_t entries = 0;
+    IT* d_index = rmq_index_of<IT>(s, d_lcp, n, &entries);
+    std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
+    std::cerr << "Index entries: " << entries << std::endl;
+    if (q) {
+        IT* d_a = (IT*)s.dev(q * sizeof(IT));
+        IT* d_b = (IT*)s.dev(q * sizeof(IT));
+        IT* d_len = (IT*)s.dev(q * sizeof(IT));
+        must(c, psacx_copy_h2d(c, d_a, a.data(), q * sizeof(IT)));
+        must(c, psacx_copy_h2d(c, d_b, b.data(), q * sizeof(IT)));
+        auto t2 = std::chrono::steady_clock::now();
+        must(c, lce(c, n, d_soff, m, d_isa, d_lcp, d_index, d_a, d_b, q, e, d_len));
+        std::cerr << "LCE time: " << ms_since(t2) << " ms" << std::endl;
+        must(c, psacx_copy_d2h(c, len.data(), d_len, q * sizeof(IT)));
     }
-    release();
+    for (uint64_t i = 0; i < q; ++i) out << (uint64_t)len[i] << '\n';
     return 0;
-}
-
-static bool read_file(const std::string& fn, std::string& into) {
-    std::ifstream f(fn.c_str(), std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    into.resize((std::size_t)f.tellg());
-    f.seekg(0);
-    if (!into.empty()) f.read(&into[0], (std::streamsize)into.size());
-    return true;
 }
 
 // "123", or with a set "s:o" = offset o in string s; false if it is neither
@@ -142,23 +104,12 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
-    if (file.empty() || pairs.empty() || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    if (file.empty() || pairs.empty() || !index_known(index)) { usage(); return EXIT_FAILURE; }
     std::string text, lines;
     if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     if (!read_file(pairs, lines)) { std::cerr << "error: cannot open " << pairs << std::endl; return EXIT_FAILURE; }
     std::vector<uint64_t> soff;
-    if (set) {                                        // the strings are the runs between '\n', laid back to back (gsac)
-        std::string flat;
-        flat.reserve(text.size());
-        soff.push_back(0);
-        for (std::size_t b = 0; b < text.size();) {
-            std::size_t en = text.find('\n', b);
-            if (en == std::string::npos) en = text.size();
-            if (en > b) { flat.append(text, b, en - b); soff.push_back(flat.size()); }
-            b = en + 1;
-        }
-        text.swap(flat);
-    }
+    if (set) { std::string flat; split_lines(text, flat, soff); text.swap(flat); }
     if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
     // one pair per line, two positions separated by blanks; empty lines are skipped
     std::vector<uint64_t> pa, pb;
@@ -183,7 +134,7 @@ int main(int argc, char** argv) {
         pa.push_back(x);
         pb.push_back(y);
     }
-    const bool use32 = index == "32" || (index == "auto" && text.size() < 0xFFFFFFFEull);
+    const bool narrow = use32(index, text.size());
     try {
         std::ofstream f;
         if (!outfile.empty()) {
@@ -191,7 +142,7 @@ int main(int argc, char** argv) {
             if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
         }
         std::ostream& out = outfile.empty() ? std::cout : f;
-        const int rc = use32 ? run<uint32_t>(text, soff, pa, pb, e, device, out) : run<uint64_t>(text, soff, pa, pb, e, device, out);
+        const int rc = narrow ? run<uint32_t>(text, soff, pa, pb, e, device, out) : run<uint64_t>(text, soff, pa, pb, e, device, out);
         out.flush();
         if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

@@ -23,7 +23,9 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/psacx.h"
+#include "query_cli.hpp"
+
+using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--longest [--suffixes] [--max-len L]]\n"
@@ -34,16 +36,6 @@ static void usage() {
                  "--max-len L: of at most L bytes of each.\n";
 }
 
-static void must(psacx_ctx* c, int rc) {
-    if (rc == PSACX_OK) return;
-    std::string msg = std::string("psacx: ") + psacx_strerror(rc);
-    const char* detail = c ? psacx_last_hip_error(c) : "";
-    if (detail && detail[0]) msg += std::string(" [") + detail + "]";
-    throw std::runtime_error(msg);
-}
-
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, uint32_t* sa, uint32_t* isa) { return psacx_construct_dev_u32(c, t, n, 0, 0, sa, isa, nullptr); }
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, uint64_t* sa, uint64_t* isa) { return psacx_construct_dev_u64(c, t, n, 0, 0, sa, isa, nullptr); }
 static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
     return psacx_lookup_table_dev_u32(c, t, n, sa, k, tab, code, sg, e);
 }
@@ -55,12 +47,6 @@ static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa
 static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code, const uint8_t* pat,
                   const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) { return psacx_locate_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, lb, ub); }
 
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint32_t* sa, uint32_t* isa) {
-    return psacx_construct_gsa_dev_u32(c, t, n, off, m, 0, 0, sa, isa, nullptr);
-}
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint64_t* sa, uint64_t* isa) {
-    return psacx_construct_gsa_dev_u64(c, t, n, off, m, 0, 0, sa, isa, nullptr);
-}
 static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t*, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg,
                  uint64_t* e) { return psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, tab, code, sg, e); }
 static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t*, uint32_t k, uint64_t* tab, uint16_t* code, uint32_t* sg,
@@ -85,18 +71,6 @@ static int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* end
     return ends ? psacx_match_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
                 : psacx_match_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
 }
-static int occurrences(psacx_ctx* c, const uint32_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* lb, const uint32_t* ub, uint64_t q,
-                       uint64_t limit, uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total) {
-    return psacx_occurrences_dev_u32(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
-}
-static int occurrences(psacx_ctx* c, const uint64_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* lb, const uint64_t* ub, uint64_t q,
-                       uint64_t limit, uint64_t* start, uint64_t* pos, uint64_t* sid, uint64_t cap, uint64_t* total) {
-    return psacx_occurrences_dev_u64(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
-}
-
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // soff: the offsets of the strings of --set (empty without it); occ: print the occurrences, at most limit each if limit > 0;
 // longest: --longest, with mflags (PSACX_MATCH_SUFFIXES for --suffixes) and max_len
@@ -106,109 +80,87 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
     const uint64_t n = text.size(), q = poff.size() - 1, m = soff.empty() ? 0 : soff.size() - 1;
     const uint64_t e = longest && (mflags & PSACX_MATCH_SUFFIXES) ? poff[q] : q;      // results: one per pattern, or one per byte of the patterns
     const bool set = m != 0;
-    psacx_ctx* c = nullptr;
-    must(nullptr, psacx_create(&c, device, nullptr));
-    std::vector<void*> held;
-    auto dev = [&](uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes)); held.push_back(p); return p; };
-    auto release = [&]() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); };
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        uint8_t* d_text = (uint8_t*)dev(n);
-        IT* d_sa = (IT*)dev(n * sizeof(IT));
-        IT* d_isa = (IT*)dev(n * sizeof(IT));
-        uint64_t* d_soff = set ? (uint64_t*)dev((m + 1) * sizeof(uint64_t)) : nullptr;
-        must(c, psacx_copy_h2d(c, d_text, text.data(), n));
-        if (set) {
-            must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
-            must(c, construct(c, d_text, n, d_soff, m, d_sa, d_isa));
-        } else {
-            must(c, construct(c, d_text, n, d_sa, d_isa));
-        }
-        std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
-        uint32_t* d_ends = nullptr;
-        if (set) {
-            auto te = std::chrono::steady_clock::now();
-            uint64_t words = 0;
-            must(c, psacx_string_ends_dev(c, nullptr, m, n, nullptr, &words));
-            d_ends = (uint32_t*)dev(words * sizeof(uint32_t));
-            must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
-            std::cerr << "Ends time: " << ms_since(te) << " ms" << std::endl;
-        }
-        uint16_t code[256];
-        IT* d_table = nullptr;
-        if (k) {
-            auto t1 = std::chrono::steady_clock::now();
-            uint32_t sigma = 0;
-            uint64_t entries = 0;
-            must(c, set ? table(c, d_text, n, d_ends, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries)
-                        : table(c, d_text, n, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries));
-            d_table = (IT*)dev(entries * sizeof(IT));
-            must(c, set ? table(c, d_text, n, d_ends, d_sa, k, d_table, code, &sigma, &entries) : table(c, d_text, n, d_sa, k, d_table, code, &sigma, &entries));
-            std::cerr << "Table time: " << ms_since(t1) << " ms" << std::endl;
-            std::cerr << "Table entries: " << entries << std::endl;
-        }
-        std::vector<IT> len(longest ? e : 0), lb(e), ub(e), pos, sid;
-        std::vector<uint64_t> start(e + 1, 0);
-        if (q) {
-            uint8_t* d_pat = (uint8_t*)dev(pat.size() + 1);
-            uint64_t* d_poff = (uint64_t*)dev((q + 1) * sizeof(uint64_t));
-            IT* d_len = longest ? (IT*)dev(e * sizeof(IT) + 1) : nullptr;
-            IT* d_lb = (IT*)dev(e * sizeof(IT) + 1);
-            IT* d_ub = (IT*)dev(e * sizeof(IT) + 1);
-            if (!pat.empty()) must(c, psacx_copy_h2d(c, d_pat, pat.data(), pat.size()));
-            must(c, psacx_copy_h2d(c, d_poff, poff.data(), (q + 1) * sizeof(uint64_t)));
-            auto t2 = std::chrono::steady_clock::now();
-            if (longest) {
-                must(c, match(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, mflags, max_len, e, d_len, d_lb, d_ub));
-                std::cerr << "Match time: " << ms_since(t2) << " ms" << std::endl;
-                if (e) must(c, psacx_copy_d2h(c, len.data(), d_len, e * sizeof(IT)));
-            } else {
-                must(c, set ? locate(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub)
-                            : locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
-                std::cerr << "Locate time: " << ms_since(t2) << " ms" << std::endl;
-            }
-            if (e) must(c, psacx_copy_d2h(c, lb.data(), d_lb, e * sizeof(IT)));
-            if (e) must(c, psacx_copy_d2h(c, ub.data(), d_ub, e * sizeof(IT)));
-            if (occ) {
-                auto t3 = std::chrono::steady_clock::now();
-                uint64_t* d_start = (uint64_t*)dev((e + 1) * sizeof(uint64_t));
-                uint64_t total = 0;
-                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, e, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
-                IT* d_pos = (IT*)dev(total * sizeof(IT) + 1);
-                IT* d_sid = set ? (IT*)dev(total * sizeof(IT) + 1) : nullptr;
-                must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, e, limit, d_start, d_pos, d_sid, total, &total));
-                std::cerr << "Occurrences time: " << ms_since(t3) << " ms" << std::endl;
-                pos.resize(total);
-                must(c, psacx_copy_d2h(c, start.data(), d_start, (e + 1) * sizeof(uint64_t)));
-                if (total) must(c, psacx_copy_d2h(c, pos.data(), d_pos, total * sizeof(IT)));
-                if (set) { sid.resize(total); if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT))); }
-            }
-        }
-        for (uint64_t i = 0; i < e; ++i) {
-            if (longest) out << (uint64_t)len[i] << ' ';
-            out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i];
-            if (occ)
-                for (uint64_t t = start[i]; t < start[i + 1]; ++t) {
-                    out << ' ';
-                    if (set) out << (uint64_t)sid[t] << ':' << (uint64_t)pos[t] - soff[(std::size_t)sid[t]]; else out << (uint64_t)pos[t];
-                }
-            out << '\n';
-        }
-    } catch (...) {
-        release();
-        throw;
+    Session s(device);
+    psacx_ctx* const c = s.c;
+    auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d_text = (uint8_t*)s.dev(n);
+    IT* d_sa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_isa = (IT*)s.dev(n * sizeof(IT));
+    uint64_t* d_soff = set ? (uint64_t*)s.dev((m + 1) * sizeof(uint64_t)) : nullptr;
+    must(c, psacx_copy_h2d(c, d_text, text.data(), n));
+    if (set) must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
+    must(c, construct(c, d_text, n, d_soff, m, 0, d_sa, d_isa, (IT*)nullptr));
+    std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+    uint32_t* d_ends = nullptr;
+    if (set) {
+        auto te = std::chrono::steady_clock::now();
+        uint64_t words = 0;
+        must(c, psacx_string_ends_dev(c, nullptr, m, n, nullptr, &words));
+        d_ends = (uint32_t*)s.dev(words * sizeof(uint32_t));
+        must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
+        std::cerr << "Ends time: " << ms_since(te) << " ms" << std::endl;
     }
-    release();
+    uint16_t code[256];
+    IT* d_table = nullptr;
+    if (k) {
+        auto t1 = std::chrono::steady_clock::now();
+        uint32_t sigma = 0;
+        uint64_t entries = 0;
+        must(c, set ? table(c, d_text, n, d_ends, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries)
+                    : table(c, d_text, n, (const IT*)nullptr, k, (IT*)nullptr, code, &sigma, &entries));
+        d_table = (IT*)s.dev(entries * sizeof(IT));
+        must(c, set ? table(c, d_text, n, d_ends, d_sa, k, d_table, code, &sigma, &entries) : table(c, d_text, n, d_sa, k, d_table, code, &sigma, &entries));
+        std::cerr << "Table time: " << ms_since(t1) << " ms" << std::endl;
+        std::cerr << "Table entries: " << entries << std::endl;
+    }
+    std::vector<IT> len(longest ? e : 0), lb(e), ub(e), pos, sid;
+    std::vector<uint64_t> start(e + 1, 0);
+    if (q) {
+        uint8_t* d_pat = (uint8_t*)s.dev(pat.size() + 1);
+        uint64_t* d_poff = (uint64_t*)s.dev((q + 1) * sizeof(uint64_t));
+        IT* d_len = longest ? (IT*)s.dev(e * sizeof(IT) + 1) : nullptr;
+        IT* d_lb = (IT*)s.dev(e * sizeof(IT) + 1);
+        IT* d_ub = (IT*)s.dev(e * sizeof(IT) + 1);
+        if (!pat.empty()) must(c, psacx_copy_h2d(c, d_pat, pat.data(), pat.size()));
+        must(c, psacx_copy_h2d(c, d_poff, poff.data(), (q + 1) * sizeof(uint64_t)));
+        auto t2 = std::chrono::steady_clock::now();
+        if (longest) {
+            must(c, match(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, mflags, max_len, e, d_len, d_lb, d_ub));
+            std::cerr << "Match time: " << ms_since(t2) << " ms" << std::endl;
+            if (e) must(c, psacx_copy_d2h(c, len.data(), d_len, e * sizeof(IT)));
+        } else {
+            must(c, set ? locate(c, d_text, n, d_ends, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub)
+                        : locate(c, d_text, n, d_sa, d_table, k, k ? code : nullptr, d_pat, d_poff, q, d_lb, d_ub));
+            std::cerr << "Locate time: " << ms_since(t2) << " ms" << std::endl;
+        }
+        if (e) must(c, psacx_copy_d2h(c, lb.data(), d_lb, e * sizeof(IT)));
+        if (e) must(c, psacx_copy_d2h(c, ub.data(), d_ub, e * sizeof(IT)));
+        if (occ) {
+            auto t3 = std::chrono::steady_clock::now();
+            uint64_t* d_start = (uint64_t*)s.dev((e + 1) * sizeof(uint64_t));
+            uint64_t total = 0;
+            must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, e, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
+            IT* d_pos = (IT*)s.dev(total * sizeof(IT) + 1);
+            IT* d_sid = set ? (IT*)s.dev(total * sizeof(IT) + 1) : nullptr;
+            must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, e, limit, d_start, d_pos, d_sid, total, &total));
+            std::cerr << "Occurrences time: " << ms_since(t3) << " ms" << std::endl;
+            pos.resize(total);
+            must(c, psacx_copy_d2h(c, start.data(), d_start, (e + 1) * sizeof(uint64_t)));
+            if (total) must(c, psacx_copy_d2h(c, pos.data(), d_pos, total * sizeof(IT)));
+            if (set) { sid.resize(total); if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT))); }
+        }
+    }
+    for (uint64_t i = 0; i < e; ++i) {
+        if (longest) out << (uint64_t)len[i] << ' ';
+        out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i];
+        if (occ)
+            for (uint64_t t = start[i]; t < start[i + 1]; ++t) {
+                out << ' ';
+                if (set) out << (uint64_t)sid[t] << ':' << (uint64_t)pos[t] - soff[(std::size_t)sid[t]]; else out << (uint64_t)pos[t];
+            }
+        out << '\n';
+    }
     return 0;
-}
-
-static bool read_file(const std::string& fn, std::string& into) {
-    std::ifstream f(fn.c_str(), std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    into.resize((std::size_t)f.tellg());
-    f.seekg(0);
-    if (!into.empty()) f.read(&into[0], (std::streamsize)into.size());
-    return true;
 }
 
 int main(int argc, char** argv) {
@@ -240,24 +192,13 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
-    if (file.empty() || queries.empty() || k < 0 || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    if (file.empty() || queries.empty() || k < 0 || !index_known(index)) { usage(); return EXIT_FAILURE; }
     if (!longest && (suffixes || max_len)) { std::cerr << "error: --suffixes and --max-len belong to --longest" << std::endl; usage(); return EXIT_FAILURE; }
     std::string text, lines;
     if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     if (!read_file(queries, lines)) { std::cerr << "error: cannot open " << queries << std::endl; return EXIT_FAILURE; }
     std::vector<uint64_t> soff;
-    if (set) {                                        // the strings are the runs between '\n', laid back to back (gsac)
-        std::string flat;
-        flat.reserve(text.size());
-        soff.push_back(0);
-        for (std::size_t b = 0; b < text.size();) {
-            std::size_t e = text.find('\n', b);
-            if (e == std::string::npos) e = text.size();
-            if (e > b) { flat.append(text, b, e - b); soff.push_back(flat.size()); }
-            b = e + 1;
-        }
-        text.swap(flat);
-    }
+    if (set) { std::string flat; split_lines(text, flat, soff); text.swap(flat); }
     if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
     // one pattern per line; a last line without its newline counts
     std::string pat;
@@ -269,7 +210,7 @@ int main(int argc, char** argv) {
         poff.push_back(pat.size());
         b = e + 1;
     }
-    const bool use32 = index == "32" || (index == "auto" && text.size() < 0xFFFFFFFEull);
+    const bool narrow = use32(index, text.size());
     try {
         std::ofstream f;
         if (!outfile.empty()) {
@@ -277,7 +218,7 @@ int main(int argc, char** argv) {
             if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
         }
         std::ostream& out = outfile.empty() ? std::cout : f;
-        const int rc = use32 ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out)
+        const int rc = narrow ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out)
                              : run<uint64_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out);
         out.flush();
         if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }

@@ -14,7 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/psacx.h"
+#include "query_cli.hpp"
+
+using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: lz77 -f <text> [--index 32|64|auto] [-c] [--list] [--device N]\n"
@@ -22,18 +24,6 @@ static void usage() {
                  "-c checks on the device that the parse decodes to the text; --list prints \"start len src\" per phrase.\n";
 }
 
-static void must(psacx_ctx* c, int rc) {
-    if (rc == PSACX_OK) return;
-    std::string msg = std::string("psacx: ") + psacx_strerror(rc);
-    const char* detail = c ? psacx_last_hip_error(c) : "";
-    if (detail && detail[0]) msg += std::string(" [") + detail + "]";
-    throw std::runtime_error(msg);
-}
-
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, uint32_t* sa, uint32_t* isa, uint32_t* lcp) { return psacx_construct_dev_u32(c, t, n, 0, PSACX_LCP, sa, isa, lcp); }
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, uint64_t* sa, uint64_t* isa, uint64_t* lcp) { return psacx_construct_dev_u64(c, t, n, 0, PSACX_LCP, sa, isa, lcp); }
-static int rmq_index(psacx_ctx* c, const uint32_t* v, uint64_t n, uint32_t* index, uint64_t* e) { return psacx_rmq_index_dev_u32(c, v, n, index, e); }
-static int rmq_index(psacx_ctx* c, const uint64_t* v, uint64_t n, uint64_t* index, uint64_t* e) { return psacx_rmq_index_dev_u64(c, v, n, index, e); }
 static int lpf(psacx_ctx* c, uint64_t n, const uint32_t* sa, const uint32_t* lcp, const uint32_t* index, uint32_t* l, uint32_t* s) { return psacx_lpf_dev_u32(c, n, sa, lcp, index, l, s); }
 static int lpf(psacx_ctx* c, uint64_t n, const uint64_t* sa, const uint64_t* lcp, const uint64_t* index, uint64_t* l, uint64_t* s) { return psacx_lpf_dev_u64(c, n, sa, lcp, index, l, s); }
 static int parse(psacx_ctx* c, uint64_t n, const uint32_t* l, const uint32_t* s, uint32_t* start, uint32_t* psrc, uint64_t cap, uint64_t* z) { return psacx_lz77_dev_u32(c, n, l, s, start, psrc, cap, z); }
@@ -41,77 +31,53 @@ static int parse(psacx_ctx* c, uint64_t n, const uint64_t* l, const uint64_t* s,
 static int verdict(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* start, const uint32_t* psrc, uint64_t z, uint64_t* e) { return psacx_check_lz77_dev_u32(c, t, n, start, psrc, z, e); }
 static int verdict(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* start, const uint64_t* psrc, uint64_t z, uint64_t* e) { return psacx_check_lz77_dev_u64(c, t, n, start, psrc, z, e); }
 
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 template <typename IT>
 static int run(const std::string& text, bool check, bool list, int device) {
     const uint64_t n = text.size();
-    psacx_ctx* c = nullptr;
-    must(nullptr, psacx_create(&c, device, nullptr));
-    std::vector<void*> held;
-    auto dev = [&](uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1)); held.push_back(p); return p; };
-    auto release = [&]() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); };
+    Session s(device);
+    psacx_ctx* const c = s.c;
     int rc = 0;
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        uint8_t* d_text = (uint8_t*)dev(n);
-        IT* d_sa = (IT*)dev(n * sizeof(IT));
-        IT* d_isa = (IT*)dev(n * sizeof(IT));
-        IT* d_lcp = (IT*)dev(n * sizeof(IT));
-        must(c, psacx_copy_h2d(c, d_text, text.data(), n));
-        must(c, construct(c, d_text, n, d_sa, d_isa, d_lcp));
-        std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
-        auto t1 = std::chrono::steady_clock::now();
-        uint64_t entries = 0;
-        must(c, rmq_index(c, (const IT*)nullptr, n, (IT*)nullptr, &entries));
-        IT* d_index = (IT*)dev(entries * sizeof(IT));
-        must(c, rmq_index(c, d_lcp, n, d_index, &entries));
-        std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
-        IT* d_lpf = d_isa;                                             // ISA is not needed any more
-        IT* d_src = (IT*)dev(n * sizeof(IT));
-        auto t2 = std::chrono::steady_clock::now();
-        must(c, lpf(c, n, d_sa, d_lcp, d_index, d_lpf, d_src));
-        std::cerr << "LPF time: " << ms_since(t2) << " ms" << std::endl;
-        auto t3 = std::chrono::steady_clock::now();
-        uint64_t z = 0;
-        must(c, parse(c, n, d_lpf, d_src, (IT*)nullptr, (IT*)nullptr, 0, &z));
-        IT* d_start = (IT*)dev((z + 1) * sizeof(IT));
-        IT* d_psrc = (IT*)dev((z + 1) * sizeof(IT));
-        must(c, parse(c, n, d_lpf, d_src, d_start, d_psrc, z + 1, &z));
-        std::cerr << "Parse time: " << ms_since(t3) << " ms" << std::endl;
-        std::cout << "z: " << z << " n/z: " << (double)n / (double)z << '\n';
-        if (check) {
-            uint64_t errors = 0;
-            must(c, verdict(c, d_text, n, d_start, d_psrc, z, &errors));
-            std::cout << "errors: " << errors << '\n';
-            if (errors) rc = EXIT_FAILURE;
-        }
-        if (list) {
-            std::vector<IT> start(z + 1), psrc(z + 1);
-            must(c, psacx_copy_d2h(c, start.data(), d_start, (z + 1) * sizeof(IT)));
-            must(c, psacx_copy_d2h(c, psrc.data(), d_psrc, z * sizeof(IT)));
-            for (uint64_t k = 0; k < z; ++k) {
-                std::cout << (uint64_t)start[k] << ' ' << (uint64_t)(start[k + 1] - start[k]) << ' ';
-                if (psrc[k] == (IT)~(IT)0) std::cout << "-\n"; else std::cout << (uint64_t)psrc[k] << '\n';
-            }
-        }
-    } catch (...) {
-        release();
-        throw;
+    auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d_text = (uint8_t*)s.dev(n);
+    IT* d_sa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_isa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_lcp = (IT*)s.dev(n * sizeof(IT));
+    must(c, psacx_copy_h2d(c, d_text, text.data(), n));
+    must(c, construct(c, d_text, n, nullptr, 0, PSACX_LCP, d_sa, d_isa, d_lcp));
+    std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+    auto t1 = std::chrono::steady_clock::now();
+    uint64_t entries = 0;
+    IT* d_index = rmq_index_of<IT>(s, d_lcp, n, &entries);
+    std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
+    IT* d_lpf = d_isa;                                             // ISA is not needed any more
+    IT* d_src = (IT*)s.dev(n * sizeof(IT));
+    auto t2 = std::chrono::steady_clock::now();
+    must(c, lpf(c, n, d_sa, d_lcp, d_index, d_lpf, d_src));
+    std::cerr << "LPF time: " << ms_since(t2) << " ms" << std::endl;
+    auto t3 = std::chrono::steady_clock::now();
+    uint64_t z = 0;
+    must(c, parse(c, n, d_lpf, d_src, (IT*)nullptr, (IT*)nullptr, 0, &z));
+    IT* d_start = (IT*)s.dev((z + 1) * sizeof(IT));
+    IT* d_psrc = (IT*)s.dev((z + 1) * sizeof(IT));
+    must(c, parse(c, n, d_lpf, d_src, d_start, d_psrc, z + 1, &z));
+    std::cerr << "Parse time: " << ms_since(t3) << " ms" << std::endl;
+    std::cout << "z: " << z << " n/z: " << (double)n / (double)z << '\n';
+    if (check) {
+        uint64_t errors = 0;
+        must(c, verdict(c, d_text, n, d_start, d_psrc, z, &errors));
+        std::cout << "errors: " << errors << '\n';
+        if (errors) rc = EXIT_FAILURE;
     }
-    release();
+    if (list) {
+        std::vector<IT> start(z + 1), psrc(z + 1);
+        must(c, psacx_copy_d2h(c, start.data(), d_start, (z + 1) * sizeof(IT)));
+        must(c, psacx_copy_d2h(c, psrc.data(), d_psrc, z * sizeof(IT)));
+        for (uint64_t k = 0; k < z; ++k) {
+            std::cout << (uint64_t)start[k] << ' ' << (uint64_t)(start[k + 1] - start[k]) << ' ';
+            if (psrc[k] == (IT)~(IT)0) std::cout << "-\n"; else std::cout << (uint64_t)psrc[k] << '\n';
+        }
+    }
     return rc;
-}
-
-static bool read_file(const std::string& fn, std::string& into) {
-    std::ifstream f(fn.c_str(), std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    into.resize((std::size_t)f.tellg());
-    f.seekg(0);
-    if (!into.empty()) f.read(&into[0], (std::streamsize)into.size());
-    return true;
 }
 
 int main(int argc, char** argv) {
@@ -132,13 +98,13 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
-    if (file.empty() || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    if (file.empty() || !index_known(index)) { usage(); return EXIT_FAILURE; }
     std::string text;
     if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
-    const bool use32 = index == "32" || (index == "auto" && text.size() < 0xFFFFFFFEull);
+    const bool narrow = use32(index, text.size());
     try {
-        const int rc = use32 ? run<uint32_t>(text, check, list, device) : run<uint64_t>(text, check, list, device);
+        const int rc = narrow ? run<uint32_t>(text, check, list, device) : run<uint64_t>(text, check, list, device);
         std::cout.flush();
         if (!std::cout) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

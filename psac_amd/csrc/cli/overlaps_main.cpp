@@ -16,7 +16,9 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/psacx.h"
+#include "query_cli.hpp"
+
+using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: overlaps -f <reads, one per line> [-l MINLEN] [--whole] [--list [LIMIT]] [--index 32|64|auto] [--device N] [-o <file>]\n"
@@ -24,22 +26,6 @@ static void usage() {
                  "--list prints \"target source length\" per overlap; --whole includes overlaps as long as the whole target.\n";
 }
 
-static void must(psacx_ctx* c, int rc) {
-    if (rc == PSACX_OK) return;
-    std::string msg = std::string("psacx: ") + psacx_strerror(rc);
-    const char* detail = c ? psacx_last_hip_error(c) : "";
-    if (detail && detail[0]) msg += std::string(" [") + detail + "]";
-    throw std::runtime_error(msg);
-}
-
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint32_t* sa, uint32_t* isa, uint32_t* lcp) {
-    return psacx_construct_gsa_dev_u32(c, t, n, off, m, 0, PSACX_LCP, sa, isa, lcp);
-}
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint64_t* sa, uint64_t* isa, uint64_t* lcp) {
-    return psacx_construct_gsa_dev_u64(c, t, n, off, m, 0, PSACX_LCP, sa, isa, lcp);
-}
-static int rmq_index(psacx_ctx* c, const uint32_t* v, uint64_t n, uint32_t* index, uint64_t* e) { return psacx_rmq_index_dev_u32(c, v, n, index, e); }
-static int rmq_index(psacx_ctx* c, const uint64_t* v, uint64_t n, uint64_t* index, uint64_t* e) { return psacx_rmq_index_dev_u64(c, v, n, index, e); }
 static int overlaps(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* ends, const uint32_t* sa, const uint32_t* isa, const uint32_t* lcp,
                     const uint32_t* index, uint64_t l, uint32_t f, uint32_t* lb, uint32_t* ub) {
     return psacx_overlaps_dev_u32(c, n, off, m, ends, sa, isa, lcp, index, l, f, lb, ub);
@@ -48,98 +34,61 @@ static int overlaps(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, c
                     const uint64_t* index, uint64_t l, uint32_t f, uint64_t* lb, uint64_t* ub) {
     return psacx_overlaps_dev_u64(c, n, off, m, ends, sa, isa, lcp, index, l, f, lb, ub);
 }
-static int occurrences(psacx_ctx* c, const uint32_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* lb, const uint32_t* ub, uint64_t q,
-                       uint64_t limit, uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total) {
-    return psacx_occurrences_dev_u32(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
-}
-static int occurrences(psacx_ctx* c, const uint64_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* lb, const uint64_t* ub, uint64_t q,
-                       uint64_t limit, uint64_t* start, uint64_t* pos, uint64_t* sid, uint64_t cap, uint64_t* total) {
-    return psacx_occurrences_dev_u64(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
-}
-
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 template <typename IT>
 static int run(const std::string& text, const std::vector<uint64_t>& soff, uint64_t min_len, bool whole, bool list, uint64_t limit, int device,
                std::ostream& out) {
     const uint64_t n = text.size(), m = soff.size() - 1;
-    psacx_ctx* c = nullptr;
-    must(nullptr, psacx_create(&c, device, nullptr));
-    std::vector<void*> held;
-    auto dev = [&](uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1)); held.push_back(p); return p; };
-    auto release = [&]() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); };
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        uint8_t* d_text = (uint8_t*)dev(n);
-        IT* d_sa = (IT*)dev(n * sizeof(IT));
-        IT* d_isa = (IT*)dev(n * sizeof(IT));
-        IT* d_lcp = (IT*)dev(n * sizeof(IT));
-        uint64_t* d_soff = (uint64_t*)dev((m + 1) * sizeof(uint64_t));
-        must(c, psacx_copy_h2d(c, d_text, text.data(), n));
-        must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
-        must(c, construct(c, d_text, n, d_soff, m, d_sa, d_isa, d_lcp));
-        std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
-        auto t1 = std::chrono::steady_clock::now();
-        uint64_t entries = 0, words = 0;
-        must(c, rmq_index(c, (const IT*)nullptr, n, (IT*)nullptr, &entries));
-        IT* d_index = (IT*)dev(entries * sizeof(IT));
-        must(c, rmq_index(c, d_lcp, n, d_index, &entries));
-        must(c, psacx_string_ends_dev(c, nullptr, m, n, nullptr, &words));
-        uint32_t* d_ends = (uint32_t*)dev(words * sizeof(uint32_t));
-        must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
-        std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
-        IT* d_lb = (IT*)dev(n * sizeof(IT));
-        IT* d_ub = (IT*)dev(n * sizeof(IT));
-        auto t2 = std::chrono::steady_clock::now();
-        must(c, overlaps(c, n, d_soff, m, d_ends, d_sa, d_isa, d_lcp, d_index, min_len, whole ? PSACX_OVERLAP_WHOLE : 0u, d_lb, d_ub));
-        std::cerr << "Overlaps time: " << ms_since(t2) << " ms" << std::endl;
-        std::vector<IT> lb(n), ub(n);
-        must(c, psacx_copy_d2h(c, lb.data(), d_lb, n * sizeof(IT)));
-        must(c, psacx_copy_d2h(c, ub.data(), d_ub, n * sizeof(IT)));
-        uint64_t slots = 0, pairs = 0;
-        for (uint64_t p = 0; p < n; ++p) if (ub[p] > lb[p]) { ++slots; pairs += (uint64_t)(ub[p] - lb[p]); }
-        std::cerr << "slots: " << slots << " pairs: " << pairs << std::endl;
-        if (list) {
-            auto t3 = std::chrono::steady_clock::now();
-            uint64_t* d_start = (uint64_t*)dev((n + 1) * sizeof(uint64_t));
-            uint64_t total = 0;
-            must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, n, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
-            IT* d_pos = (IT*)dev(total * sizeof(IT));
-            IT* d_sid = (IT*)dev(total * sizeof(IT));
-            must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, n, limit, d_start, d_pos, d_sid, total, &total));
-            std::cerr << "List time: " << ms_since(t3) << " ms" << std::endl;
-            std::vector<uint64_t> start(n + 1);
-            std::vector<IT> sid(total);
-            must(c, psacx_copy_d2h(c, start.data(), d_start, (n + 1) * sizeof(uint64_t)));
-            if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT)));
-            uint64_t j = 0;
-            for (uint64_t p = 0; p < n; ++p) {                         // slot p = o_j + d - 1
-                while (soff[j + 1] <= p) ++j;
-                for (uint64_t t = start[p]; t < start[p + 1]; ++t) out << j << ' ' << (uint64_t)sid[t] << ' ' << (p - soff[j] + 1) << '\n';
-            }
+    Session s(device);
+    psacx_ctx* const c = s.c;
+    auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d_text = (uint8_t*)s.dev(n);
+    IT* d_sa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_isa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_lcp = (IT*)s.dev(n * sizeof(IT));
+    uint64_t* d_soff = (uint64_t*)s.dev((m + 1) * sizeof(uint64_t));
+    must(c, psacx_copy_h2d(c, d_text, text.data(), n));
+    must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
+    must(c, construct(c, d_text, n, d_soff, m, PSACX_LCP, d_sa, d_isa, d_lcp));
+    std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+    auto t1 = std::chrono::steady_clock::now();
+    uint64_t entries = 0, words = 0;
+    IT* d_index = rmq_index_of<IT>(s, d_lcp, n, &entries);
+    must(c, psacx_string_ends_dev(c, nullptr, m, n, nullptr, &words));
+    uint32_t* d_ends = (uint32_t*)s.dev(words * sizeof(uint32_t));
+    must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
+    std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
+    IT* d_lb = (IT*)s.dev(n * sizeof(IT));
+    IT* d_ub = (IT*)s.dev(n * sizeof(IT));
+    auto t2 = std::chrono::steady_clock::now();
+    must(c, overlaps(c, n, d_soff, m, d_ends, d_sa, d_isa, d_lcp, d_index, min_len, whole ? PSACX_OVERLAP_WHOLE : 0u, d_lb, d_ub));
+    std::cerr << "Overlaps time: " << ms_since(t2) << " ms" << std::endl;
+    std::vector<IT> lb(n), ub(n);
+    must(c, psacx_copy_d2h(c, lb.data(), d_lb, n * sizeof(IT)));
+    must(c, psacx_copy_d2h(c, ub.data(), d_ub, n * sizeof(IT)));
+    uint64_t slots = 0, pairs = 0;
+    for (uint64_t p = 0; p < n; ++p) if (ub[p] > lb[p]) { ++slots; pairs += (uint64_t)(ub[p] - lb[p]); }
+    std::cerr << "slots: " << slots << " pairs: " << pairs << std::endl;
+    if (list) {
+        auto t3 = std::chrono::steady_clock::now();
+        uint64_t* d_start = (uint64_t*)s.dev((n + 1) * sizeof(uint64_t));
+        uint64_t total = 0;
+        must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, n, limit, d_start, (IT*)nullptr, (IT*)nullptr, 0, &total));
+        IT* d_pos = (IT*)s.dev(total * sizeof(IT));
+        IT* d_sid = (IT*)s.dev(total * sizeof(IT));
+        must(c, occurrences(c, d_sa, n, d_soff, m, d_lb, d_ub, n, limit, d_start, d_pos, d_sid, total, &total));
+        std::cerr << "List time: " << ms_since(t3) << " ms" << std::endl;
+        std::vector<uint64_t> start(n + 1);
+        std::vector<IT> sid(total);
+        must(c, psacx_copy_d2h(c, start.data(), d_start, (n + 1) * sizeof(uint64_t)));
+        if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT)));
+        uint64_t j = 0;
+        for (uint64_t p = 0; p < n; ++p) {                         // slot p = o_j + d - 1
+            while (soff[j + 1] <= p) ++j;
+            for (uint64_t t = start[p]; t < start[p + 1]; ++t) out << j << ' ' << (uint64_t)sid[t] << ' ' << (p - soff[j] + 1) << '\n';
         }
-    } catch (...) {
-        release();
-        throw;
     }
-    release();
     return 0;
-}
-
-static bool read_file(const std::string& fn, std::string& into) {
-    std::ifstream f(fn.c_str(), std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    into.resize((std::size_t)f.tellg());
-    f.seekg(0);
-    if (!into.empty()) f.read(&into[0], (std::streamsize)into.size());
-    return true;
-}
-
-static bool number(const char* w) {
-    const std::string s = w;
-    return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos;
 }
 
 int main(int argc, char** argv) {
@@ -167,20 +116,14 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
-    if (file.empty() || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    if (file.empty() || !index_known(index)) { usage(); return EXIT_FAILURE; }
     if (min_len == 0) { std::cerr << "error: the minimum length must be at least 1" << std::endl; return EXIT_FAILURE; }
     std::string raw, text;
     if (!read_file(file, raw)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
-    std::vector<uint64_t> soff(1, 0);                  // the strings are the runs between '\n', laid back to back (gsac)
-    text.reserve(raw.size());
-    for (std::size_t b = 0; b < raw.size();) {
-        std::size_t en = raw.find('\n', b);
-        if (en == std::string::npos) en = raw.size();
-        if (en > b) { text.append(raw, b, en - b); soff.push_back(text.size()); }
-        b = en + 1;
-    }
+    std::vector<uint64_t> soff;
+    split_lines(raw, text, soff);
     if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
-    const bool use32 = index == "32" || (index == "auto" && text.size() < 0xFFFFFFFEull);
+    const bool narrow = use32(index, text.size());
     try {
         std::ofstream f;
         if (!outfile.empty()) {
@@ -188,7 +131,7 @@ int main(int argc, char** argv) {
             if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
         }
         std::ostream& out = outfile.empty() ? std::cout : f;
-        const int rc = use32 ? run<uint32_t>(text, soff, min_len, whole, list, limit, device, out) : run<uint64_t>(text, soff, min_len, whole, list, limit, device, out);
+        const int rc = narrow ? run<uint32_t>(text, soff, min_len, whole, list, limit, device, out) : run<uint64_t>(text, soff, min_len, whole, list, limit, device, out);
         out.flush();
         if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

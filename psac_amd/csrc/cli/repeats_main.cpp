@@ -15,7 +15,9 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/psacx.h"
+#include "query_cli.hpp"
+
+using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: repeats -f <text> [--set] [--index 32|64|auto] [--kind right|maximal|super] [-l MINLEN] [--min-occ K] [--max-occ K]\n"
@@ -25,22 +27,6 @@ static void usage() {
                  "repeat: it is the len bytes at pos and occurs at SA[lb .. ub).  --bwt writes the SA-aligned BWT and prints the primary.\n";
 }
 
-static void must(psacx_ctx* c, int rc) {
-    if (rc == PSACX_OK) return;
-    std::string msg = std::string("psacx: ") + psacx_strerror(rc);
-    const char* detail = c ? psacx_last_hip_error(c) : "";
-    if (detail && detail[0]) msg += std::string(" [") + detail + "]";
-    throw std::runtime_error(msg);
-}
-
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint32_t* sa, uint32_t* isa, uint32_t* lcp) {
-    return off ? psacx_construct_gsa_dev_u32(c, t, n, off, m, 0, PSACX_LCP, sa, isa, lcp) : psacx_construct_dev_u32(c, t, n, 0, PSACX_LCP, sa, isa, lcp);
-}
-static int construct(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* off, uint64_t m, uint64_t* sa, uint64_t* isa, uint64_t* lcp) {
-    return off ? psacx_construct_gsa_dev_u64(c, t, n, off, m, 0, PSACX_LCP, sa, isa, lcp) : psacx_construct_dev_u64(c, t, n, 0, PSACX_LCP, sa, isa, lcp);
-}
-static int rmq_index(psacx_ctx* c, const uint32_t* v, uint64_t n, uint32_t* index, uint64_t* e) { return psacx_rmq_index_dev_u32(c, v, n, index, e); }
-static int rmq_index(psacx_ctx* c, const uint64_t* v, uint64_t n, uint64_t* index, uint64_t* e) { return psacx_rmq_index_dev_u64(c, v, n, index, e); }
 static int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, uint8_t* b, uint32_t* f, uint64_t* p) {
     return psacx_bwt_dev_u32(c, t, n, ends, sa, b, f, p);
 }
@@ -56,10 +42,6 @@ static int repeats(psacx_ctx* c, uint64_t n, const uint64_t* lcp, const uint64_t
     return psacx_repeats_dev_u64(c, n, lcp, index, b, f, kind, l, lo, hi, lb, ub, len, cap, z);
 }
 
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 struct Options {
     uint32_t kind;
     uint64_t min_len, min_occ, max_occ, limit;
@@ -71,94 +53,69 @@ struct Options {
 template <typename IT>
 static int run(const std::string& text, const std::vector<uint64_t>& soff, const Options& o) {
     const uint64_t n = text.size(), m = soff.empty() ? 0 : soff.size() - 1;
-    psacx_ctx* c = nullptr;
-    must(nullptr, psacx_create(&c, o.device, nullptr));
-    std::vector<void*> held;
-    auto dev = [&](uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1)); held.push_back(p); return p; };
-    auto release = [&]() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); };
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        uint8_t* d_text = (uint8_t*)dev(n);
-        IT* d_sa = (IT*)dev(n * sizeof(IT));
-        IT* d_isa = (IT*)dev(n * sizeof(IT));
-        IT* d_lcp = (IT*)dev(n * sizeof(IT));
-        uint64_t* d_soff = nullptr;
-        must(c, psacx_copy_h2d(c, d_text, text.data(), n));
-        if (m) {
-            d_soff = (uint64_t*)dev((m + 1) * sizeof(uint64_t));
-            must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
-        }
-        must(c, construct(c, d_text, n, d_soff, m, d_sa, d_isa, d_lcp));
-        std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
-        auto t1 = std::chrono::steady_clock::now();
-        uint64_t entries = 0, words = (n >> 5) + 1;
-        must(c, rmq_index(c, (const IT*)nullptr, n, (IT*)nullptr, &entries));
-        IT* d_index = (IT*)dev(entries * sizeof(IT));
-        must(c, rmq_index(c, d_lcp, n, d_index, &entries));
-        uint32_t* d_ends = nullptr;
-        if (m) {
-            d_ends = (uint32_t*)dev(words * sizeof(uint32_t));
-            must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
-        }
-        std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
-        auto t2 = std::chrono::steady_clock::now();
-        uint8_t* d_bwt = (uint8_t*)dev(n);
-        uint32_t* d_first = (uint32_t*)dev(words * sizeof(uint32_t));
-        uint64_t primary = 0;
-        must(c, bwt(c, d_text, n, d_ends, d_sa, d_bwt, d_first, &primary));
-        std::cerr << "BWT time: " << ms_since(t2) << " ms" << std::endl;
-        auto t3 = std::chrono::steady_clock::now();
-        uint64_t z = 0;
-        must(c, repeats(c, n, d_lcp, d_index, d_bwt, d_first, o.kind, o.min_len, o.min_occ, o.max_occ, (IT*)nullptr, (IT*)nullptr, (IT*)nullptr, 0, &z));
-        IT *d_lb = nullptr, *d_ub = nullptr, *d_len = nullptr;
-        if (o.list) {
-            d_lb = (IT*)dev(z * sizeof(IT)); d_ub = (IT*)dev(z * sizeof(IT)); d_len = (IT*)dev(z * sizeof(IT));
-            must(c, repeats(c, n, d_lcp, d_index, d_bwt, d_first, o.kind, o.min_len, o.min_occ, o.max_occ, d_lb, d_ub, d_len, z, &z));
-        }
-        std::cerr << "Repeats time: " << ms_since(t3) << " ms" << std::endl;
-        std::cout << "z: " << z << '\n';
-        if (!o.bwt_out.empty()) {
-            std::string b(n, '\0');
-            must(c, psacx_copy_d2h(c, &b[0], d_bwt, n));
-            std::ofstream f(o.bwt_out.c_str(), std::ios::binary | std::ios::trunc);
-            f.write(b.data(), (std::streamsize)n);
-            f.flush();
-            if (!f) throw std::runtime_error("cannot write " + o.bwt_out);
-            std::cout << "primary: " << primary << '\n';
-        }
-        if (o.list && z) {
-            std::vector<IT> lb(z), ub(z), len(z), sa(n);
-            must(c, psacx_copy_d2h(c, lb.data(), d_lb, z * sizeof(IT)));
-            must(c, psacx_copy_d2h(c, ub.data(), d_ub, z * sizeof(IT)));
-            must(c, psacx_copy_d2h(c, len.data(), d_len, z * sizeof(IT)));
-            must(c, psacx_copy_d2h(c, sa.data(), d_sa, n * sizeof(IT)));
-            const uint64_t shown = o.limit && o.limit < z ? o.limit : z;
-            for (uint64_t k = 0; k < shown; ++k) {
-                uint64_t pos = (uint64_t)sa[lb[k]];                 // the first occurrence in the text
-                for (uint64_t r = (uint64_t)lb[k]; r < (uint64_t)ub[k]; ++r) if ((uint64_t)sa[r] < pos) pos = (uint64_t)sa[r];
-                std::cout << (uint64_t)lb[k] << ' ' << (uint64_t)ub[k] << ' ' << (uint64_t)len[k] << ' ' << pos << '\n';
-            }
-        }
-    } catch (...) {
-        release();
-        throw;
+    Session s(o.device);
+    psacx_ctx* const c = s.c;
+    auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d_text = (uint8_t*)s.dev(n);
+    IT* d_sa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_isa = (IT*)s.dev(n * sizeof(IT));
+    IT* d_lcp = (IT*)s.dev(n * sizeof(IT));
+    uint64_t* d_soff = nullptr;
+    must(c, psacx_copy_h2d(c, d_text, text.data(), n));
+    if (m) {
+        d_soff = (uint64_t*)s.dev((m + 1) * sizeof(uint64_t));
+        must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
     }
-    release();
+    must(c, construct(c, d_text, n, d_soff, m, PSACX_LCP, d_sa, d_isa, d_lcp));
+    std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
+    auto t1 = std::chrono::steady_clock::now();
+    uint64_t entries = 0, words = (n >> 5) + 1;
+    IT* d_index = rmq_index_of<IT>(s, d_lcp, n, &entries);
+    uint32_t* d_ends = nullptr;
+    if (m) {
+        d_ends = (uint32_t*)s.dev(words * sizeof(uint32_t));
+        must(c, psacx_string_ends_dev(c, d_soff, m, n, d_ends, &words));
+    }
+    std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
+    auto t2 = std::chrono::steady_clock::now();
+    uint8_t* d_bwt = (uint8_t*)s.dev(n);
+    uint32_t* d_first = (uint32_t*)s.dev(words * sizeof(uint32_t));
+    uint64_t primary = 0;
+    must(c, bwt(c, d_text, n, d_ends, d_sa, d_bwt, d_first, &primary));
+    std::cerr << "BWT time: " << ms_since(t2) << " ms" << std::endl;
+    auto t3 = std::chrono::steady_clock::now();
+    uint64_t z = 0;
+    must(c, repeats(c, n, d_lcp, d_index, d_bwt, d_first, o.kind, o.min_len, o.min_occ, o.max_occ, (IT*)nullptr, (IT*)nullptr, (IT*)nullptr, 0, &z));
+    IT *d_lb = nullptr, *d_ub = nullptr, *d_len = nullptr;
+    if (o.list) {
+        d_lb = (IT*)s.dev(z * sizeof(IT)); d_ub = (IT*)s.dev(z * sizeof(IT)); d_len = (IT*)s.dev(z * sizeof(IT));
+        must(c, repeats(c, n, d_lcp, d_index, d_bwt, d_first, o.kind, o.min_len, o.min_occ, o.max_occ, d_lb, d_ub, d_len, z, &z));
+    }
+    std::cerr << "Repeats time: " << ms_since(t3) << " ms" << std::endl;
+    std::cout << "z: " << z << '\n';
+    if (!o.bwt_out.empty()) {
+        std::string b(n, '\0');
+        must(c, psacx_copy_d2h(c, &b[0], d_bwt, n));
+        std::ofstream f(o.bwt_out.c_str(), std::ios::binary | std::ios::trunc);
+        f.write(b.data(), (std::streamsize)n);
+        f.flush();
+        if (!f) throw std::runtime_error("cannot write " + o.bwt_out);
+        std::cout << "primary: " << primary << '\n';
+    }
+    if (o.list && z) {
+        std::vector<IT> lb(z), ub(z), len(z), sa(n);
+        must(c, psacx_copy_d2h(c, lb.data(), d_lb, z * sizeof(IT)));
+        must(c, psacx_copy_d2h(c, ub.data(), d_ub, z * sizeof(IT)));
+        must(c, psacx_copy_d2h(c, len.data(), d_len, z * sizeof(IT)));
+        must(c, psacx_copy_d2h(c, sa.data(), d_sa, n * sizeof(IT)));
+        const uint64_t shown = o.limit && o.limit < z ? o.limit : z;
+        for (uint64_t k = 0; k < shown; ++k) {
+            uint64_t pos = (uint64_t)sa[lb[k]];                 // the first occurrence in the text
+            for (uint64_t r = (uint64_t)lb[k]; r < (uint64_t)ub[k]; ++r) if ((uint64_t)sa[r] < pos) pos = (uint64_t)sa[r];
+            std::cout << (uint64_t)lb[k] << ' ' << (uint64_t)ub[k] << ' ' << (uint64_t)len[k] << ' ' << pos << '\n';
+        }
+    }
     return 0;
-}
-
-static bool read_file(const std::string& fn, std::string& into) {
-    std::ifstream f(fn.c_str(), std::ios::binary | std::ios::ate);
-    if (!f) return false;
-    into.resize((std::size_t)f.tellg());
-    f.seekg(0);
-    if (!into.empty()) f.read(&into[0], (std::streamsize)into.size());
-    return true;
-}
-
-static bool number(const char* w) {
-    const std::string s = w;
-    return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos;
 }
 
 int main(int argc, char** argv) {
@@ -194,24 +151,15 @@ int main(int argc, char** argv) {
     else if (kind == "maximal") o.kind = PSACX_REPEATS_MAXIMAL;
     else if (kind == "super" || kind == "supermaximal") o.kind = PSACX_REPEATS_SUPERMAXIMAL;
     else { usage(); return EXIT_FAILURE; }
-    if (file.empty() || (index != "32" && index != "64" && index != "auto")) { usage(); return EXIT_FAILURE; }
+    if (file.empty() || !index_known(index)) { usage(); return EXIT_FAILURE; }
     std::string raw, text;
     if (!read_file(file, raw)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     std::vector<uint64_t> soff;
-    if (set) {                                         // the strings are the runs between '\n', laid back to back (gsac)
-        soff.push_back(0);
-        text.reserve(raw.size());
-        for (std::size_t b = 0; b < raw.size();) {
-            std::size_t en = raw.find('\n', b);
-            if (en == std::string::npos) en = raw.size();
-            if (en > b) { text.append(raw, b, en - b); soff.push_back(text.size()); }
-            b = en + 1;
-        }
-    } else text.swap(raw);
+    if (set) split_lines(raw, text, soff); else text.swap(raw);
     if (text.empty()) { std::cerr << "error: empty input" << std::endl; return EXIT_FAILURE; }
-    const bool use32 = index == "32" || (index == "auto" && text.size() < 0xFFFFFFFEull);
+    const bool narrow = use32(index, text.size());
     try {
-        const int rc = use32 ? run<uint32_t>(text, soff, o) : run<uint64_t>(text, soff, o);
+        const int rc = narrow ? run<uint32_t>(text, soff, o) : run<uint64_t>(text, soff, o);
         std::cout.flush();
         if (!std::cout) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

@@ -14,11 +14,6 @@
 
 namespace psacx {
 
-// check.hip: the offsets of a string set start at 0, end at n and ascend strictly (PSACX_EINVAL otherwise; waits); and the bitmap of
-// the string ends of valid offsets, queued on the ctx stream
-int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n);
-int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits);
-
 static const uint64_t LOCATE_MAX_KEYS = 1ull << 30;
 
 // B^k, or 0 if that exceeds LOCATE_MAX_KEYS
@@ -201,13 +196,7 @@ int search_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* o
     T* d_len = longest ? (T*)s.alloc(entries * sizeof(T)) : nullptr;
     T* d_lb = (T*)s.alloc(entries * sizeof(T));
     T* d_ub = (T*)s.alloc(entries * sizeof(T));
-    uint32_t* d_ends = nullptr;
-    if (offsets) {
-        const uint64_t* d_off = (const uint64_t*)s.upload(offsets, (m + 1) * sizeof(uint64_t));
-        d_ends = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
-        if (s.rc == PSACX_OK) s.rc = string_offsets_valid_dev(c, d_off, m, n);
-        if (s.rc == PSACX_OK) s.rc = string_ends_bitmap_dev(c, d_off, m, n, d_ends);
-    }
+    const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
     CodeTable tab;
     T* d_table = nullptr;
     if (s.rc == PSACX_OK && k) {                      // one histogram for the alphabet, then the table sized by it
@@ -272,8 +261,7 @@ int occurrences_dev(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_o
     return PSACX_OK;
 }
 
-// the scan for callers outside this file (lz.hip): a caller that keeps scratch of its own in the slab leaves the first
-// exclusive_scan_slab_bytes(len) bytes to the scan and sizes the slab before it places anything
+// the scan for callers outside this file (query_calls.hpp)
 int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len) { return exclusive_scan_dev<uint64_t>(c, d_a, len); }
 uint64_t exclusive_scan_slab_bytes(uint64_t len) {
     return (len + 256 * LOCATE_SCAN_ITEMS - 1) / (256 * LOCATE_SCAN_ITEMS) * sizeof(unsigned long long) + 4096;

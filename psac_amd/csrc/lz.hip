@@ -7,30 +7,15 @@
 
 namespace psacx {
 
-// ansv.hip: all nearest smaller values of an array in HBM into two arrays of n 64-bit entries (pyramid in the ctx slab; waits)
-int ansv_dev_u32(psacx_ctx* c, const uint32_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
-int ansv_dev_u64(psacx_ctx* c, const uint64_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
-// locate.hip: the scan of scan.hpp over 64-bit entries, queued on the ctx stream, and the bytes it takes at the base of the ctx slab
-int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len);
-uint64_t exclusive_scan_slab_bytes(uint64_t len);
 static int ansv_dev(psacx_ctx* c, const uint32_t* in, uint64_t n, uint64_t* l, uint64_t* r) { return ansv_dev_u32(c, in, n, 0, 0, ~0ull, l, r); }
 static int ansv_dev(psacx_ctx* c, const uint64_t* in, uint64_t n, uint64_t* l, uint64_t* r) { return ansv_dev_u64(c, in, n, 0, 0, ~0ull, l, r); }
-static int rmq_index(psacx_ctx* c, const uint32_t* v, uint64_t n, uint32_t* index, uint64_t* e) { return psacx_rmq_index_dev_u32(c, v, n, index, e); }
-static int rmq_index(psacx_ctx* c, const uint64_t* v, uint64_t n, uint64_t* index, uint64_t* e) { return psacx_rmq_index_dev_u64(c, v, n, index, e); }
-
-template <typename T>
-static int lz_check_n(uint64_t n) {
-    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
-    if (n > (1ull << 48)) return PSACX_ERANGE;        // the range-minimum index ends there (rmq.hip)
-    return PSACX_OK;
-}
 
 // psacx_lpf_dev_*: the neighbours of every rank (nearest smaller values of SA on both sides, 16 n bytes of memory of their own for
 // the time of the call), then one launch over the ranks.  Nothing is written before the memory is there.
 template <typename T>
 int lpf_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const T* d_LCP, const T* d_index, T* d_lpf, T* d_src) {
     if (!c) return PSACX_EINVAL;
-    PSACX_TRY(lz_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (!d_lpf || !d_src) return PSACX_EINVAL;
     if (n == 0) return PSACX_OK;
     if (!d_SA || !d_LCP || !d_index) return PSACX_EINVAL;
@@ -57,7 +42,7 @@ template <typename T>
 int lz77_dev(psacx_ctx* c, uint64_t n, const T* d_lpf, const T* d_src, T* d_start, T* d_psrc, uint64_t cap, uint64_t* z) {
     if (!c || !z) return PSACX_EINVAL;
     *z = 0;
-    PSACX_TRY(lz_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (d_psrc && (!d_src || !d_start)) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     if (n == 0) {
@@ -91,14 +76,10 @@ int lz77_dev(psacx_ctx* c, uint64_t n, const T* d_lpf, const T* d_src, T* d_star
     hipLaunchKernelGGL((lz_mark_kernel<T>), dim3(grid), dim3(256), 0, c->stream, d_lpf, n, geo, ngroups,
                        (const uint64_t*)d_gentry, d_marks, d_counts);
     PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_counts, ntiles + 1));
-    PSACX_HIP(c, hipMemcpyAsync(z, d_counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PSACX_TRY(select_positions(c, d_counts, ntiles, false, z));      // (cleared above with the counts)
     if (!d_start) return PSACX_OK;                    // count query
     if (*z + 1 > cap) return PSACX_ERANGE;
-    hipLaunchKernelGGL((lz_emit_kernel<T>), dim3(grid_for(c, ntiles * 256, 256, 8)), dim3(256), 0, c->stream, d_lpf, d_src, n, geo.B, ntiles,
-                       (const unsigned char*)d_marks, (const uint64_t*)d_counts, d_start, d_psrc);
-    PSACX_HIP(c, hipGetLastError());
+    PSACX_HIP(c, select_emit(c, d_marks, geo.B, ntiles, d_counts, LzEmit<T>{d_lpf, d_src, n, d_start, d_psrc}));
     PSACX_HIP(c, hipStreamSynchronize(c->stream));
     return PSACX_OK;
 }
@@ -107,7 +88,7 @@ template <typename T>
 int check_lz77_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_start, const T* d_psrc, uint64_t z, uint64_t* errors) {
     if (!c || !errors) return PSACX_EINVAL;
     *errors = 0;
-    PSACX_TRY(lz_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (!d_start || (z && !d_psrc) || (n && !d_text) || z > n) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     PSACX_TRY(ensure_slab(c, 4096));
@@ -126,7 +107,7 @@ int check_lz77_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_s
 template <typename T>
 int lpf_host(psacx_ctx* c, uint64_t n, const T* SA, const T* LCP, T* lpf, T* src) {
     if (!c) return PSACX_EINVAL;
-    PSACX_TRY(lz_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (!lpf || !src) return PSACX_EINVAL;
     if (n == 0) return PSACX_OK;
     if (!SA || !LCP) return PSACX_EINVAL;
@@ -140,7 +121,7 @@ int lpf_host(psacx_ctx* c, uint64_t n, const T* SA, const T* LCP, T* lpf, T* src
     T* d_index = (T*)s.alloc(Y.entries * sizeof(T));
     T* d_lpf = (T*)s.alloc(n * sizeof(T));
     T* d_src = (T*)s.alloc(n * sizeof(T));
-    if (s.rc == PSACX_OK) s.rc = rmq_index(c, d_LCP, n, d_index, &entries);
+    if (s.rc == PSACX_OK) s.rc = rmq_index_dev<T>(c, d_LCP, n, d_index, &entries);
     if (s.rc == PSACX_OK) s.rc = lpf_dev<T>(c, n, d_SA, d_LCP, d_index, d_lpf, d_src);
     s.download(lpf, d_lpf, n * sizeof(T));
     s.download(src, d_src, n * sizeof(T));
@@ -153,7 +134,7 @@ template <typename T>
 int lz77_host(psacx_ctx* c, uint64_t n, const T* SA, const T* LCP, T* start, T* src, uint64_t cap, uint64_t* z) {
     if (!c || !z) return PSACX_EINVAL;
     *z = 0;
-    PSACX_TRY(lz_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if ((start == nullptr) != (src == nullptr)) return PSACX_EINVAL;
     if (n == 0) {
         if (start && cap < 1) return PSACX_ERANGE;
@@ -171,7 +152,7 @@ int lz77_host(psacx_ctx* c, uint64_t n, const T* SA, const T* LCP, T* start, T* 
     T* d_index = (T*)s.alloc(Y.entries * sizeof(T));
     T* d_lpf = (T*)s.alloc(n * sizeof(T));
     T* d_src = (T*)s.alloc(n * sizeof(T));
-    if (s.rc == PSACX_OK) s.rc = rmq_index(c, d_LCP, n, d_index, &entries);
+    if (s.rc == PSACX_OK) s.rc = rmq_index_dev<T>(c, d_LCP, n, d_index, &entries);
     if (s.rc == PSACX_OK) s.rc = lpf_dev<T>(c, n, d_SA, d_LCP, d_index, d_lpf, d_src);
     if (s.rc == PSACX_OK) s.rc = lz77_dev<T>(c, n, d_lpf, d_src, (T*)nullptr, (T*)nullptr, 0, z);
     if (s.rc != PSACX_OK || !start) return s.rc;

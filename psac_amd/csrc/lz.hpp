@@ -18,18 +18,21 @@
 //  3. lz_mark_kernel: a workgroup per entered group goes through its tiles from the first to the last; in a tile that holds the
 //     running position the same doubling carries a mark along (after round k the first 2^(k+1) chain positions are marked), and
 //     the running position becomes its exit.  G dependent tile loads per workgroup.
-//  4. the tile counts are scanned (scan.hpp, through locate.hip) and lz_emit_kernel writes the marked positions and their sources in order.
+//  4. the tile counts are scanned and the marked positions and their sources are written in order: the compaction of select.hpp, whose
+//     functor here is LzEmit.
 // No kernel holds a chain of dependent global loads longer than max(G, ceil(n / (B G))) (+ the scan's own).
 //
 // Check.  check_lz77_kernel: one lane per text position finds its phrase by a binary search in start and compares its byte with
 // the byte at the same offset of the source; one lane per phrase checks the order of the starts and the shape of the phrase.
 #pragma once
 #include "rmq.hpp"
+#include "select.hpp"
 
 namespace psacx {
 
-constexpr int LZ_TILE_MAX = 1024;                      // B: positions of a tile (4 per thread)
-constexpr int LZ_PER = 4;                              // marks a thread of lz_emit_kernel owns: one 32-bit word
+constexpr int LZ_TILE_MAX = 1024;                      // B: positions of a tile, at most
+constexpr int LZ_PER = LZ_TILE_MAX / 256;              // tile positions a thread of the doubling rounds owns
+static_assert((unsigned)LZ_TILE_MAX <= SELECT_TILE_MAX, "the compaction takes a tile per workgroup");
 
 struct LzGeometry {
     unsigned B, G, rounds;                             // rounds = ceil(log2(B))
@@ -198,32 +201,20 @@ __global__ __launch_bounds__(256) void lz_mark_kernel(const T* __restrict__ lpf,
     }
 }
 
-// counts: the exclusive sums of the tile counts, ntiles + 1 entries.  start[k], psrc[k] of the k-th marked position; start[z] = n.
+// The functor of select_emit_kernel: start[k], psrc[k] of the k-th marked position (psrc == nullptr: the starts alone); start[z] = n.
 template <typename T>
-__global__ __launch_bounds__(256) void lz_emit_kernel(const T* __restrict__ lpf, const T* __restrict__ src, uint64_t n, unsigned B, uint64_t ntiles,
-                                                      const unsigned char* __restrict__ marks, const uint64_t* __restrict__ counts,
-                                                      T* __restrict__ start, T* __restrict__ psrc) {
-    __shared__ uint32_t sh[256 / WAVE + 1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) start[counts[ntiles]] = (T)n;
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t base = counts[t];
-        if (counts[t + 1] == base) continue;
-        const uint64_t ts = t * B;
-        const unsigned j0 = threadIdx.x * LZ_PER;
-        uint32_t word = 0;
-        if (j0 < B) word = *reinterpret_cast<const uint32_t*>(marks + ts + j0);          // (B is a multiple of 4, marks holds whole tiles)
-        uint32_t total;
-        uint64_t at = base + block_scan_exclusive<256, uint32_t>((uint32_t)__popc(word), OpSum(), 0u, sh, &total);
-#pragma unroll
-        for (int d = 0; d < LZ_PER; ++d) {
-            if (!((word >> (8 * d)) & 0xFFu)) continue;
-            const uint64_t pos = ts + j0 + d;
-            start[at] = (T)pos;
-            if (psrc) psrc[at] = lpf[pos] == 0 ? ~(T)0 : src[pos];
-            ++at;
-        }
+struct LzEmit {
+    const T* __restrict__ lpf;
+    const T* __restrict__ src;
+    uint64_t n;
+    T* __restrict__ start;
+    T* __restrict__ psrc;
+    __device__ __forceinline__ void operator()(uint64_t at, uint64_t pos) const {
+        start[at] = (T)pos;
+        if (psrc) psrc[at] = lpf[pos] == 0 ? ~(T)0 : src[pos];
     }
-}
+    __device__ __forceinline__ void finish(uint64_t z) const { start[z] = (T)n; }
+};
 
 // the phrase of position x: the largest k < z with start[k] <= x as a bisection finds it (k = 0 where there is none); z >= 1
 template <typename T>

@@ -1,5 +1,6 @@
 // psacx_abi.hip -- extern "C" surface of libpsacx.so (include/psacx.h).
 #include "engine.hpp"
+#include "query_calls.hpp"      // ansv_dev_u32 / _u64
 
 namespace psacx {
 int construct_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*);
@@ -35,8 +36,6 @@ int check_suffix_tree_gsa_dev_u32(psacx_ctx*, const uint8_t*, uint64_t, const ui
 int check_suffix_tree_gsa_dev_u64(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*);
 int ansv_host_u32(psacx_ctx*, const uint32_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
 int ansv_host_u64(psacx_ctx*, const uint64_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
-int ansv_dev_u32(psacx_ctx*, const uint32_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
-int ansv_dev_u64(psacx_ctx*, const uint64_t*, uint64_t, int, int, uint64_t, uint64_t*, uint64_t*);
 }
 
 using namespace psacx;

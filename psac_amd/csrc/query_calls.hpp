@@ -1,0 +1,40 @@
+// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, and check.hip and
+// ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
+// that moves in one place alone does not compile.
+#pragma once
+#include "engine.hpp"
+
+namespace psacx {
+
+// check.hip: the m + 1 offsets of a string set on the device start at 0, end at n and ascend strictly (PSACX_EINVAL otherwise; uses the
+// first bytes of the ctx slab and waits); and the bitmap of the string ends of valid offsets into bits[(n >> 5) + 1], queued on the
+// ctx stream
+int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n);
+int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits);
+
+// locate.hip: the scan of scan.hpp over 64-bit entries, queued on the ctx stream, and the bytes it takes at the base of the ctx slab:
+// a caller that keeps scratch of its own in the slab leaves the first exclusive_scan_slab_bytes(len) bytes to the scan and sizes the
+// slab before it places anything
+int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len);
+uint64_t exclusive_scan_slab_bytes(uint64_t len);
+
+// ansv.hip: all nearest smaller values of an array in HBM into two arrays of n 64-bit entries (pyramid in the ctx slab; waits)
+int ansv_dev_u32(psacx_ctx* c, const uint32_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
+int ansv_dev_u64(psacx_ctx* c, const uint64_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
+
+// rmq.hip: psacx_rmq_index_dev_* itself (size query with d_index == nullptr; waits; keeps the psacx_profile bookkeeping), instantiated
+// there for both widths
+template <typename T>
+int rmq_index_dev(psacx_ctx* c, const T* d_values, uint64_t n, T* d_index, uint64_t* entries);
+
+constexpr uint64_t RMQ_MAX_N = 1ull << 48;             // 64^PYR_MAX: the top level of the range-minimum index is one group
+
+// n of a call that takes (or builds) the range-minimum index, with entries of type T
+template <typename T>
+inline int index_check_n(uint64_t n) {
+    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
+    if (n > RMQ_MAX_N) return PSACX_ERANGE;
+    return PSACX_OK;
+}
+
+} // namespace psacx

@@ -7,26 +7,13 @@
 
 namespace psacx {
 
-// locate.hip: the scan of scan.hpp over 64-bit entries, queued on the ctx stream, and the bytes it takes at the base of the ctx slab
-int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len);
-uint64_t exclusive_scan_slab_bytes(uint64_t len);
-static int rmq_index(psacx_ctx* c, const uint32_t* v, uint64_t n, uint32_t* index, uint64_t* e) { return psacx_rmq_index_dev_u32(c, v, n, index, e); }
-static int rmq_index(psacx_ctx* c, const uint64_t* v, uint64_t n, uint64_t* index, uint64_t* e) { return psacx_rmq_index_dev_u64(c, v, n, index, e); }
-
-template <typename T>
-static int repeats_check_n(uint64_t n) {
-    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
-    if (n > (1ull << 48)) return PSACX_ERANGE;        // the range-minimum index ends there (rmq.hip)
-    return PSACX_OK;
-}
-
 // psacx_bwt_dev_*: one launch over the ranks.  The primary travels through eight bytes of the ctx slab.
 template <typename T>
 int bwt_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, uint8_t* d_bwt, uint32_t* d_first,
             uint64_t* primary) {
     if (!c) return PSACX_EINVAL;
     if (primary) *primary = ~0ull;
-    PSACX_TRY(repeats_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (!d_bwt && !d_first) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     if (n == 0) {
@@ -57,7 +44,7 @@ int repeats_dev(psacx_ctx* c, uint64_t n, const T* d_LCP, const T* d_index, cons
                 uint64_t min_len, uint64_t min_occ, uint64_t max_occ, T* d_lb, T* d_ub, T* d_len, uint64_t cap, uint64_t* z) {
     if (!c || !z) return PSACX_EINVAL;
     *z = 0;
-    PSACX_TRY(repeats_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (kind > (uint32_t)REPEATS_SUPERMAXIMAL) return PSACX_EINVAL;
     if (kind != (uint32_t)REPEATS_RIGHT && (!d_bwt || !d_first)) return PSACX_EINVAL;
     if ((d_lb == nullptr) != (d_ub == nullptr) || (!d_lb && d_len)) return PSACX_EINVAL;
@@ -114,18 +101,13 @@ int repeats_dev(psacx_ctx* c, uint64_t n, const T* d_LCP, const T* d_index, cons
     else PSACX_REPEATS_LAUNCH(REPEATS_RIGHT);
 #undef PSACX_REPEATS_LAUNCH
     PSACX_HIP(c, hipGetLastError());
-    PSACX_HIP(c, hipMemsetAsync(d_counts + ntiles, 0, sizeof(uint64_t), c->stream));
-    hipLaunchKernelGGL(select_count_kernel, dim3(grid_for(c, ntiles * 256, 256, 8)), dim3(256), 0, c->stream, (const unsigned char*)d_sel, ntiles,
+    hipLaunchKernelGGL(select_count_kernel<REP_TILE>, dim3(grid_for(c, ntiles * 256, 256, 8)), dim3(256), 0, c->stream, (const unsigned char*)d_sel, ntiles,
                        d_counts);
     PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_counts, ntiles + 1));
-    PSACX_HIP(c, hipMemcpyAsync(z, d_counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PSACX_TRY(select_positions(c, d_counts, ntiles, true, z));
     if (!d_lb) return PSACX_OK;                       // count query
     if (*z > cap) return PSACX_ERANGE;
-    hipLaunchKernelGGL((repeats_emit_kernel<T>), dim3(grid_for(c, ntiles * 256, 256, 8)), dim3(256), 0, c->stream, d_LCP, n, ntiles,
-                       (const unsigned char*)d_sel, (const uint64_t*)d_counts, (const T*)d_clb, (const T*)d_cub, d_lb, d_ub, d_len);
-    s.step(hipGetLastError());
+    s.step(select_emit(c, d_sel, REP_TILE, ntiles, d_counts, RepeatsEmit<T>{d_LCP, d_clb, d_cub, d_lb, d_ub, d_len}));
     s.step(hipStreamSynchronize(c->stream));
     return s.rc;
 }
@@ -136,7 +118,7 @@ template <typename T>
 int bwt_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const T* SA, uint8_t* bwt, uint64_t* primary) {
     if (!c) return PSACX_EINVAL;
     if (primary) *primary = ~0ull;
-    PSACX_TRY(repeats_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (n == 0) return PSACX_OK;
     if (!text || !SA || !bwt || (offsets && (m == 0 || m > n))) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
@@ -144,13 +126,7 @@ int bwt_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* offs
     uint8_t* d_text = (uint8_t*)s.upload(text, n);
     T* d_SA = (T*)s.upload(SA, n * sizeof(T));
     uint8_t* d_bwt = (uint8_t*)s.alloc(n);
-    uint32_t* d_ends = nullptr;
-    if (offsets) {
-        uint64_t* d_off = (uint64_t*)s.upload(offsets, (m + 1) * sizeof(uint64_t));
-        d_ends = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
-        uint64_t words = 0;
-        if (s.rc == PSACX_OK) s.rc = psacx_string_ends_dev(c, d_off, m, n, d_ends, &words);
-    }
+    const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
     if (s.rc == PSACX_OK) s.rc = bwt_dev<T>(c, d_text, n, d_ends, d_SA, d_bwt, (uint32_t*)nullptr, primary);
     s.download(bwt, d_bwt, n);
     s.step(hipStreamSynchronize(c->stream));
@@ -163,7 +139,7 @@ int repeats_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* 
                  uint64_t min_len, uint64_t min_occ, uint64_t max_occ, T* lb, T* ub, T* len, uint64_t cap, uint64_t* z) {
     if (!c || !z) return PSACX_EINVAL;
     *z = 0;
-    PSACX_TRY(repeats_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (kind > (uint32_t)REPEATS_SUPERMAXIMAL) return PSACX_EINVAL;
     if ((lb == nullptr) != (ub == nullptr) || (!lb && len)) return PSACX_EINVAL;
     if (n <= 1) return PSACX_OK;
@@ -178,19 +154,13 @@ int repeats_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* 
     T* d_index = (T*)s.alloc(Y.entries * sizeof(T));
     uint8_t* d_bwt = nullptr;
     uint32_t* d_first = nullptr;
-    if (s.rc == PSACX_OK) s.rc = rmq_index(c, d_LCP, n, d_index, &entries);
+    if (s.rc == PSACX_OK) s.rc = rmq_index_dev<T>(c, d_LCP, n, d_index, &entries);
     if (left) {
         uint8_t* d_text = (uint8_t*)s.upload(text, n);
         T* d_SA = (T*)s.upload(SA, n * sizeof(T));
         d_bwt = (uint8_t*)s.alloc(n);
         d_first = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
-        uint32_t* d_ends = nullptr;
-        if (offsets) {
-            uint64_t* d_off = (uint64_t*)s.upload(offsets, (m + 1) * sizeof(uint64_t));
-            d_ends = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
-            uint64_t words = 0;
-            if (s.rc == PSACX_OK) s.rc = psacx_string_ends_dev(c, d_off, m, n, d_ends, &words);
-        }
+        const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
         if (s.rc == PSACX_OK) s.rc = bwt_dev<T>(c, d_text, n, d_ends, d_SA, d_bwt, d_first, (uint64_t*)nullptr);
     }
     if (s.rc == PSACX_OK)

@@ -21,15 +21,15 @@
 // bytes against it, and the sixteen sets are merged by xor-shuffles, where two sets that share a bit are a collision.  Lane 0 stores
 // one select byte per rank and the interval of a selected head at slot j.
 //
-// Compaction.  select_count_kernel counts the select bytes per tile of REP_TILE ranks, the scan of scan.hpp turns the counts into
-// list positions (the last entry is z), and repeats_emit_kernel writes lb, ub and L[j] in the order of j.
+// Compaction.  The select bytes go through select.hpp in tiles of REP_TILE ranks: counts per tile, their scan (the last entry is z),
+// and the functor RepeatsEmit writes lb, ub and L[j] in the order of j.
 #pragma once
 #include "rmq.hpp"
+#include "select.hpp"
 
 namespace psacx {
 
-constexpr int REP_TILE = 1024;                         // ranks of a tile of the compaction (4 per thread)
-constexpr int REP_PER = 4;                             // select bytes a thread of the compaction owns: one 32-bit word
+constexpr int REP_TILE = 1024;                         // ranks of a tile of the compaction (select.hpp: 4 per thread)
 constexpr unsigned REP_MAX_DISTINCT = 256;             // byte values: an interval with more ranks that do not start a string repeats one
 
 enum { REPEATS_RIGHT = 0, REPEATS_MAXIMAL = 1, REPEATS_SUPERMAXIMAL = 2 };
@@ -231,40 +231,23 @@ __global__ __launch_bounds__(256) void repeats_kernel(uint64_t n, const T* __res
     }
 }
 
-// counts[t] = the select bytes set in tile t; sel holds whole tiles (the call has cleared what lies behind n)
-__global__ __launch_bounds__(256) void select_count_kernel(const unsigned char* __restrict__ sel, uint64_t ntiles, uint64_t* __restrict__ counts) {
-    __shared__ uint32_t sh[256 / WAVE];
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint32_t word = *reinterpret_cast<const uint32_t*>(sel + t * REP_TILE + threadIdx.x * REP_PER);
-        const uint32_t total = block_reduce<256, uint32_t>((uint32_t)__popc(word & 0x01010101u), OpSum(), sh);
-        if (threadIdx.x == 0) counts[t] = total;
-    }
-}
-
-// counts: the exclusive sums of the tile counts, ntiles + 1 entries.  The k-th selected head j gives lb[k], ub[k], len[k] = L[j].
+// The functor of select_emit_kernel: the k-th selected head j gives lb[k], ub[k] and, where asked for, len[k] = L[j]
+// (j < n: nothing behind n is selected).
 template <typename T>
-__global__ __launch_bounds__(256) void repeats_emit_kernel(const T* __restrict__ LCP, uint64_t n, uint64_t ntiles,
-                                                           const unsigned char* __restrict__ sel, const uint64_t* __restrict__ counts,
-                                                           const T* __restrict__ cand_lb, const T* __restrict__ cand_ub, T* __restrict__ lb,
-                                                           T* __restrict__ ub, T* __restrict__ len) {
-    __shared__ uint32_t sh[256 / WAVE + 1];
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t base = counts[t];
-        if (counts[t + 1] == base) continue;
-        const uint64_t j0 = t * REP_TILE + threadIdx.x * REP_PER;
-        const uint32_t word = *reinterpret_cast<const uint32_t*>(sel + j0) & 0x01010101u;
-        uint32_t total;
-        uint64_t at = base + block_scan_exclusive<256, uint32_t>((uint32_t)__popc(word), OpSum(), 0u, sh, &total);
-#pragma unroll
-        for (int d = 0; d < REP_PER; ++d) {
-            if (!((word >> (8 * d)) & 1u)) continue;
-            const uint64_t j = j0 + d;                  // < n: nothing behind n is selected
-            lb[at] = cand_lb[j];
-            ub[at] = cand_ub[j];
-            if (len) len[at] = LCP[j];
-            ++at;
-        }
+struct RepeatsEmit {
+    const T* __restrict__ LCP;
+    const T* __restrict__ cand_lb;
+    const T* __restrict__ cand_ub;
+    T* __restrict__ lb;
+    T* __restrict__ ub;
+    T* __restrict__ len;
+    __device__ __forceinline__ void operator()(uint64_t at, uint64_t j) const {
+        const T l = cand_lb[j], u = cand_ub[j];         // both loads in flight before the first store (restrict does not reach a member)
+        lb[at] = l;
+        ub[at] = u;
+        if (len) len[at] = LCP[j];
     }
-}
+    __device__ __forceinline__ void finish(uint64_t) const {}
+};
 
 } // namespace psacx

@@ -12,20 +12,6 @@
 
 namespace psacx {
 
-// check.hip: the offsets of a string set start at 0, end at n and ascend strictly (PSACX_EINVAL otherwise; waits); and the bitmap of
-// the string ends of valid offsets, queued on the ctx stream
-int string_offsets_valid_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n);
-int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint64_t n, uint32_t* bits);
-
-static const uint64_t RMQ_MAX_N = 1ull << 48;          // 64^PYR_MAX: the top level is one group
-
-template <typename T>
-static int rmq_check_n(uint64_t n) {
-    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
-    if (n > RMQ_MAX_N) return PSACX_ERANGE;
-    return PSACX_OK;
-}
-
 // the levels >= 1 and their running minima, queued on the ctx stream (profile: an event pair around the kernel of level 1, the
 // one pass over the values themselves)
 template <typename T>
@@ -49,7 +35,7 @@ static int rmq_index_fill(psacx_ctx* c, const T* d_values, uint64_t n, T* d_inde
 template <typename T>
 int rmq_index_dev(psacx_ctx* c, const T* d_values, uint64_t n, T* d_index, uint64_t* entries) {
     if (!c || !entries) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     RmqLayout Y;
     rmq_layout(n, Y);
     *entries = Y.entries;
@@ -67,11 +53,13 @@ int rmq_index_dev(psacx_ctx* c, const T* d_values, uint64_t n, T* d_index, uint6
     c->profile = false; c->ev_used = 0;
     return rc;
 }
+template int rmq_index_dev<uint32_t>(psacx_ctx*, const uint32_t*, uint64_t, uint32_t*, uint64_t*);
+template int rmq_index_dev<uint64_t>(psacx_ctx*, const uint64_t*, uint64_t, uint64_t*, uint64_t*);
 
 template <typename T>
 int rmq_dev(psacx_ctx* c, const T* d_values, uint64_t n, const T* d_index, const T* d_lo, const T* d_hi, uint64_t q, T* d_min, T* d_arg) {
     if (!c || (!d_min && !d_arg)) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (q == 0) return PSACX_OK;
     if (!d_lo || !d_hi || (n && (!d_values || !d_index))) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
@@ -86,7 +74,7 @@ template <typename T>
 int lce_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, const T* d_ISA, const T* d_LCP, const T* d_index, const T* d_a,
             const T* d_b, uint64_t q, uint64_t e, T* d_len) {
     if (!c) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (d_off && (m == 0 || m > n)) return PSACX_EINVAL;
     if (q == 0) return PSACX_OK;
     if (!d_a || !d_b || !d_len || (n && (!d_ISA || !d_LCP || !d_index))) return PSACX_EINVAL;
@@ -105,7 +93,7 @@ int lce_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, const T
 template <typename T>
 int rmq_host(psacx_ctx* c, const T* values, uint64_t n, const T* lo, const T* hi, uint64_t q, T* mn, T* arg) {
     if (!c || (!mn && !arg)) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (q == 0) return PSACX_OK;
     if (!lo || !hi || (n && !values)) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
@@ -130,7 +118,7 @@ template <typename T>
 int lce_host(psacx_ctx* c, uint64_t n, const uint64_t* offsets, uint64_t m, const T* ISA, const T* LCP, const T* a, const T* b, uint64_t q,
              uint64_t e, T* len) {
     if (!c) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (offsets && (m == 0 || m > n)) return PSACX_EINVAL;
     if (q == 0) return PSACX_OK;
     if (!a || !b || !len || (n && (!ISA || !LCP))) return PSACX_EINVAL;
@@ -158,7 +146,7 @@ template <typename T>
 int overlaps_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, const uint32_t* d_ends, const T* d_SA, const T* d_ISA, const T* d_LCP,
                  const T* d_index, uint64_t min_len, uint32_t flags, T* d_lb, T* d_ub) {
     if (!c || min_len == 0 || (flags & ~(uint32_t)PSACX_OVERLAP_WHOLE)) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (m == 0 || n == 0) return PSACX_OK;
     if (m > n || !d_off || !d_ends || !d_SA || !d_ISA || !d_LCP || !d_index || !d_lb || !d_ub) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
@@ -176,7 +164,7 @@ template <typename T>
 int overlaps_host(psacx_ctx* c, uint64_t n, const uint64_t* offsets, uint64_t m, const T* SA, const T* ISA, const T* LCP, uint64_t min_len,
                   uint32_t flags, T* lb, T* ub) {
     if (!c || min_len == 0 || (flags & ~(uint32_t)PSACX_OVERLAP_WHOLE)) return PSACX_EINVAL;
-    PSACX_TRY(rmq_check_n<T>(n));
+    PSACX_TRY(index_check_n<T>(n));
     if (m == 0 || n == 0) return PSACX_OK;
     if (m > n || !offsets || !SA || !ISA || !LCP || !lb || !ub) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
@@ -186,13 +174,11 @@ int overlaps_host(psacx_ctx* c, uint64_t n, const uint64_t* offsets, uint64_t m,
     T* d_SA = (T*)s.upload(SA, n * sizeof(T));
     T* d_ISA = (T*)s.upload(ISA, n * sizeof(T));
     T* d_LCP = (T*)s.upload(LCP, n * sizeof(T));
-    uint64_t* d_off = (uint64_t*)s.upload(offsets, (m + 1) * sizeof(uint64_t));
-    uint32_t* d_ends = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
     T* d_index = (T*)s.alloc(Y.entries * sizeof(T));
     T* d_lb = (T*)s.alloc(n * sizeof(T));
     T* d_ub = (T*)s.alloc(n * sizeof(T));
-    if (s.rc == PSACX_OK) s.rc = string_offsets_valid_dev(c, d_off, m, n);
-    if (s.rc == PSACX_OK) s.rc = string_ends_bitmap_dev(c, d_off, m, n, d_ends);
+    const uint64_t* d_off = nullptr;
+    const uint32_t* d_ends = s.string_ends(offsets, m, n, &d_off);
     if (s.rc == PSACX_OK) s.rc = rmq_index_fill<T>(c, d_LCP, n, d_index);
     if (s.rc == PSACX_OK) s.rc = overlaps_dev<T>(c, n, d_off, m, d_ends, d_SA, d_ISA, d_LCP, d_index, min_len, flags, d_lb, d_ub);
     s.download(lb, d_lb, n * sizeof(T));

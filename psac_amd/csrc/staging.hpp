@@ -1,8 +1,9 @@
-// staging.hpp -- device memory of a host-pointer call (psacx_locate_*, psacx_match_*, psacx_rmq_*, psacx_lce_*): the arrays are
-// staged in memory of their own for the time of the call (the slab belongs to the device forms), and everything allocated is freed
-// on every path.  rc is sticky: after the first failure every later step does nothing.
+// staging.hpp -- device memory of a host-pointer call (psacx_locate_*, psacx_match_*, psacx_rmq_*, psacx_lce_*, psacx_overlaps_*,
+// psacx_lpf_*, psacx_lz77_*, psacx_bwt_*, psacx_repeats_*) and of the device forms that need arrays of n entries for the time of a
+// call (psacx_lpf_dev_*, psacx_repeats_dev_*): the arrays are staged in memory of their own (the slab belongs to the device forms),
+// and everything allocated is freed on every path.  rc is sticky: after the first failure every later step does nothing.
 #pragma once
-#include "engine.hpp"
+#include "query_calls.hpp"
 
 namespace psacx {
 
@@ -25,6 +26,16 @@ struct Staging {
         return p;
     }
     void download(void* dst, const void* src, size_t bytes) { if (rc == PSACX_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); }
+    // The string set of a call: its m + 1 offsets go up (*d_off: where they are), are checked on the device (PSACX_EINVAL; waits), and
+    // give the bitmap of the string ends, (n >> 5) + 1 words, queued on the ctx stream.  1 <= m <= n is the caller's test.
+    const uint32_t* string_ends(const uint64_t* offsets, uint64_t m, uint64_t n, const uint64_t** d_off = nullptr) {
+        const uint64_t* d = (const uint64_t*)upload(offsets, (m + 1) * sizeof(uint64_t));
+        uint32_t* bits = (uint32_t*)alloc(((n >> 5) + 1) * sizeof(uint32_t));
+        if (rc == PSACX_OK) rc = string_offsets_valid_dev(c, d, m, n);
+        if (rc == PSACX_OK) rc = string_ends_bitmap_dev(c, d, m, n, bits);
+        if (d_off) *d_off = d;
+        return bits;
+    }
 };
 
 } // namespace psacx

@@ -11,6 +11,8 @@ to the model):
     strings x w for every byte x plus w itself (w is supermaximal with 257 occurrences) and its twin with one x doubled (it is not);
   - every filter alone and combined; the count query; PSACX_ERANGE at cap = z - 1 with z right and the lists untouched; the NULL
     rules and an unknown kind; d_len NULL;
+  - a^2049 with min_len 1023, 1024, 1025 and 2048: the first selected rank on the last slot of a tile of the compaction, on the first
+    two slots of the next and alone in the third, with nothing selected in front of it;
   - z of the right-maximal kind == edges - n of psacx_suffix_tree_dev_* on the same arrays;
   - d_lb / d_ub of a maximal-repeat call handed to psacx_occurrences_dev_* give the model's occurrence positions;
   - totality: LCP[0] overwritten (the result does not change), LCP entries of all ones, an index of noise, bwt / first of noise --
@@ -144,6 +146,28 @@ def test_filters_count_query_and_erange(ctx, bits):
                 agree((lb[:z].astype(np.int64), ub[:z].astype(np.int64)), full, (kind, "no len"))
                 assert np.all(lb[z:] == SENTINEL) and np.all(ub[z:] == SENTINEL)
             assert d.unchanged()
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("bits", [32, 64])
+@pytest.mark.parametrize("min_len", [1023, 1024, 1025, 2048])
+def test_first_selected_rank_at_a_tile_edge(ctx, min_len, bits):
+    # a^2049: rank j is a head with L[j] = j, so min_len puts the first selected rank on the last slot of the first tile of 1024 ranks
+    # of the compaction, on the first and second slot of the second tile, and on the one rank of the third, with nothing selected
+    # in front of it
+    n = 2049
+    dev = Dev(ctx, bits)
+    try:
+        case = text_case("a", n)
+        d = RepIndex(dev, case)
+        d.run_bwt()
+        for kind in (M.RIGHT, M.MAXIMAL):
+            want = M.select(case.results(kind), min_len=min_len)
+            assert d.count(kind, min_len=min_len) == len(want) == n - min_len
+            agree(d.run(kind, min_len=min_len), want, (kind, min_len))          # (run: the count query, then the lists)
+        assert M.select(case.results(M.MAXIMAL), min_len=min_len) == [(j, j - 1, n, j) for j in range(min_len, n)]
+        assert d.unchanged()
     finally:
         dev.close()
 
