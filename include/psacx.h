@@ -97,6 +97,9 @@ typedef struct psacx_stats {
     uint64_t group_sort;           /* the one-word prefix sort of the last construction: 0 = LSD passes on every digit inside the 256 buckets, 1 = upper digits most
                                       significant first and the groups of the last 16 prefix bits sorted on chip, 2 = that form entered, a group longer
                                       than its cap found, the remaining digits sorted LSD inside the partition reached */
+    uint64_t grid_cuts;            /* launches of grid-stride kernels since the context was created whose grid came out smaller than the workgroups their items
+                                      asked for, by the default bound of a few workgroups per CU or by PSACX_OPT_GRID_CAP: some workgroup of such a launch takes a
+                                      second trip through its loop.  Never cleared; filled by psacx_get_stats. */
 } psacx_stats;
 
 /* life cycle ------------------------------------------------------------- */
@@ -149,13 +152,17 @@ int psacx_trim(psacx_ctx* ctx);
  *   FIRST_LEAD        test option: leading bits the two-stage first round sorts on; honoured when a multiple of 8, at least bits(n - 1) + 3, at most 40
  *                     and at most the bits of the first key word, ignored otherwise (40 reaches the sub-bucket passes on small texts)
  *   LZ_SMALL_TILES    test option: psacx_lz77_dev_* parses on tiles of 64 positions in groups of 4 tiles, not 1024 in groups of 128, so that every
- *                     level of the parse, the walk over the groups included, is taken at a few hundred positions; the parse is the same     */
+ *                     level of the parse, the walk over the groups included, is taken at a few hundred positions; the parse is the same
+ *   GRID_CAP          test option: 1..65535 = every grid-stride kernel is launched on at most this many workgroups, not on the default bound of a few
+ *                     workgroups per CU, so that the second and later trips of its loop are taken at a few thousand items (psacx_stats.grid_cuts counts
+ *                     the launches that were cut); 0 = the default bound; larger values are refused; no result changes     */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
     PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD, PSACX_OPT_LZ_SMALL_TILES,
+    PSACX_OPT_GRID_CAP,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);

@@ -23,7 +23,8 @@ PSACX_REPEATS_RIGHT, PSACX_REPEATS_MAXIMAL, PSACX_REPEATS_SUPERMAXIMAL = 0, 1, 2
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
            "widen_last": 8, "no_digit_bytes": 9, "no_bucket_sort": 10, "isa_update": 11, "gather": 12, "no_heavy": 13, "no_whole": 14, "no_lazy_ranks": 15, "no_early_out": 16,
            "no_spread_cursors": 17, "locate_shape": 18, "locate_count": 19, "generic_rebucket": 20,
-           "plain_side_kernels": 21, "lsd_bucket_passes": 22, "first_lead": 23, "lz_small_tiles": 24}
+           "plain_side_kernels": 21, "lsd_bucket_passes": 22, "first_lead": 23, "lz_small_tiles": 24,
+           "grid_cap": 25}
 MULTI_OPTIONS = {"layout": 1, "slab": 2, "output_slack": 3, "trace": 4, "wire_piece": 5, "pieces": 6, "check_chunks": 7, "global_refine_sort": 8,
                  "one_stage": 9, "two_word": 10, "one_word": 11, "no_slices": 12, "slice_wide": 13, "slice_shape": 14}
 MULTI_FORCE_WIRE, MULTI_NO_RCCL, MULTI_SHM = 1, 2, 4
@@ -86,7 +87,7 @@ class Stats(C.Structure):
                 ("scatter_bytes", C.c_uint64 * 3), ("hist_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64), ("onew_passes", C.c_uint64),
                 ("heavy_rounds", C.c_uint64), ("heavy_records", C.c_uint64), ("light_records", C.c_uint64), ("level_gathers", C.c_uint64),
                 ("ms_host", C.c_double * 9), ("locate_fetches", C.c_uint64 * 2), ("rebucket_1w", C.c_uint64),
-                ("group_sort", C.c_uint64)]
+                ("group_sort", C.c_uint64), ("grid_cuts", C.c_uint64)]
 
 
 class PsacxError(RuntimeError):

@@ -73,6 +73,8 @@ struct Knobs {
     bool lz_small_tiles = false;  // PSACX_OPT_LZ_SMALL_TILES: the LZ77 parse works on tiles of 64 positions in groups of 4 (tests: every level of lz.hpp at a few hundred positions)
     int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (search.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
+    unsigned grid_cap = 0;        // PSACX_OPT_GRID_CAP: grid_for cuts every grid to at most this many workgroups, not n_cu * per_cu (tests: the second and
+                                  // later trips of the grid-stride loops at a few thousand items; 0 = the default bound)
 };
 
 } // namespace psacx
@@ -126,6 +128,7 @@ struct psacx_ctx {
     size_t ev_used = 0;
     int n_cu = 256;
     psacx::Knobs knobs;              // psacx_configure
+    mutable uint64_t grid_cuts = 0;  // grid_for calls since the ctx was made whose grid came out smaller than the workgroups asked for (psacx_stats.grid_cuts)
     uint64_t slab_gen = 0;           // bumped whenever an operation claims the slab as its scratch (ensure_slab)
     struct { const void* s1 = nullptr; uint64_t cnt = 0; unsigned lo1 = 0; uint64_t gen = 0; } tie_stamp;      // dist_ops.hpp: op_compact_ties(counted)
 };
@@ -563,8 +566,9 @@ inline void pool_free(psacx_ctx* c, void* p, size_t cap) {
 inline int grid_for(const psacx_ctx* c, uint64_t work_items, int block, int per_cu = 8);
 inline int grid_for(const psacx_ctx* c, uint64_t work_items, int block, int per_cu) {
     uint64_t want = (work_items + block - 1) / block;
-    uint64_t cap = (uint64_t)c->n_cu * per_cu;
+    const uint64_t cap = c->knobs.grid_cap ? (uint64_t)c->knobs.grid_cap : (uint64_t)c->n_cu * per_cu;
     if (want < 1) want = 1;
+    if (want > cap) ++c->grid_cuts;
     return (int)std::min<uint64_t>(want, cap);
 }
 

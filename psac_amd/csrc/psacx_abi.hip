@@ -133,6 +133,7 @@ int psacx_configure(psacx_ctx* c, int option, uint64_t value) {
     case PSACX_OPT_PLAIN_SIDE_KERNELS: k.plain_side_kernels = value != 0; return PSACX_OK;
     case PSACX_OPT_LSD_BUCKET_PASSES: k.lsd_bucket_passes = value != 0; return PSACX_OK;
     case PSACX_OPT_LZ_SMALL_TILES: k.lz_small_tiles = value != 0; return PSACX_OK;
+    case PSACX_OPT_GRID_CAP: if (value > 65535) return PSACX_EINVAL; k.grid_cap = (unsigned)value; return PSACX_OK;
     case PSACX_OPT_FIRST_LEAD: if (value > 64) return PSACX_EINVAL; k.first_lead = (unsigned)value; return PSACX_OK;
     default: return PSACX_EINVAL;
     }
@@ -155,6 +156,7 @@ int psacx_configure_from_env(psacx_ctx* c) {
     for (const auto& f : flags) if (psacx_debug_env(f.name)) (void)psacx_configure(c, f.option, 1);
     if (const char* e = psacx_debug_env("PSACX_DIET_CAP")) (void)psacx_configure(c, PSACX_OPT_DIET_CAP, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_FIRST_LEAD")) (void)psacx_configure(c, PSACX_OPT_FIRST_LEAD, strtoull(e, nullptr, 10));
+    if (const char* e = psacx_debug_env("PSACX_GRID_CAP")) (void)psacx_configure(c, PSACX_OPT_GRID_CAP, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_ONE_WORD_MIN")) (void)psacx_configure(c, PSACX_OPT_ONE_WORD_MIN, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_ISA_UPDATE")) (void)psacx_configure(c, PSACX_OPT_ISA_UPDATE, e[0] == 's' ? 1 : 2);
     if (const char* e = psacx_debug_env("PSACX_LOCATE_SHAPE")) (void)psacx_configure(c, PSACX_OPT_LOCATE_SHAPE, e[0] == 'g' ? 2 : 1);
@@ -230,6 +232,7 @@ int psacx_profile(psacx_ctx* c, int on) {
 int psacx_get_stats(const psacx_ctx* c, psacx_stats* out) {
     if (!c || !out) return PSACX_EINVAL;
     *out = c->stats;
+    out->grid_cuts = c->grid_cuts;          // (kept beside the stats: a construction clears those)
     return PSACX_OK;
 }
 

@@ -186,6 +186,13 @@ def strings_of(name):
     return _sets[name]
 
 
+def add_set(name, strings):
+    """A further named set, for a test that needs a size of its own; the catalogue lists (GST, ALL, GPU) do not change."""
+    if name not in _sets:
+        _sets[name] = list(strings)
+    return name
+
+
 def arrays(name):
     """(text, off, SA) of a named set: the oracle's generalized suffix array (64-bit), equal suffixes in text order."""
     if name not in _arrays:

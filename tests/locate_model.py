@@ -134,6 +134,13 @@ def text_of(name):
     return _texts[name]
 
 
+def add_text(name, text):
+    """A further named text, for a test that needs a size of its own; the catalogue lists (SMALL, ALL) do not change."""
+    if name not in _texts:
+        _texts[name] = np.ascontiguousarray(text, dtype=np.uint8)
+    return name
+
+
 def sa_of(name):
     """The oracle's suffix array of a named text (64-bit entries)."""
     if name not in _sa:

@@ -100,30 +100,40 @@ def test_lists_of_the_catalogue_equal_the_model(ctx, name, bits):
         o.close()
 
 
+HAND_N = 4097                                                                            # unary: SA = n - 1 .. 0; four tiles and one slot
+HAND_OFF = np.array([0, 1, 31, 32, 33, 64, 1000, 1001, 4096, HAND_N], np.uint64)
+
+
+def hand_made_batches():
+    """(lb, ub, limit, the total stated by hand or None) of the hand-made batches over HAND_N ranks, in a fixed order"""
+    n = HAND_N
+    empties = [9] * 1000
+    out = [([], [], 0, 0),
+           ([5] * 300, [5] * 300, 0, 0),                                                 # all empty
+           ([0], [n], 0, n),                                                             # one interval over every tile
+           ([0, 7], [n, n], 0, 2 * n - 7),
+           ([3] + empties + [100], [10] + empties + [2500], 0, 7 + 2400),                # 1 000 empty intervals between two others
+           ([9, 3, 100, 9], [9, 10, 2500, 9], 0, 7 + 2400),                              # an empty interval first and last
+           ([7, 0, 5, n - 3, n], [6, n + 1, 9, n, n], 0, 4 + 3)]                         # lb > ub and ub > n count 0
+    rng = np.random.RandomState(2)
+    for q in (1, 63, 64, 65, 5000):
+        lb = rng.randint(0, n, q)
+        ub = np.minimum(n, lb + rng.choice([0, 0, 1, 2, 70, 1500], q, p=[.3, .3, .2, .1, .09, .01]))
+        out += [(lb, ub, 0, None), (lb, ub, 3, None)]
+    # many short intervals per tile, and more patterns than a workgroup holds at a time between two outputs
+    out.append((np.arange(n - 1), np.arange(n - 1) + 1, 0, None))
+    out.append(([1] + [2] * 3000 + [4], [2] + [2] * 3000 + [5], 0, None))
+    return out
+
+
 @pytest.mark.parametrize("bits", [32, 64])
 def test_hand_made_batches(ctx, bits):
-    n = 4097                                                                             # unary: SA = n - 1 .. 0; four tiles and one slot
-    SA = np.arange(n, dtype=np.uint64)[::-1].copy()
-    off = np.array([0, 1, 31, 32, 33, 64, 1000, 1001, 4096, n], np.uint64)
-    o = Occ(ctx, SA, n, off, bits)
+    SA = np.arange(HAND_N, dtype=np.uint64)[::-1].copy()
+    o = Occ(ctx, SA, HAND_N, HAND_OFF, bits)
     try:
-        assert o.check([], []) == 0
-        assert o.check([5] * 300, [5] * 300) == 0                                        # all empty
-        assert o.check([0], [n]) == n                                                    # one interval over every tile
-        assert o.check([0, 7], [n, n]) == 2 * n - 7
-        empties = [9] * 1000
-        assert o.check([3] + empties + [100], [10] + empties + [2500]) == 7 + 2400       # 1 000 empty intervals between two others
-        assert o.check([9, 3, 100, 9], [9, 10, 2500, 9]) == 7 + 2400                     # an empty interval first and last
-        assert o.check([7, 0, 5, n - 3, n], [6, n + 1, 9, n, n]) == 4 + 3                # lb > ub and ub > n count 0
-        rng = np.random.RandomState(2)
-        for q in (1, 63, 64, 65, 5000):
-            lb = rng.randint(0, n, q)
-            ub = np.minimum(n, lb + rng.choice([0, 0, 1, 2, 70, 1500], q, p=[.3, .3, .2, .1, .09, .01]))
-            o.check(lb, ub)
-            o.check(lb, ub, 3)
-        # many short intervals per tile, and more patterns than a workgroup holds at a time between two outputs
-        o.check(np.arange(n - 1), np.arange(n - 1) + 1)
-        o.check([1] + [2] * 3000 + [4], [2] + [2] * 3000 + [5])
+        for lb, ub, limit, by_hand in hand_made_batches():
+            total = o.check(lb, ub, limit)
+            assert by_hand is None or total == by_hand
     finally:
         o.close()
 

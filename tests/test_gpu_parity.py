@@ -860,6 +860,41 @@ def test_options_through_the_abi(ctx, monkeypatch):
         d = run(ctx, text, bits=64)
         assert in_lds(d) and d.rounds == a.rounds
         assert ctx._lib.psacx_configure(ctx.handle, 999, 1) == -1 and ctx._lib.psacx_configure(ctx.handle, psac_amd._lib.OPTIONS["gather"], 7) == -1
+        # PSACX_OPT_GRID_CAP: 1 .. 65535 are taken, anything above is refused and leaves the option as it was, 0 and RESET give the
+        # default bound back.  A size query of psacx_occurrences_dev_* over 1024 intervals asks for 5 workgroups (occ_counts_kernel: a
+        # thread per entry of start[]), which only a cap cuts: psacx_stats.grid_cuts says whether it was.  (No construction runs under
+        # the cap here: tests/test_gpu_grid_trips.py says what does.)
+        cap_opt = psac_amd._lib.OPTIONS["grid_cap"]
+        zeros = np.zeros(1024, np.uint64)
+        d_sa, d_lb, d_ub, d_start = [ctx.alloc(1025 * 8) for _ in range(4)]
+        for p in (d_sa, d_lb, d_ub):
+            ctx.h2d(p, zeros)
+
+        def cut_by_a_size_query():
+            before = ctx.stats().grid_cuts
+            assert psac_amd.occurrences_device(ctx, d_sa, 1024, None, 0, d_lb, d_ub, 1024, 0, d_start, None, None, 0, 64) == 0
+            return ctx.stats().grid_cuts - before
+        assert cut_by_a_size_query() == 0
+        for v in (1, 3, 65535):
+            assert ctx._lib.psacx_configure(ctx.handle, cap_opt, v) == 0
+            assert cut_by_a_size_query() == (1 if v < 5 else 0), v
+        ctx.configure(grid_cap=2)
+        for v in (65536, 1 << 32, (1 << 64) - 1):
+            assert ctx._lib.psacx_configure(ctx.handle, cap_opt, v) == -1
+        assert cut_by_a_size_query() == 1                           # a refused value changes nothing: the cap is still 2
+        ctx.configure(grid_cap=0)
+        assert cut_by_a_size_query() == 0
+        ctx.configure(grid_cap=1)
+        ctx.configure(reset=0)
+        assert cut_by_a_size_query() == 0
+        monkeypatch.setenv("PSACX_GRID_CAP", "3")                   # the shim takes the variable; the library on its own does not
+        assert cut_by_a_size_query() == 0
+        ctx.check(ctx._lib.psacx_configure_from_env(ctx.handle))
+        assert cut_by_a_size_query() == 1
+        monkeypatch.delenv("PSACX_GRID_CAP")
+        ctx.configure(reset=0)
+        for p in (d_sa, d_lb, d_ub, d_start):
+            ctx.free(p)
         # ... and the shim: the same variable, asked for explicitly
         ctx.check(ctx._lib.psacx_configure_from_env(ctx.handle))
         e = run(ctx, text, bits=64)

@@ -36,6 +36,16 @@ def test_the_option_and_the_wrappers_are_there():
     import psac_amd
     from psac_amd import _lib
     assert _lib.OPTIONS["lz_small_tiles"] == 24
+    # the option that cuts the grids of the stride loops, the next number, and the counter of the cut launches: the last field of the
+    # statistics, as in include/psacx.h
+    assert _lib.OPTIONS["grid_cap"] == 25 == max(_lib.OPTIONS.values()) and len(set(_lib.OPTIONS.values())) == len(_lib.OPTIONS)
+    assert _lib.Stats._fields_[-1][0] == "grid_cuts" and _lib.Stats.grid_cuts.size == 8
+    with open(os.path.join(ROOT, "include", "psacx.h")) as f:
+        header = f.read()
+    enum = header[header.index("PSACX_OPT_RESET = 0"):header.index("PSACX_OPT_COUNT")].replace("= 0", "").replace("\n", " ")
+    names = [x.strip() for x in enum.split(",") if x.strip()]
+    assert names.index("PSACX_OPT_GRID_CAP") == 25 and names.index("PSACX_OPT_LZ_SMALL_TILES") == 24
+    assert header.index("uint64_t grid_cuts;") > header.index("uint64_t group_sort;") and header.index("} psacx_stats;") > header.index("uint64_t grid_cuts;")
     for name in ("lpf_device", "lz77_device", "check_lz77_device", "lpf", "lz77", "lz77_decode"):
         assert callable(getattr(psac_amd, name)), name
     start, src = M.parse_of("mississippi")
