@@ -149,6 +149,8 @@ int psacx_trim(psacx_ctx* ctx);
  *                     kernels (top_digit_hist_kernel, tie_resolve_1w_kernel), not the persistent ones (parity tests, A/B runs)
  *   LSD_BUCKET_PASSES the one-word prefix sort of the first round sorts every digit below the top one by LSD passes inside the 256 buckets, not the
  *                     upper digits most significant first and the last 16 bits on chip (psacx_stats.group_sort; parity tests, A/B runs)
+ *   GROUP_COUNTING_ROUNDS the group form orders the last 16 prefix bits of every batch by two or three stable counting rounds, not by one round and the
+ *                     ranks inside its buckets (radix.hpp: group_sort16_kernel; the records it leaves are the same; parity tests, A/B runs)
  *   FIRST_LEAD        test option: leading bits the two-stage first round sorts on; honoured when a multiple of 8, at least bits(n - 1) + 3, at most 40
  *                     and at most the bits of the first key word, ignored otherwise (40 reaches the sub-bucket passes on small texts)
  *   LZ_SMALL_TILES    test option: psacx_lz77_dev_* parses on tiles of 64 positions in groups of 4 tiles, not 1024 in groups of 128, so that every
@@ -162,7 +164,7 @@ enum {
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
     PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD, PSACX_OPT_LZ_SMALL_TILES,
-    PSACX_OPT_GRID_CAP,
+    PSACX_OPT_GRID_CAP, PSACX_OPT_GROUP_COUNTING_ROUNDS,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);

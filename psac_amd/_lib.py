@@ -25,6 +25,9 @@ OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_rad
            "no_spread_cursors": 17, "locate_shape": 18, "locate_count": 19, "generic_rebucket": 20,
            "plain_side_kernels": 21, "lsd_bucket_passes": 22, "first_lead": 23, "lz_small_tiles": 24,
            "grid_cap": 25}
+# options that pin the form of one kernel for A/B runs and parity tests (the enum of include/psacx.h goes on behind GRID_CAP);
+# Context.configure takes them by name like the ones above
+KERNEL_OPTIONS = {"group_counting_rounds": 26}
 MULTI_OPTIONS = {"layout": 1, "slab": 2, "output_slack": 3, "trace": 4, "wire_piece": 5, "pieces": 6, "check_chunks": 7, "global_refine_sort": 8,
                  "one_stage": 9, "two_word": 10, "one_word": 11, "no_slices": 12, "slice_wide": 13, "slice_shape": 14}
 MULTI_FORCE_WIRE, MULTI_NO_RCCL, MULTI_SHM = 1, 2, 4

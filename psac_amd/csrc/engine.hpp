@@ -68,6 +68,8 @@ struct Knobs {
                                   // top_digit_hist_waves_kernel and tie_resolve_1w_waves_kernel (sa_kernels.hpp; parity tests and A/B runs)
     bool lsd_bucket_passes = false; // PSACX_OPT_LSD_BUCKET_PASSES: the one-word prefix sort runs LSD passes on all digits inside the 256 buckets, not the group form
                                   // (onew_bucket_passes: upper digits most significant first, the last 16 bits on chip; parity tests and A/B runs)
+    bool group_counting_rounds = false; // PSACX_OPT_GROUP_COUNTING_ROUNDS: group_sort16_kernel orders every batch by stable counting rounds, not by one round and the ranks
+                                  // inside its buckets (radix.hpp; parity tests and A/B runs)
     unsigned first_lead = 0;      // PSACX_OPT_FIRST_LEAD: leading bits the two-stage first round sorts on (tests: 40 reaches the sub-bucket form of the group
                                   // form at sizes a test can afford); honoured when a multiple of 8, >= bits_for(n - 1) + 3, <= 40 and <= the bits of word 1
     bool lz_small_tiles = false;  // PSACX_OPT_LZ_SMALL_TILES: the LZ77 parse works on tiles of 64 positions in groups of 4 (tests: every level of lz.hpp at a few hundred positions)
@@ -1127,8 +1129,12 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
     PSACX_TRY(scatter(tg, mid_shift, false, gbase, (uint8_t*)nullptr, 0));
     {
         ProfScope ps(c, TC_SORT_SCATTER2);
-        // (persistent waves, five workgroups of 256 per CU -- 82 VGPRs: five waves per SIMD; 20 KB of LDS each)
-        hipLaunchKernelGGL(group_sort16_kernel<256>, dim3((unsigned)grid_for(c, ngroups, 256, 5)), dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
+        // (persistent waves, five workgroups of 256 per CU -- 96 VGPRs, 82 in the form of counting rounds only: five waves per SIMD; 20 KB of LDS each)
+        const dim3 grid((unsigned)grid_for(c, ngroups, 256, 5));
+        if (c->knobs.group_counting_rounds)
+            hipLaunchKernelGGL((group_sort16_kernel<256, false>), grid, dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
+        else
+            hipLaunchKernelGGL((group_sort16_kernel<256, true>), grid, dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
         PSACX_HIP(c, hipGetLastError());
         c->stats.scatter_launches[2] += 1; c->stats.scatter_records[2] += nrec; c->stats.scatter_bytes[2] += 17ull * nrec;      // (record read and written, tie byte)
         c->stats.onew_passes += 1;

@@ -132,6 +132,7 @@ int psacx_configure(psacx_ctx* c, int option, uint64_t value) {
     case PSACX_OPT_GENERIC_REBUCKET: k.generic_rebucket = value != 0; return PSACX_OK;
     case PSACX_OPT_PLAIN_SIDE_KERNELS: k.plain_side_kernels = value != 0; return PSACX_OK;
     case PSACX_OPT_LSD_BUCKET_PASSES: k.lsd_bucket_passes = value != 0; return PSACX_OK;
+    case PSACX_OPT_GROUP_COUNTING_ROUNDS: k.group_counting_rounds = value != 0; return PSACX_OK;
     case PSACX_OPT_LZ_SMALL_TILES: k.lz_small_tiles = value != 0; return PSACX_OK;
     case PSACX_OPT_GRID_CAP: if (value > 65535) return PSACX_EINVAL; k.grid_cap = (unsigned)value; return PSACX_OK;
     case PSACX_OPT_FIRST_LEAD: if (value > 64) return PSACX_EINVAL; k.first_lead = (unsigned)value; return PSACX_OK;
@@ -151,7 +152,7 @@ int psacx_configure_from_env(psacx_ctx* c) {
         {"PSACX_NO_EARLY_OUT", PSACX_OPT_NO_EARLY_OUT}, {"PSACX_NO_SPREAD_CURSORS", PSACX_OPT_NO_SPREAD_CURSORS},
         {"PSACX_LOCATE_COUNT", PSACX_OPT_LOCATE_COUNT}, {"PSACX_GENERIC_REBUCKET", PSACX_OPT_GENERIC_REBUCKET},
         {"PSACX_PLAIN_SIDE_KERNELS", PSACX_OPT_PLAIN_SIDE_KERNELS}, {"PSACX_LSD_BUCKET_PASSES", PSACX_OPT_LSD_BUCKET_PASSES},
-        {"PSACX_LZ_SMALL_TILES", PSACX_OPT_LZ_SMALL_TILES}};
+        {"PSACX_LZ_SMALL_TILES", PSACX_OPT_LZ_SMALL_TILES}, {"PSACX_GROUP_COUNTING_ROUNDS", PSACX_OPT_GROUP_COUNTING_ROUNDS}};
     (void)psacx_configure(c, PSACX_OPT_RESET, 0);
     for (const auto& f : flags) if (psacx_debug_env(f.name)) (void)psacx_configure(c, f.option, 1);
     if (const char* e = psacx_debug_env("PSACX_DIET_CAP")) (void)psacx_configure(c, PSACX_OPT_DIET_CAP, strtoull(e, nullptr, 10));

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "dev_common.hpp"
 #include "sort_scratch.hpp"
+#include "group_rank.hpp"
 
 namespace psacx {
 
@@ -981,22 +982,104 @@ __global__ __launch_bounds__(BLOCK) void onew_max_group_kernel(const unsigned lo
     if (lane_id() == 0 && m) atomicMax(out, m);
 }
 
+// One batch of group_sort16_kernel (below) in ONE counting round (the rule and why it gives the stable order: group_rank.hpp).  r: the batch in
+// rows of 64, NR of them, all full but the last; cnt: 256 counters; stage: GROUP_CAP words, whose first half holds the 32-bit keys until the
+// records go through it.  Returns false, with r as it was, when a bucket holds more than GROUP_RANK_MAX records: the rank loop is linear in
+// the largest bucket, and the caller's counting rounds are not.  Nothing depends on the order in which the LDS serves the lanes of one returning add:
+// the value it returns only has to differ from lane to lane of a bucket.
+__device__ __forceinline__ uint64_t wave_uniform64(uint64_t v) {          // a value that is the same in every lane, in scalar registers
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)), lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    return (uint64_t)hi << 32 | lo;          // (the builtin returns an int: without the casts a low half from 2^31 on would fill the high half with ones)
+}
+template <int NR>
+__device__ __forceinline__ bool group_rank_rows(uint64_t (&r)[GROUP_CAP / WAVE], unsigned* cnt, uint64_t* stage, const unsigned count, const int sfield,
+                                                const unsigned first, const unsigned gbits, const unsigned lane) {
+    static_assert(GROUP_CAP == 1 << GROUP_RANK_PLACE_BITS && GROUP_RANK_MAX + 2 <= (unsigned)WAVE, "the keys of a batch and their filler lie in half of the stage");
+    unsigned* const keys = reinterpret_cast<unsigned*>(stage);
+    const bool last = (unsigned)((NR - 1) * WAVE) + lane < count;          // this lane holds a record in the last row
+#pragma unroll
+    for (int i = 0; i < RADIX / WAVE; ++i) cnt[i * WAVE + lane] = 0;
+    xrun_order();
+    unsigned key[NR], pos[NR], top = 0;          // pos: the slot inside the bucket, then the bucket's start; top: the largest slot this lane was given
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned ck = group_rank_ckey(r[i], sfield, first, gbits);
+        key[i] = group_rank_key(ck, (unsigned)(i * WAVE) + lane);
+        pos[i] = 0;
+        if (i + 1 < NR || last) pos[i] = __hip_atomic_fetch_add(&cnt[group_rank_bucket(ck, gbits)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+#pragma unroll
+    for (int i = 0; i < NR; ++i) top = pos[i] > top ? pos[i] : top;
+    if (__ballot(!group_rank_fits(top + 1))) return false;
+    xrun_order();
+    // exclusive scan of the 256 counters: four neighbours per lane
+    {
+        uint4 c4 = reinterpret_cast<uint4*>(cnt)[lane];
+        const unsigned sum = c4.x + c4.y + c4.z + c4.w;
+        unsigned ex = wave_scan_inclusive<unsigned>(sum, OpSum()) - sum;
+        uint4 e4;
+        e4.x = ex; ex += c4.x; e4.y = ex; ex += c4.y; e4.z = ex; ex += c4.z; e4.w = ex;
+        reinterpret_cast<uint4*>(cnt)[lane] = e4;
+    }
+    xrun_order();
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned start = cnt[key[i] >> (GROUP_RANK_PLACE_BITS + 8 + gbits)];
+        if (i + 1 < NR || last) keys[start + pos[i]] = key[i];
+        pos[i] = i + 1 < NR || last ? start : 0u;
+    }
+    if (lane < GROUP_RANK_MAX + 2) keys[count + lane] = GROUP_RANK_FILL;
+    xrun_order();
+    // smaller keys among the first `largest bucket` keys from the bucket's start on: two keys per trip (the second may lie one past that, inside the filler)
+    unsigned below[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) below[i] = 0;
+#pragma unroll
+    for (unsigned j = 0; j < GROUP_RANK_MAX; j += 2) {          // (unrolled: j is part of the instruction, not of an address computed per row)
+        if (!__ballot(j <= top)) break;
+        unsigned k0[NR], k1[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) { k0[i] = keys[pos[i] + j]; k1[i] = keys[pos[i] + j + 1]; }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            below[i] += k0[i] < key[i] ? 1u : 0u; below[i] += k1[i] < key[i] ? 1u : 0u;
+            asm("" : "+v"(below[i]));          // (a compare and an add with carry per key: the optimizer otherwise packs the counts of the rows into bytes)
+        }
+    }
+    xrun_order();
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+        if (i + 1 < NR || last) stage[pos[i] + below[i]] = r[i];
+    xrun_order();
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+        if (i + 1 < NR || last) r[i] = stage[(unsigned)(i * WAVE) + lane];
+    xrun_order();
+    return true;
+}
+
 // ---------------------------------------------------------------------------
 // The last 16 prefix bits on chip (engine.hpp: onew_bucket_passes, group form).  The records that agree in everything above their
 // low 16 prefix bits form a group, [starts[g], starts[g + 1]); groups hold n / 2^24 records at 32 prefix bits in the word -- 256 at
 // n = 2^32.  A wave owns whole groups: it takes 64 consecutive groups per trip (they lie in ONE bucket of the pass before: 256 groups
 // each, numbered from a multiple of 256), cuts them into batches of whole groups of at most GROUP_CAP records, reads a batch into
-// registers, orders it by stable 8-bit counting rounds through its own counters and stage in LDS -- two rounds for one group, a third
-// on the digit above for a batch of several groups (that digit numbers the groups of a bucket) -- and writes it back where it
-// came from, with the lowest prefix byte of every record beside it (tie_bytes).  In place is safe because the wave has read the whole
-// batch before it writes, and no other wave touches these groups.  No workgroup barrier.
+// registers, orders it through its own counters and stage in LDS, and writes it back where it came from, with the lowest prefix byte of every
+// record beside it (tie_bytes).  In place is safe because the wave has read the whole batch before it writes, and no other wave touches these
+// groups.  No workgroup barrier.
+// RANK: batches of at most GROUP_RANK_BATCH records, ordered by ONE counting round and the ranks inside its buckets (group_rank_rows); a batch with
+// a bucket too large for that, and a single group of more than GROUP_RANK_BATCH records, takes the way of the other form.
+// !RANK (PSACX_OPT_GROUP_COUNTING_ROUNDS): batches of at most GROUP_CAP records, ordered by stable 8-bit counting rounds -- two rounds for one
+// group, a third on the digit above for a batch of several groups (that digit numbers the groups of a bucket).
+// Both leave the stable order by the 16 bits inside every group, so the same records and tie bytes.
 // A group longer than GROUP_CAP is left as it is: the caller checks the largest group before it launches.
 // ---------------------------------------------------------------------------
 // (GROUP_CAP: sort_scratch.hpp -- the layouts of the group form depend on it)
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void group_sort16_kernel(uint64_t* __restrict__ recs, const unsigned long long* __restrict__ starts, uint64_t ngroups,
+template <int BLOCK, bool RANK = true>
+__global__ __launch_bounds__(BLOCK, RANK ? 5 : 1) void group_sort16_kernel(uint64_t* __restrict__ recs, const unsigned long long* __restrict__ starts, uint64_t ngroups,
                                                              uint64_t nrec, int sfield, uint8_t* __restrict__ tie_bytes) {
     constexpr int NW = BLOCK / WAVE, ROWS = GROUP_CAP / WAVE;
+    constexpr unsigned BATCH = RANK ? GROUP_RANK_BATCH : (unsigned)GROUP_CAP;          // records of a batch of several groups
+    static_assert(GROUP_RANK_BATCH == 6 * WAVE, "group_rank_rows is instantiated for one to six rows");
     __shared__ unsigned s_cnt[NW][RADIX];
     __shared__ uint64_t s_stage[NW][GROUP_CAP];
     const unsigned wave = threadIdx.x / WAVE, lane = lane_id();
@@ -1011,20 +1094,37 @@ __global__ __launch_bounds__(BLOCK) void group_sort16_kernel(uint64_t* __restric
         if (__ballot(snext < s || snext > nrec)) continue;          // (tables that are not what they must be: nothing is touched)
         unsigned g = 0;
         while (g < (unsigned)WAVE) {
-            const uint64_t a = shfl<uint64_t>(s, (int)g);
-            // the groups g .. g + run - 1 end at most GROUP_CAP records behind a (the starts are monotone: the lanes that fit come first)
-            const uint64_t fit = __ballot(snext - a <= (uint64_t)GROUP_CAP) >> g;
-            const unsigned run = ~fit ? (unsigned)__builtin_ctzll(~fit) : (unsigned)WAVE;
+            uint64_t a = shfl<uint64_t>(s, (int)g);
+            if constexpr (RANK) a = wave_uniform64(a);          // (the same in every lane: addresses from a scalar base)
+            // the groups g .. g + run - 1 end at most BATCH records behind a (the starts are monotone: the lanes that fit come first)
+            const uint64_t fit = __ballot(snext - a <= (uint64_t)BATCH) >> g;
+            unsigned run = ~fit ? (unsigned)__builtin_ctzll(~fit) : (unsigned)WAVE;
+            if (RANK && run == 0 && ((__ballot(snext - a <= (uint64_t)GROUP_CAP) >> g) & 1)) run = 1;          // (a group between BATCH and GROUP_CAP: a batch of its own)
             if (run == 0) { ++g; continue; }
-            const unsigned count = (unsigned)(shfl<uint64_t>(snext, (int)(g + run - 1)) - a);
+            unsigned count = (unsigned)(shfl<uint64_t>(snext, (int)(g + run - 1)) - a);
+            if constexpr (RANK) count = __builtin_amdgcn_readfirstlane(count);
             const unsigned filled = (unsigned)__builtin_popcountll(__ballot(lane >= g && lane < g + run && snext != s));
             g += run;
             if (count == 0) continue;
-            const int rounds = count == 1 ? 0 : filled > 1 ? 3 : 2;
+            int rounds = count == 1 ? 0 : filled > 1 ? 3 : 2;
             const unsigned rows = (count + WAVE - 1) / WAVE;
             uint64_t r[ROWS];
 #pragma unroll
             for (int i = 0; i < ROWS; ++i) r[i] = (unsigned)(i * WAVE) + lane < count ? recs[a + (unsigned)(i * WAVE) + lane] : 0ull;
+            if (RANK && rounds) {
+                const unsigned first = (unsigned)(g0 + g - run) & (RADIX - 1), gbits = group_rank_gbits(run);
+                bool done = false;
+                switch (__builtin_amdgcn_readfirstlane(rows)) {          // (the rows as a constant: no branch per row inside)
+                case 1: done = group_rank_rows<1>(r, cnt, stage, count, sfield, first, gbits, lane); break;
+                case 2: done = group_rank_rows<2>(r, cnt, stage, count, sfield, first, gbits, lane); break;
+                case 3: done = group_rank_rows<3>(r, cnt, stage, count, sfield, first, gbits, lane); break;
+                case 4: done = group_rank_rows<4>(r, cnt, stage, count, sfield, first, gbits, lane); break;
+                case 5: done = group_rank_rows<5>(r, cnt, stage, count, sfield, first, gbits, lane); break;
+                case 6: done = group_rank_rows<6>(r, cnt, stage, count, sfield, first, gbits, lane); break;
+                default: break;          // (more than GROUP_RANK_BATCH records: one group, the counting rounds)
+                }
+                if (done) rounds = 0;
+            }
             for (int rd = 0; rd < rounds; ++rd) {
                 const int shift = sfield + rd * RADIX_BITS;
 #pragma unroll

@@ -42,7 +42,7 @@ class Context(object):
     def configure(self, **options):
         """psacx_configure: pins the form of single stages (include/psacx.h), e.g. configure(force_diet=1, diet_cap=1 << 20), configure(reset=0)."""
         for name, value in options.items():
-            self.check(self._lib.psacx_configure(self.handle, _lib.OPTIONS[name], int(value)))
+            self.check(self._lib.psacx_configure(self.handle, _lib.OPTIONS[name] if name in _lib.OPTIONS else _lib.KERNEL_OPTIONS[name], int(value)))
 
     def _pre(self):
         """Before every call that runs the engine: with _lib.ENV_KNOBS the options come from PSACX_* variables (debug shim)."""
