@@ -24,6 +24,21 @@ launches, (a) .. (h) below:
                                   three-word records whose 32-bit payloads come in as such -- (d) and (f) with v32_in -- and refinement rounds
   u32 string set 2^21             inputs.dna(2^21, 9) cut into some 20 000 strings: key_pairs_kernel<..., GSA> and one sort over both words:
                                   (g) <false, 1> three-word records, word payloads
+The first round's two ways from the two-stage sort to one sort over both words, and the reduced-memory layout in its first-round forms (the
+texts are those of test_gpu_parity.py; test_the_recorded_cases_reach_their_paths holds the relations that show each path was taken):
+  u64 rep probe                   a tiled text: the probe of the one-word sort finds nearly every sampled prefix repeated -> one sort over both words
+  u64 rep probe first_lead40      ... the same with room for the tables of the one-word passes (a text of 2^22 characters in 256 even buckets has none in
+                                  the scratch of its size; PSACX_FIRST_LEAD=40 adds the supplement of carve): the probe alone stands between this case and
+  u64 rep always first_lead40     ... the probe off (PSACX_ONE_WORD_ALWAYS): the one-word passes run
+  u64 third                       a third of the text repeats: the one-word sort gives up before it writes anything (PSACX_RETRY_1W: the probe's lower threshold,
+                                  and at this size no room for its tables either), two stages stay: the keys are made and the two-array passes run
+  u64 third no_one_word           ... the same passes asked for outright (PSACX_NO_ONE_WORD)
+  u64 / u32 tandem diet           inputs.tandem(2^21 + 5, 1024, ...), PSACX_FORCE_DIET, PSACX_DIET_CAP=2^19: more ties than the reduced layout has room
+                                  for -> the first round again as one sort (the abandoned attempt's passes stay in the counters), rounds in slabs
+  u64 / u32 tandem diet one_stage ... one sort from the start (PSACX_ONE_STAGE)
+  u64 dna diet                    inputs.dna(2^22 + 1, 6), PSACX_FORCE_DIET: two stages in the reduced layout, an even number of passes that starts from the
+                                  output buffers (no room for the one-word tables at this size: the keys are made, two-array passes)
+  u64 dna diet 2^23               the text of `u64 dna default`, PSACX_FORCE_DIET: the one-word form in the reduced layout, the same parity rule
 
 `python tests/test_gpu_sort_driver_stats.py --record <commit>` writes the JSON (on a GPU) with the commit it was recorded on."""
 import json
@@ -58,8 +73,25 @@ def _string_set():
     return [bytes(text[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
 
+def _rep():
+    rep = np.tile(inputs.dna(1 << 12, 9), 1 << 10)
+    rep[::4099] = 84
+    return rep
+
+
+def _third():
+    third = inputs.dna((1 << 22) + 9, 31)
+    third[: (1 << 22) // 3] = np.tile(inputs.dna(1 << 11, 33), (1 << 22) // 3 // (1 << 11) + 1)[: (1 << 22) // 3]
+    return third
+
+
+def _tandem():
+    return inputs.tandem((1 << 21) + 5, 1024, inputs.dna(1024, 3))
+
+
 # name -> (index bits, text maker, string set?, PSACX_* variables)
 ONE_WORD = {"PSACX_ONE_WORD_MIN": "21"}
+DIET = {"PSACX_FORCE_DIET": "1", "PSACX_DIET_CAP": str(1 << 19)}
 CASES = {
     "u64 dna default": (64, _dna_n1, False, ONE_WORD),
     "u64 dna first_lead40": (64, _dna_n1, False, dict(ONE_WORD, PSACX_FIRST_LEAD="40")),
@@ -73,6 +105,17 @@ CASES = {
     "u64 dna 2^20+3": (64, lambda: inputs.dna((1 << 20) + 3, 7), False, {}),
     "u64 two_symbols 2^23+3": (64, _two_symbols, False, dict(ONE_WORD, PSACX_ONE_WORD_ALWAYS="1")),
     "u32 string set 2^21": (32, _string_set, True, {}),
+    "u64 rep probe": (64, _rep, False, ONE_WORD),
+    "u64 rep probe first_lead40": (64, _rep, False, dict(ONE_WORD, PSACX_FIRST_LEAD="40")),
+    "u64 rep always first_lead40": (64, _rep, False, dict(ONE_WORD, PSACX_FIRST_LEAD="40", PSACX_ONE_WORD_ALWAYS="1")),
+    "u64 third": (64, _third, False, ONE_WORD),
+    "u64 third no_one_word": (64, _third, False, dict(ONE_WORD, PSACX_NO_ONE_WORD="1")),
+    "u64 tandem diet": (64, _tandem, False, DIET),
+    "u32 tandem diet": (32, _tandem, False, DIET),
+    "u64 tandem diet one_stage": (64, _tandem, False, dict(DIET, PSACX_ONE_STAGE="1")),
+    "u32 tandem diet one_stage": (32, _tandem, False, dict(DIET, PSACX_ONE_STAGE="1")),
+    "u64 dna diet": (64, lambda: inputs.dna((1 << 22) + 1, 6), False, dict(ONE_WORD, PSACX_FORCE_DIET="1")),
+    "u64 dna diet 2^23": (64, _dna_n1, False, dict(ONE_WORD, PSACX_FORCE_DIET="1")),
 }
 KNOBS = sorted({k for c in CASES.values() for k in c[3]})
 
@@ -122,6 +165,23 @@ def test_the_recording_holds_these_cases_only(golden):
     keys = sorted(["scatter_launches", "scatter_records", "scatter_bytes", "hist_bytes", "onew_passes", "group_sort", "workspace_bytes",
                    "round0_sort_passes", "round0_sort_passes_skipped"])
     assert all(sorted(v) == keys for v in golden["cases"].values())
+
+
+def test_the_recorded_cases_reach_their_paths(golden):
+    # equality with a recording does not show that a case takes the path it is named for: these relations between recorded values do
+    c = golden["cases"]
+    # the probe gave the two-stage sort up before any one-word pass; with the probe off the passes run
+    for name in ("u64 rep probe", "u64 rep probe first_lead40"):
+        assert c[name]["onew_passes"] == 0 and c[name]["group_sort"] == 0
+    assert c["u64 rep always first_lead40"]["onew_passes"] > 0
+    # the probe kept two stages in two-array passes: the launches of the form asked for outright
+    assert c["u64 third"]["onew_passes"] == 0
+    assert c["u64 third"]["scatter_launches"] == c["u64 third no_one_word"]["scatter_launches"]
+    # the passes of the abandoned two-stage attempt are counted on top of those of the one sort that stood
+    for bits in ("u64", "u32"):
+        assert sum(c[bits + " tandem diet"]["scatter_launches"]) > sum(c[bits + " tandem diet one_stage"]["scatter_launches"])
+    # the one-word form ran in the reduced layout
+    assert c["u64 dna diet 2^23"]["onew_passes"] > 0 and c["u64 dna diet 2^23"]["workspace_bytes"] < c["u64 dna default"]["workspace_bytes"]
 
 
 def record(commit):
