@@ -157,14 +157,17 @@ int psacx_trim(psacx_ctx* ctx);
  *                     level of the parse, the walk over the groups included, is taken at a few hundred positions; the parse is the same
  *   GRID_CAP          test option: 1..65535 = every grid-stride kernel is launched on at most this many workgroups, not on the default bound of a few
  *                     workgroups per CU, so that the second and later trips of its loop are taken at a few thousand items (psacx_stats.grid_cuts counts
- *                     the launches that were cut); 0 = the default bound; larger values are refused; no result changes     */
+ *                     the launches that were cut); 0 = the default bound; larger values are refused; no result changes
+ *   MEMS_STOP         timing option (tools/mems_time.py): 1..3 = psacx_mems_dev_* without PSACX_MEMS_SUPER returns PSACX_OK with z = 0 after its
+ *                     counting walk and the two scans (1), after the writing walk (2), after the marks (3), synchronised; work is set as usual; the
+ *                     differences of the times are the times of the stages.  0 = the whole call; larger values are refused                      */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
     PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD, PSACX_OPT_LZ_SMALL_TILES,
-    PSACX_OPT_GRID_CAP, PSACX_OPT_GROUP_COUNTING_ROUNDS,
+    PSACX_OPT_GRID_CAP, PSACX_OPT_GROUP_COUNTING_ROUNDS, PSACX_OPT_MEMS_STOP,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
@@ -955,6 +958,84 @@ int psacx_repeats_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uin
 int psacx_repeats_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
                       const uint64_t* LCP, uint32_t kind, uint64_t min_len, uint64_t min_occ, uint64_t max_occ, uint64_t* lb, uint64_t* ub,
                       uint64_t* len, uint64_t cap, uint64_t* z);
+
+/* maximal exact matches ------------------------------------------------------------------
+ * The maximal exact matches (MEMs) of a batch of patterns against the indexed text: the seeds of read mapping and the anchors of
+ * genome alignment (MUMmer, essaMEM, BWA-MEM).  They follow from the matching statistics of psacx_match_dev_* by walking the
+ * LCP-intervals that enclose each slot's interval, with the BWT for the left side.  No text is read.  The reference has no
+ * counterpart.  One GPU.
+ *
+ * Setting, as for the repeats above.  One text S[0..n), or a string set whose suffix i is S[i..end(i)).  L[r] = LCP[r], with L[0]
+ * and L[n] read as 0.  Ranks are SA indices.  Patterns are pat / poff as for psacx_match_dev_*; a slot p in [0, poff[q]) is a byte
+ * of the pattern buffer and belongs to the pattern j with poff[j] <= p < poff[j+1].
+ *
+ * A MEM is a triple (p, t, l) with l >= max(min_len, 1) and pat[p..p+l) == S[t..t+l), where
+ *  - the match lies inside pattern j and inside the string of t;
+ *  - it is not right-extensible: p + l == poff[j+1], or t + l == end(t), or the next bytes differ;
+ *  - it is not left-extensible: p == poff[j], or t starts a string, or pat[p-1] != S[t-1];
+ *  - with max_occ > 0, pat[p..p+l) has at most max_occ occurrences (the size of its locate interval); max_occ == 1 gives the matches
+ *    that are unique in the indexed text;
+ *  - with PSACX_MEMS_SUPER, only MEMs whose pattern range [p, p+l) is contained in no other MEM's range of the same pattern are kept
+ *    (SMEMs).  These are exactly the triples (p, SA[r], len_p) for r in [lb_p, ub_p) of the slots with p == poff[j] or
+ *    len_{p-1} <= len_p, under the same min_len / max_occ filters; they need no left-character test.
+ *
+ * From the statistics (len_p, lb_p, ub_p) of slot p, uncapped (max_len == 0):
+ *  - Shell 0 is [lb_p, ub_p) with l = len_p.
+ *  - The next shell has l' = max(L[lb], L[ub]), which is < l.  Its interval is lb' = the largest x <= lb with L[x] < l' and
+ *    ub' = the smallest y >= ub with L[y] < l', or n.  Its ranks are [lb', lb) and [ub, ub').
+ *  - Every rank of a shell matches pat[p..] in exactly that shell's l bytes and is right-maximal.
+ *  - The walk ends at the first shell with l < max(min_len, 1), or with max_occ > 0 and ub' - lb' > max_occ.  That shell is not
+ *    counted as walked.
+ *  - A rank r of a shell is a candidate.  It is a MEM iff p == poff[j], or bit r of `first` is set, or bwt[r] != pat[p-1].
+ *
+ * Output order, pinned: ascending slot; inside a slot descending l; inside a shell ascending rank.
+ *
+ * psacx_mems_dev_*: d_index is the index of psacx_rmq_index_dev_* over d_LCP; d_bwt / d_first are the outputs of psacx_bwt_dev_*;
+ * d_mlen / d_mlb / d_mub are the three outputs of psacx_match_dev_* or psacx_match_gsa_dev_* with PSACX_MATCH_SUFFIXES and
+ * max_len == 0, poff[q] entries each.
+ *  - Output: z triples, d_qpos (the slot), d_tpos = SA[r] and d_len (index type).
+ *  - d_qpos == NULL is the count query; d_tpos and d_len must then be NULL too, and none of them otherwise (PSACX_EINVAL).
+ *  - z > cap returns PSACX_ERANGE with *z valid and nothing written to the lists.  *z is always set.
+ *  - Unknown flag bits return PSACX_EINVAL.  poff[0] != 0 or a descending pair returns PSACX_EINVAL, found on the device before any
+ *    result is written.  q == 0 or n == 0 gives z = 0.  n beyond the index type, or beyond 2^48, returns PSACX_ERANGE.
+ *  - min_len 0 and 1 mean the same.
+ *  - work may be NULL.  Otherwise work[0] is the number of shells walked and work[1] the number of candidates tested; with
+ *    PSACX_MEMS_SUPER, the slots kept and their ranks.  Both are functions of the inputs alone: max_occ bounds the work, not only
+ *    the output.
+ *  - With PSACX_MEMS_SUPER neither d_LCP, d_index, d_bwt, d_first nor d_pat is read, and each may be NULL.  The count query does not
+ *    read d_SA.
+ *  - Totality, whatever the arrays hold: nothing is read or written out of range (d_first inside its (n >> 5) + 1 words); every walk
+ *    ends, since a step that does not strictly lower l ends it; a statistics entry with lb >= ub or ub > n gives no shell; d_mlen is
+ *    cut to the rest of the pattern, so every triple has l >= 1 and p + l <= poff[j+1]; tpos is the SA entry as it is.  No input is
+ *    written.
+ *  - Sixteen lanes per slot walk the shells, twice: once to count, once to write the shell records.  The candidates are then tested
+ *    by workgroups that own 1024 candidate numbers each, whatever the shells are, so a slot with millions of candidates is spread
+ *    over as many workgroups as it fills; one bwt byte and one bit of `first` per candidate, one SA entry per MEM.
+ *  - Scratch.  In the ctx slab, with s = poff[q] + 1: the shell and candidate counts per slot, 2 * 8 s bytes (8 s + 8 with
+ *    PSACX_MEMS_SUPER), behind the block sums of the scans, 8 bytes per 4096 of s beyond 4 KiB; each part rounded up to 256 bytes.
+ *    Beside the slab and for the time of the call, with h shells, c candidates and t = ceil(c / 1024): the shell records,
+ *    4 h entries of the index type and 8 h bytes; their candidate starts, 8 (h + 1); the mark bytes, 1024 t; the tile counts,
+ *    8 (t + 1).  Where that fails the call returns PSACX_ENOMEM and the outputs are untouched.  PSACX_MEMS_SUPER allocates nothing
+ *    beside the slab.  The count query runs everything but the last kernel.
+ * psacx_mems_*: the host-pointer form.  offsets == NULL means one text (m is ignored); otherwise the m + 1 offsets of the strings,
+ * which must start at 0, end at n and ascend strictly (PSACX_EINVAL).  It stages the arrays, builds the bitmap of the string ends,
+ * the table when k > 0, the statistics, the index and the BWT, calls the device form and frees what it allocated on every path.
+ * qpos == NULL is the count query, z > cap returns PSACX_ERANGE with *z valid. */
+#define PSACX_MEMS_SUPER 1u
+int psacx_mems_dev_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* d_SA, const uint32_t* d_LCP, const uint32_t* d_index,
+                       const uint8_t* d_bwt, const uint32_t* d_first, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                       const uint32_t* d_mlen, const uint32_t* d_mlb, const uint32_t* d_mub, uint64_t min_len, uint64_t max_occ,
+                       uint32_t flags, uint64_t* d_qpos, uint32_t* d_tpos, uint32_t* d_len, uint64_t cap, uint64_t* z, uint64_t* work);
+int psacx_mems_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_SA, const uint64_t* d_LCP, const uint64_t* d_index,
+                       const uint8_t* d_bwt, const uint32_t* d_first, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q,
+                       const uint64_t* d_mlen, const uint64_t* d_mlb, const uint64_t* d_mub, uint64_t min_len, uint64_t max_occ,
+                       uint32_t flags, uint64_t* d_qpos, uint64_t* d_tpos, uint64_t* d_len, uint64_t cap, uint64_t* z, uint64_t* work);
+int psacx_mems_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                   const uint32_t* LCP, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint64_t min_len,
+                   uint64_t max_occ, uint32_t flags, uint64_t* qpos, uint32_t* tpos, uint32_t* len, uint64_t cap, uint64_t* z);
+int psacx_mems_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                   const uint64_t* LCP, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint64_t min_len,
+                   uint64_t max_occ, uint32_t flags, uint64_t* qpos, uint64_t* tpos, uint64_t* len, uint64_t cap, uint64_t* z);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

@@ -1041,4 +1041,78 @@ repeat_intervals<index_t> repeats(suffix_array<char, index_t, true, false>& sa, 
     return psacx::repeats_of(sa, text, &soff, kind, min_len, min_occ, max_occ);
 }
 
+// The maximal exact matches of a batch of patterns against the text (psacx.h: "maximal exact matches"): match i is
+// pattern bytes [qpos[i], qpos[i] + len[i]) -- qpos counts the bytes of the patterns laid back to back -- equal to the text at
+// tpos[i], at least min_len long and extensible on neither side inside its pattern and its string.  max_occ > 0 keeps matches whose
+// bytes occur at most that often, super those contained in no other match of their pattern.  Order: ascending qpos, then
+// descending len, then rank in local_SA.  The suffix array must have been constructed with its LCP.  One rank only, as match.
+template <typename index_t>
+struct mem_lists {
+    std::vector<uint64_t> qpos;
+    std::vector<index_t> tpos, len;
+};
+
+namespace psacx {
+
+template <typename index_t>
+mem_lists<index_t> mems_of(suffix_array<char, index_t, true, false>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff,
+                           const std::vector<std::string>& patterns, std::size_t min_len, unsigned int k, std::size_t max_occ, bool super) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, const uint32_t* l, const uint8_t* p,
+                       const uint64_t* po, uint64_t q, uint32_t k, uint64_t a, uint64_t b, uint32_t f, uint64_t* qp, uint32_t* tp, uint32_t* len,
+                       uint64_t cap, uint64_t* z) {
+            return psacx_mems_u32(c, t, n, o, m, s, l, p, po, q, k, a, b, f, qp, tp, len, cap, z);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, const uint64_t* l, const uint8_t* p,
+                       const uint64_t* po, uint64_t q, uint32_t k, uint64_t a, uint64_t b, uint32_t f, uint64_t* qp, uint64_t* tp, uint64_t* len,
+                       uint64_t cap, uint64_t* z) {
+            return psacx_mems_u64(c, t, n, o, m, s, l, p, po, q, k, a, b, f, qp, tp, len, cap, z);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: mems needs a single-rank communicator (the search runs on one GPU)");
+    if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n || sa.local_LCP.size() != sa.n)
+        throw std::runtime_error("mems: the suffix array holds no SA and LCP of this text");
+    std::vector<uint8_t> pat;
+    std::vector<uint64_t> poff(1, 0);
+    for (std::size_t i = 0; i < patterns.size(); ++i) {
+        pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+        poff.push_back((uint64_t)pat.size());
+    }
+    const W* s = reinterpret_cast<const W*>(sa.local_SA.data());
+    const W* l = reinterpret_cast<const W*>(sa.local_LCP.data());
+    const uint64_t* o = soff ? soff->data() : (const uint64_t*)0;
+    const uint64_t m = soff ? (uint64_t)soff->size() - 1 : 0, q = (uint64_t)patterns.size();
+    const uint32_t flags = super ? PSACX_MEMS_SUPER : 0u;
+    uint64_t z = 0;
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, l, pat.data(), poff.data(), q, k, min_len, max_occ, flags, (uint64_t*)0,
+                                  (W*)0, (W*)0, 0, &z));
+    std::vector<uint64_t> qpos(z + 1);
+    std::vector<W> tpos(z + 1), len(z + 1);
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, l, pat.data(), poff.data(), q, k, min_len, max_occ, flags, qpos.data(),
+                                  tpos.data(), len.data(), z, &z));
+    mem_lists<index_t> out;
+    out.qpos.assign(qpos.begin(), qpos.begin() + z);
+    out.tpos.assign(tpos.begin(), tpos.begin() + z);
+    out.len.assign(len.begin(), len.begin() + z);
+    return out;
+}
+
+} // namespace psacx
+
+template <typename index_t, typename Iterator>
+mem_lists<index_t> mems(suffix_array<char, index_t, true, false>& sa, Iterator begin, Iterator end, const std::vector<std::string>& patterns,
+                        std::size_t min_len, unsigned int k = 0, std::size_t max_occ = 0, bool super = false) {
+    return psacx::mems_of(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, patterns, min_len, k, max_occ, super);
+}
+
+template <typename index_t>
+mem_lists<index_t> mems(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, const std::vector<std::string>& patterns,
+                        std::size_t min_len, unsigned int k = 0, std::size_t max_occ = 0, bool super = false) {
+    std::vector<uint8_t> text; std::vector<uint64_t> soff;
+    psacx::flatten_set(ss, text, soff);
+    return psacx::mems_of(sa, text, &soff, patterns, min_len, k, max_occ, super);
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -59,19 +59,6 @@ static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* en
                   const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) {
     return psacx_locate_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, lb, ub);
 }
-static int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, const uint32_t* tab, uint32_t k, const uint16_t* code,
-                 const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint32_t* len, uint32_t* lb,
-                 uint32_t* ub) {
-    return ends ? psacx_match_gsa_dev_u32(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
-                : psacx_match_dev_u32(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
-}
-static int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code,
-                 const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint64_t* len, uint64_t* lb,
-                 uint64_t* ub) {
-    return ends ? psacx_match_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
-                : psacx_match_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
-}
-
 // soff: the offsets of the strings of --set (empty without it); occ: print the occurrences, at most limit each if limit > 0;
 // longest: --longest, with mflags (PSACX_MATCH_SUFFIXES for --suffixes) and max_len
 template <typename IT>

@@ -1,6 +1,6 @@
-// Shared by the query command lines (locate, lce, overlaps, lz77, repeats): the error rule, a wall clock, the readers of their
+// Shared by the query command lines (locate, lce, overlaps, lz77, repeats, mems): the error rule, a wall clock, the readers of their
 // inputs, the --index choice, the owner of the ctx and the device memory of a run, and the u32 / u64 overload pairs of the calls that
-// more than one of them makes.  read_file is the one of bench_common.hpp.
+// more than one of them makes (construction, index, occurrences, longest match, BWT).  read_file is the one of bench_common.hpp.
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -78,6 +78,26 @@ inline int occurrences(psacx_ctx* c, const uint32_t* sa, uint64_t n, const uint6
 inline int occurrences(psacx_ctx* c, const uint64_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* lb, const uint64_t* ub, uint64_t q,
                        uint64_t limit, uint64_t* start, uint64_t* pos, uint64_t* sid, uint64_t cap, uint64_t* total) {
     return psacx_occurrences_dev_u64(c, sa, n, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
+}
+
+// ends == nullptr: one text
+inline int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, const uint32_t* tab, uint32_t k, const uint16_t* code,
+                 const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint32_t* len, uint32_t* lb,
+                 uint32_t* ub) {
+    return ends ? psacx_match_gsa_dev_u32(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
+                : psacx_match_dev_u32(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
+}
+inline int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, const uint64_t* tab, uint32_t k, const uint16_t* code,
+                 const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint64_t* len, uint64_t* lb,
+                 uint64_t* ub) {
+    return ends ? psacx_match_gsa_dev_u64(c, t, n, ends, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub)
+                : psacx_match_dev_u64(c, t, n, sa, tab, k, code, pat, poff, q, flags, max_len, entries, len, lb, ub);
+}
+inline int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, uint8_t* b, uint32_t* f, uint64_t* p) {
+    return psacx_bwt_dev_u32(c, t, n, ends, sa, b, f, p);
+}
+inline int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, uint8_t* b, uint32_t* f, uint64_t* p) {
+    return psacx_bwt_dev_u64(c, t, n, ends, sa, b, f, p);
 }
 
 // the range-minimum index of d_values, in memory of the session: the size query, then the build

@@ -27,12 +27,6 @@ static void usage() {
                  "repeat: it is the len bytes at pos and occurs at SA[lb .. ub).  --bwt writes the SA-aligned BWT and prints the primary.\n";
 }
 
-static int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, uint8_t* b, uint32_t* f, uint64_t* p) {
-    return psacx_bwt_dev_u32(c, t, n, ends, sa, b, f, p);
-}
-static int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, uint8_t* b, uint32_t* f, uint64_t* p) {
-    return psacx_bwt_dev_u64(c, t, n, ends, sa, b, f, p);
-}
 static int repeats(psacx_ctx* c, uint64_t n, const uint32_t* lcp, const uint32_t* index, const uint8_t* b, const uint32_t* f, uint32_t kind, uint64_t l,
                    uint64_t lo, uint64_t hi, uint32_t* lb, uint32_t* ub, uint32_t* len, uint64_t cap, uint64_t* z) {
     return psacx_repeats_dev_u32(c, n, lcp, index, b, f, kind, l, lo, hi, lb, ub, len, cap, z);

@@ -75,6 +75,7 @@ struct Knobs {
     bool lz_small_tiles = false;  // PSACX_OPT_LZ_SMALL_TILES: the LZ77 parse works on tiles of 64 positions in groups of 4 (tests: every level of lz.hpp at a few hundred positions)
     int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (search.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
+    unsigned mems_stop = 0;       // PSACX_OPT_MEMS_STOP: psacx_mems_dev_* returns after this stage with z = 0 (tools/mems_time.py times the stages by it)
     unsigned grid_cap = 0;        // PSACX_OPT_GRID_CAP: grid_for cuts every grid to at most this many workgroups, not n_cu * per_cu (tests: the second and
                                   // later trips of the grid-stride loops at a few thousand items; 0 = the default bound)
 };

@@ -1,4 +1,4 @@
-// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, and check.hip and
+// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, and check.hip and
 // ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
 // that moves in one place alone does not compile.
 #pragma once
@@ -26,6 +26,12 @@ int ansv_dev_u64(psacx_ctx* c, const uint64_t* in, uint64_t n, int lt, int rt, u
 // there for both widths
 template <typename T>
 int rmq_index_dev(psacx_ctx* c, const T* d_values, uint64_t n, T* d_index, uint64_t* entries);
+
+// mems.hip: psacx_mems_dev_* itself (kernels in mems.hpp; waits), instantiated there for both widths
+template <typename T>
+int mems_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const T* d_LCP, const T* d_index, const uint8_t* d_bwt, const uint32_t* d_first,
+             const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, const T* d_mlen, const T* d_mlb, const T* d_mub, uint64_t min_len,
+             uint64_t max_occ, uint32_t flags, uint64_t* d_qpos, T* d_tpos, T* d_len, uint64_t cap, uint64_t* z, uint64_t* work);
 
 constexpr uint64_t RMQ_MAX_N = 1ull << 48;             // 64^PYR_MAX: the top level of the range-minimum index is one group
 

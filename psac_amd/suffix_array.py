@@ -259,6 +259,16 @@ class SuffixArray(object):
             raise ValueError("repeats needs construct or construct_ss with lcp=True first")
         return repeats(self._text, self.local_SA, self.local_LCP, kind, min_len, min_occ, max_occ, offsets=self._text_off, ctx=self.ctx)
 
+    def mems(self, patterns, min_len, k=0, max_occ=0, super=False):
+        """(qpos, tpos, len) of the maximal exact matches of the patterns against the text or string set of the last construct /
+        construct_ss (which needs lcp=True): mems() over its arrays."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("mems needs a single-rank context (the search runs on one GPU)")
+        if getattr(self, "_text", None) is None or self._text.size != self.n or not self.lcp or self.local_LCP.size != self.n:
+            raise ValueError("mems needs construct or construct_ss with lcp=True first")
+        return mems(self._text, self.local_SA, self.local_LCP, patterns, min_len, k=k, offsets=self._text_off, max_occ=max_occ, super=super,
+                    ctx=self.ctx)
+
     def construct_device(self, d_text, n, d_sa, d_isa, d_lcp=None, fast_resolval=True, k=0, profile=False, d_lc=None):
         """Same with every buffer already resident in HBM (raw device addresses)."""
         args = [self.ctx.handle, C.c_void_p(d_text), int(n), int(k), self._flags(fast_resolval, profile),
@@ -841,6 +851,60 @@ def repeats(text, SA, LCP, kind="maximal", min_len=1, min_occ=2, max_occ=0, offs
     lb, ub, ln = (np.zeros(max(1, z.value), sa.dtype) for _ in range(3))
     ctx.check(fn(*(head + [_ptr(lb), _ptr(ub), _ptr(ln), z.value, C.byref(z)])))
     return lb[:z.value], ub[:z.value], ln[:z.value]
+
+
+MEMS_SUPER = _lib.PSACX_MEMS_SUPER
+
+
+def mems_device(ctx, n, d_sa, d_lcp, d_index, d_bwt, d_first, d_pat, d_poff, q, d_mlen, d_mlb, d_mub, min_len, max_occ, flags, d_qpos, d_tpos,
+                d_len, cap, index_bits, work=None):
+    """psacx_mems_dev_*: the maximal exact matches of q patterns against the index resident in HBM (include/psacx.h: "maximal exact
+    matches"), from SA, LCP, the index of rmq_index_device over it, the two outputs of bwt_device and the three outputs of
+    match_device / match_gsa_device with MATCH_SUFFIXES and max_len = 0.  flags is 0 or MEMS_SUPER.  d_qpos (uint64) / d_tpos / d_len
+    receive z entries each in the pinned order; d_qpos=None is the count query.  work, where given, is a list that receives the two
+    work counters.  Returns z; raises PsacxError -2 where z exceeds cap, with the lists untouched and z in the error's attribute z."""
+    fn = getattr(ctx._lib, "psacx_mems_dev_u%d" % index_bits)
+    z = C.c_uint64(0)
+    w = (C.c_uint64 * 2)()
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, int(n), opt(d_sa), opt(d_lcp), opt(d_index), opt(d_bwt), opt(d_first), opt(d_pat), opt(d_poff), int(q), opt(d_mlen),
+                     opt(d_mlb), opt(d_mub), int(min_len), int(max_occ), int(flags), opt(d_qpos), opt(d_tpos), opt(d_len), int(cap), C.byref(z),
+                     w if work is not None else None))
+    except PsacxError as e:
+        e.z = z.value
+        raise
+    finally:
+        if work is not None:
+            work[:] = [int(w[0]), int(w[1])]
+    return z.value
+
+
+def mems(text, SA, LCP, patterns, min_len, k=0, offsets=None, max_occ=0, super=False, ctx=None):
+    """psacx_mems_*: (qpos, tpos, len) of the maximal exact matches of the patterns against the text: MEM i is
+    pat[qpos[i]:qpos[i] + len[i]] == text[tpos[i]:tpos[i] + len[i]] with len[i] >= min_len, extensible on neither side inside its
+    pattern and its string; qpos counts bytes of the pattern buffer (pattern_buffer(patterns)).  max_occ > 0 keeps matches whose
+    bytes occur at most that often (1: unique in the text); super=True keeps those contained in no other match of their pattern
+    (SMEMs).  Order: ascending qpos, then descending len, then suffix-array rank.  k > 0 puts the k-mer lookup table in front of
+    the matching statistics.  offsets: text is a string set and SA / LCP its generalized arrays.  Host arrays; everything is staged."""
+    sa, lcp = _sa_lcp(SA, LCP, "mems")
+    t = _text_bytes(text)
+    if t.size != sa.size:
+        raise ValueError("SA and LCP must have one entry per byte of the text")
+    pat, off = pattern_buffer(patterns)
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    ctx = ctx if ctx is not None else Context(0)
+    ctx._pre()
+    fn = getattr(ctx._lib, "psacx_mems_u%d" % (sa.dtype.itemsize * 8))
+    z = C.c_uint64(0)
+    head = [ctx.handle, _ptr(t), t.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(sa), _ptr(lcp),
+            _ptr(pat) if pat.size else None, _ptr(off), int(off.size - 1), int(k), int(min_len), int(max_occ), MEMS_SUPER if super else 0]
+    ctx.check(fn(*(head + [None, None, None, 0, C.byref(z)])))
+    qpos = np.zeros(max(1, z.value), np.uint64)
+    tpos, ln = (np.zeros(max(1, z.value), sa.dtype) for _ in range(2))
+    ctx.check(fn(*(head + [_ptr(qpos), _ptr(tpos), _ptr(ln), z.value, C.byref(z)])))
+    return qpos[:z.value], tpos[:z.value], ln[:z.value]
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
