@@ -160,14 +160,17 @@ int psacx_trim(psacx_ctx* ctx);
  *                     the launches that were cut); 0 = the default bound; larger values are refused; no result changes
  *   MEMS_STOP         timing option (tools/mems_time.py): 1..3 = psacx_mems_dev_* without PSACX_MEMS_SUPER returns PSACX_OK with z = 0 after its
  *                     counting walk and the two scans (1), after the writing walk (2), after the marks (3), synchronised; work is set as usual; the
- *                     differences of the times are the times of the stages.  0 = the whole call; larger values are refused                      */
+ *                     differences of the times are the times of the stages.  0 = the whole call; larger values are refused
+ *   KMISMATCH_STOP    timing option (tools/kmismatch_time.py): 1..2 = psacx_kmismatch_dev_* returns PSACX_OK with z = 0 after the piece searches
+ *                     and the scan of their counts (1), after the marks (2), synchronised; work is set as far as it is known; the count query is
+ *                     the stage after them.  0 = the whole call; larger values are refused                                                      */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
     PSACX_OPT_ISA_UPDATE, PSACX_OPT_GATHER, PSACX_OPT_NO_HEAVY, PSACX_OPT_NO_WHOLE, PSACX_OPT_NO_LAZY_RANKS, PSACX_OPT_NO_EARLY_OUT,
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
     PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD, PSACX_OPT_LZ_SMALL_TILES,
-    PSACX_OPT_GRID_CAP, PSACX_OPT_GROUP_COUNTING_ROUNDS, PSACX_OPT_MEMS_STOP,
+    PSACX_OPT_GRID_CAP, PSACX_OPT_GROUP_COUNTING_ROUNDS, PSACX_OPT_MEMS_STOP, PSACX_OPT_KMISMATCH_STOP,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
@@ -1036,6 +1039,74 @@ int psacx_mems_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64
 int psacx_mems_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
                    const uint64_t* LCP, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint64_t min_len,
                    uint64_t max_occ, uint32_t flags, uint64_t* qpos, uint64_t* tpos, uint64_t* len, uint64_t cap, uint64_t* z);
+
+/* pattern search with mismatches ----------------------------------------------------------
+ * Where a pattern occurs in the indexed text with at most e substituted bytes (Hamming distance): what a read mapper does with the
+ * seeds of the calls above.  The pattern is cut into e + 1 pieces, one of which must occur exactly (pigeonhole); the pieces are
+ * searched by the pattern search, and every occurrence of a piece is verified against the text.  No insertions or deletions.  The
+ * reference has no counterpart.  One GPU.
+ *
+ * Setting, as for psacx_locate_dev_* and psacx_locate_gsa_dev_*.  One text S[0..n), or a string set whose suffix i is S[i..end(i));
+ * for a set, d_ends is the bitmap of psacx_string_ends_dev.  Patterns are pat / poff as for psacx_locate_dev_*.  e is the number of
+ * mismatches allowed, 0 <= e <= 15 (PSACX_EINVAL above).
+ *
+ * A hit is a triple (j, t, d) where
+ *  - pattern j has m_j bytes and t + m_j <= n;
+ *  - the window [t, t + m_j) lies inside one string: for a set, no bit of d_ends is set at t + 1 .. t + m_j - 1;
+ *  - d = #{ x < m_j : pat[poff[j] + x] != S[t + x] } <= e.
+ * A pattern with m_j < e + 1 has no hits (every window would be one) and owns no candidate.
+ *
+ * Pieces.  Pattern j is cut at b_i = floor(i m_j / (e + 1)), i = 0 .. e + 1: e + 1 non-empty pieces that tile it.  The boundaries of
+ * all patterns are a valid offset array of q (e + 1) patterns over the same pattern buffer, and the pieces are searched as
+ * psacx_locate_dev_* (with d_ends: psacx_locate_gsa_dev_*) searches them; with a table, a piece of at most k bytes takes no search.
+ *
+ * Candidates.  Every rank r of the interval of piece i of pattern j is a candidate, with s = SA[r] and t = s - b_i.  It is tested iff
+ * s >= b_i, s < n, t + m_j <= n and the window lies inside one string.  It is a hit iff d <= e and each of the pieces 0 .. i - 1 has
+ * at least one mismatch at this alignment: every hit has an exact piece, and it is reported from its first one, exactly once.
+ *
+ * Output order, pinned: ascending pattern; inside a pattern ascending piece; inside a piece ascending rank.
+ *
+ * psacx_kmismatch_dev_*: d_table / k / code as for psacx_locate_dev_*: the table of psacx_lookup_table_dev_*, or with d_ends that of
+ * psacx_lookup_table_gsa_dev_*, with its k and code[], or NULL, 0, NULL; any other mix returns PSACX_EINVAL.
+ *  - Output: z triples, d_qid (the pattern, uint64), d_tpos = t (index type) and d_dist = d (uint8).
+ *  - d_qid == NULL is the count query; d_tpos and d_dist must then be NULL too, and none of them otherwise (PSACX_EINVAL).
+ *  - z > cap returns PSACX_ERANGE with *z valid and nothing written to the lists.  *z is always set.
+ *  - work may be NULL.  Otherwise work[0] is the number of candidates and work[1] the number tested.  Both are functions of the
+ *    inputs alone.
+ *  - With max_cand > 0 and work[0] > max_cand the call returns PSACX_ERANGE before anything sized by the candidates is allocated;
+ *    *z = 0 and work[0] is valid.  A pattern of a repeat can own n candidates per piece: this is the guard.
+ *  - poff[0] != 0 or a descending pair returns PSACX_EINVAL, found on the device before any result is written.  q == 0 or n == 0
+ *    gives z = 0.  n beyond the index type returns PSACX_ERANGE.
+ *  - Totality, whatever SA and table hold: nothing is read or written out of range (d_ends inside its (n >> 5) + 1 words); every
+ *    triple reported is a true hit with exactly that d, because the verification reads the text and not the index; completeness
+ *    and the pinned order need a correct SA (and table).  No input is written.
+ *  - Workgroups own 1024 candidate numbers each, whatever the pieces are, so a piece with millions of occurrences is spread over as
+ *    many workgroups as it fills; one lane per candidate fetches SA[r] and compares 8 bytes per step until a piece before its own
+ *    is exact or d exceeds e; one mark byte per candidate carries the hit and its d into the ordered compaction.
+ *  - Scratch.  The ctx slab holds only the three words of the searches and the block sums of the scans, 8 bytes per 4096 entries
+ *    beyond 4 KiB.  Beside the slab and for the time of the call, with Q = q (e + 1), c candidates and t = ceil(c / 1024): one block
+ *    of the piece offsets, 8 (Q + 1) bytes, the candidate starts, 8 (Q + 1), one word for work[1] and the piece intervals, 2 Q
+ *    entries of the index type; and, once c is known and has passed max_cand, one block of the mark bytes, 1024 t, and the tile
+ *    counts, 8 (t + 1); each part rounded up to 256 bytes.  Where that fails the call returns PSACX_ENOMEM and the outputs are
+ *    untouched.  The count query runs everything but the last kernel.
+ * psacx_kmismatch_*: the host-pointer form.  offsets == NULL means one text (m is ignored); otherwise the m + 1 offsets of the
+ * strings, which must start at 0, end at n and ascend strictly (PSACX_EINVAL).  It stages the arrays, builds the bitmap of the string
+ * ends and the table when k > 0, calls the device form and frees what it allocated on every path.  qid == NULL is the count query,
+ * z > cap returns PSACX_ERANGE with *z valid. */
+int psacx_kmismatch_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint32_t* d_SA,
+                            const uint32_t* d_table, uint32_t k, const uint16_t code[256], const uint8_t* d_pat, const uint64_t* d_poff,
+                            uint64_t q, uint32_t e, uint64_t max_cand, uint64_t* d_qid, uint32_t* d_tpos, uint8_t* d_dist, uint64_t cap,
+                            uint64_t* z, uint64_t* work);
+int psacx_kmismatch_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint64_t* d_SA,
+                            const uint64_t* d_table, uint32_t k, const uint16_t code[256], const uint8_t* d_pat, const uint64_t* d_poff,
+                            uint64_t q, uint32_t e, uint64_t max_cand, uint64_t* d_qid, uint64_t* d_tpos, uint8_t* d_dist, uint64_t cap,
+                            uint64_t* z, uint64_t* work);
+int psacx_kmismatch_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                        const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t e, uint64_t max_cand, uint64_t* qid,
+                        uint32_t* tpos, uint8_t* dist, uint64_t cap, uint64_t* z);
+int psacx_kmismatch_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                        const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t e, uint64_t max_cand, uint64_t* qid,
+                        uint64_t* tpos, uint8_t* dist, uint64_t cap, uint64_t* z);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

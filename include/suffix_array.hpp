@@ -1115,4 +1115,74 @@ mem_lists<index_t> mems(suffix_array<char, index_t, true, false>& sa, simple_dst
     return psacx::mems_of(sa, text, &soff, patterns, min_len, k, max_occ, super);
 }
 
+// Where the patterns occur in the text with at most e substituted bytes (psacx.h: "pattern search with mismatches"): hit i is pattern
+// qid[i] at text position tpos[i] (a position of the strings laid back to back, for a set), inside one string, with dist[i] <= e
+// differing bytes.  Patterns shorter than e + 1 bytes have no hits.  Order: ascending pattern, then the first piece of the pattern
+// that occurs exactly there, then rank in local_SA.  k > 0 puts the k-mer lookup table in front of the piece searches.  One rank
+// only, as locate.
+template <typename index_t>
+struct mismatch_lists {
+    std::vector<uint64_t> qid;
+    std::vector<index_t> tpos;
+    std::vector<uint8_t> dist;
+};
+
+namespace psacx {
+
+template <typename index_t>
+mismatch_lists<index_t> kmismatch_of(suffix_array<char, index_t, true, false>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff,
+                                     const std::vector<std::string>& patterns, unsigned int e, unsigned int k) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, const uint8_t* p, const uint64_t* po,
+                       uint64_t q, uint32_t k, uint32_t e, uint64_t* qi, uint32_t* tp, uint8_t* d, uint64_t cap, uint64_t* z) {
+            return psacx_kmismatch_u32(c, t, n, o, m, s, p, po, q, k, e, 0, qi, tp, d, cap, z);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, const uint8_t* p, const uint64_t* po,
+                       uint64_t q, uint32_t k, uint32_t e, uint64_t* qi, uint64_t* tp, uint8_t* d, uint64_t cap, uint64_t* z) {
+            return psacx_kmismatch_u64(c, t, n, o, m, s, p, po, q, k, e, 0, qi, tp, d, cap, z);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: kmismatch needs a single-rank communicator (the search runs on one GPU)");
+    if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n)
+        throw std::runtime_error("kmismatch: the suffix array holds no SA of this text");
+    std::vector<uint8_t> pat;
+    std::vector<uint64_t> poff(1, 0);
+    for (std::size_t i = 0; i < patterns.size(); ++i) {
+        pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+        poff.push_back((uint64_t)pat.size());
+    }
+    const W* s = reinterpret_cast<const W*>(sa.local_SA.data());
+    const uint64_t* o = soff ? soff->data() : (const uint64_t*)0;
+    const uint64_t m = soff ? (uint64_t)soff->size() - 1 : 0, q = (uint64_t)patterns.size();
+    uint64_t z = 0;
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, pat.data(), poff.data(), q, k, e, (uint64_t*)0, (W*)0, (uint8_t*)0, 0, &z));
+    std::vector<uint64_t> qid(z + 1);
+    std::vector<W> tpos(z + 1);
+    std::vector<uint8_t> dist(z + 1);
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, pat.data(), poff.data(), q, k, e, qid.data(), tpos.data(), dist.data(), z, &z));
+    mismatch_lists<index_t> out;
+    out.qid.assign(qid.begin(), qid.begin() + z);
+    out.tpos.assign(tpos.begin(), tpos.begin() + z);
+    out.dist.assign(dist.begin(), dist.begin() + z);
+    return out;
+}
+
+} // namespace psacx
+
+template <typename index_t, typename Iterator>
+mismatch_lists<index_t> kmismatch(suffix_array<char, index_t, true, false>& sa, Iterator begin, Iterator end, const std::vector<std::string>& patterns,
+                                  unsigned int e, unsigned int k = 0) {
+    return psacx::kmismatch_of(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, patterns, e, k);
+}
+
+template <typename index_t>
+mismatch_lists<index_t> kmismatch(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, const std::vector<std::string>& patterns,
+                                  unsigned int e, unsigned int k = 0) {
+    std::vector<uint8_t> text; std::vector<uint64_t> soff;
+    psacx::flatten_set(ss, text, soff);
+    return psacx::kmismatch_of(sa, text, &soff, patterns, e, k);
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

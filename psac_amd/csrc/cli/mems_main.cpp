@@ -27,12 +27,6 @@ static void usage() {
                  "contained in no other match of their pattern.  --list prints \"pattern offset string position length\" per match.\n";
 }
 
-static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, tab, code, sg, e) : psacx_lookup_table_dev_u32(c, t, n, nullptr, k, tab, code, sg, e);
-}
-static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint64_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u64(c, t, n, ends, k, tab, code, sg, e) : psacx_lookup_table_dev_u64(c, t, n, nullptr, k, tab, code, sg, e);
-}
 static int mems(psacx_ctx* c, uint64_t n, const uint32_t* sa, const uint32_t* lcp, const uint32_t* index, const uint8_t* b, const uint32_t* f,
                 const uint8_t* pat, const uint64_t* poff, uint64_t q, const uint32_t* ml, const uint32_t* mlb, const uint32_t* mub, uint64_t l,
                 uint64_t hi, uint32_t flags, uint64_t* qpos, uint32_t* tpos, uint32_t* len, uint64_t cap, uint64_t* z) {
@@ -89,9 +83,9 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
     if (o.k) {
         uint32_t sigma = 0;
         uint64_t te = 0;
-        must(c, table(c, d_text, n, d_ends, o.k, (IT*)nullptr, code, &sigma, &te));
+        must(c, lookup_table(c, d_text, n, d_ends, o.k, (IT*)nullptr, code, &sigma, &te));
         d_table = (IT*)s.dev(te * sizeof(IT));
-        must(c, table(c, d_text, n, d_ends, o.k, d_table, code, &sigma, &te));
+        must(c, lookup_table(c, d_text, n, d_ends, o.k, d_table, code, &sigma, &te));
     }
     std::cerr << "Index time: " << ms_since(t1) << " ms" << std::endl;
     auto t2 = std::chrono::steady_clock::now();

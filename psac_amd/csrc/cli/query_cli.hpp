@@ -1,6 +1,6 @@
-// Shared by the query command lines (locate, lce, overlaps, lz77, repeats, mems): the error rule, a wall clock, the readers of their
+// Shared by the query command lines (locate, lce, overlaps, lz77, repeats, mems, kmismatch): the error rule, a wall clock, the readers of their
 // inputs, the --index choice, the owner of the ctx and the device memory of a run, and the u32 / u64 overload pairs of the calls that
-// more than one of them makes (construction, index, occurrences, longest match, BWT).  read_file is the one of bench_common.hpp.
+// more than one of them makes (construction, index, occurrences, the table over a text or a set, longest match, BWT).  read_file is the one of bench_common.hpp.
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -81,6 +81,12 @@ inline int occurrences(psacx_ctx* c, const uint64_t* sa, uint64_t n, const uint6
 }
 
 // ends == nullptr: one text
+inline int lookup_table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
+    return ends ? psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, tab, code, sg, e) : psacx_lookup_table_dev_u32(c, t, n, nullptr, k, tab, code, sg, e);
+}
+inline int lookup_table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint64_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
+    return ends ? psacx_lookup_table_gsa_dev_u64(c, t, n, ends, k, tab, code, sg, e) : psacx_lookup_table_dev_u64(c, t, n, nullptr, k, tab, code, sg, e);
+}
 inline int match(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, const uint32_t* tab, uint32_t k, const uint16_t* code,
                  const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t entries, uint32_t* len, uint32_t* lb,
                  uint32_t* ub) {

@@ -116,10 +116,11 @@ static int search_with_slab_words(psacx_ctx* c, const uint64_t* d_poff, uint64_t
     return PSACX_OK;
 }
 
-// d_ends != nullptr: psacx_locate_gsa_dev_* (one pattern per lane whatever PSACX_OPT_LOCATE_SHAPE says)
+// d_ends != nullptr: psacx_locate_gsa_dev_* (one pattern per lane whatever PSACX_OPT_LOCATE_SHAPE says).  Declared in query_calls.hpp:
+// kmismatch.hip searches its pieces by it.
 template <typename T>
 int locate_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_SA, const T* d_table, uint32_t k, const uint16_t* code,
-               const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb, T* d_ub, const uint32_t* d_ends = nullptr) {
+               const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb, T* d_ub, const uint32_t* d_ends) {
     if (!c) return PSACX_EINVAL;
     PSACX_TRY(search_table_valid(d_table, k, code));
     if (q == 0) return PSACX_OK;
@@ -140,6 +141,11 @@ int locate_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_SA, c
         });
     });
 }
+
+template int locate_dev<uint32_t>(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, const uint32_t*, uint32_t, const uint16_t*, const uint8_t*, const uint64_t*,
+                                  uint64_t, uint32_t*, uint32_t*, const uint32_t*);
+template int locate_dev<uint64_t>(psacx_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, const uint16_t*, const uint8_t*, const uint64_t*,
+                                  uint64_t, uint64_t*, uint64_t*, const uint32_t*);
 
 // psacx_match_dev_* / psacx_match_gsa_dev_* (set: the string-set form, which needs d_ends): the checks of locate_dev, the offsets
 // kernel with the rule for out_entries, and one launch of match_kernel.

@@ -1,4 +1,4 @@
-// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, and check.hip and
+// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, and check.hip and
 // ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
 // that moves in one place alone does not compile.
 #pragma once
@@ -18,6 +18,12 @@ int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint
 int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len);
 uint64_t exclusive_scan_slab_bytes(uint64_t len);
 
+// locate.hip: psacx_locate_dev_* itself, and with d_ends psacx_locate_gsa_dev_* (uses the first words of the ctx slab; waits), instantiated
+// there for both widths
+template <typename T>
+int locate_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_SA, const T* d_table, uint32_t k, const uint16_t* code,
+               const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb, T* d_ub, const uint32_t* d_ends = nullptr);
+
 // ansv.hip: all nearest smaller values of an array in HBM into two arrays of n 64-bit entries (pyramid in the ctx slab; waits)
 int ansv_dev_u32(psacx_ctx* c, const uint32_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
 int ansv_dev_u64(psacx_ctx* c, const uint64_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
@@ -32,6 +38,12 @@ template <typename T>
 int mems_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const T* d_LCP, const T* d_index, const uint8_t* d_bwt, const uint32_t* d_first,
              const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, const T* d_mlen, const T* d_mlb, const T* d_mub, uint64_t min_len,
              uint64_t max_occ, uint32_t flags, uint64_t* d_qpos, T* d_tpos, T* d_len, uint64_t cap, uint64_t* z, uint64_t* work);
+
+// kmismatch.hip: psacx_kmismatch_dev_* itself (kernels in kmismatch.hpp; waits), instantiated there for both widths
+template <typename T>
+int kmismatch_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table, uint32_t k,
+                  const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t e, uint64_t max_cand, uint64_t* d_qid,
+                  T* d_tpos, uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
 
 constexpr uint64_t RMQ_MAX_N = 1ull << 48;             // 64^PYR_MAX: the top level of the range-minimum index is one group
 

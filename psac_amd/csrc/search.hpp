@@ -188,9 +188,10 @@ __device__ __forceinline__ void search_count(unsigned long long* __restrict__ co
 }
 
 // poff[0] == 0, poff[i] <= poff[i + 1] for the q + 1 offsets and, where check_total is set (the suffix mode of the longest match),
-// poff[q] == total -- or *bad becomes nonzero
-__global__ __launch_bounds__(256) void search_offsets_kernel(const uint64_t* __restrict__ poff, uint64_t q, bool check_total, uint64_t total,
-                                                             unsigned long long* bad) {
+// poff[q] == total -- or *bad becomes nonzero.  (static: locate.hip launches it; kmismatch.hip includes this header for the word compare
+// and reaches the check through locate_dev)
+static __global__ __launch_bounds__(256) void search_offsets_kernel(const uint64_t* __restrict__ poff, uint64_t q, bool check_total, uint64_t total,
+                                                                    unsigned long long* bad) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool wrong = false;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < q; i += stride) {

@@ -269,6 +269,15 @@ class SuffixArray(object):
         return mems(self._text, self.local_SA, self.local_LCP, patterns, min_len, k=k, offsets=self._text_off, max_occ=max_occ, super=super,
                     ctx=self.ctx)
 
+    def kmismatch(self, patterns, e, k=0, max_cand=0):
+        """(qid, tpos, dist) of the occurrences of the patterns with at most e substituted bytes in the text or string set of the last
+        construct / construct_ss: kmismatch() over its arrays."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("kmismatch needs a single-rank context (the search runs on one GPU)")
+        if getattr(self, "_text", None) is None or self._text.size != self.n or self.local_SA.size != self.n:
+            raise ValueError("kmismatch needs construct or construct_ss first")
+        return kmismatch(self._text, self.local_SA, patterns, e, k=k, offsets=self._text_off, max_cand=max_cand, ctx=self.ctx)
+
     def construct_device(self, d_text, n, d_sa, d_isa, d_lcp=None, fast_resolval=True, k=0, profile=False, d_lc=None):
         """Same with every buffer already resident in HBM (raw device addresses)."""
         args = [self.ctx.handle, C.c_void_p(d_text), int(n), int(k), self._flags(fast_resolval, profile),
@@ -905,6 +914,62 @@ def mems(text, SA, LCP, patterns, min_len, k=0, offsets=None, max_occ=0, super=F
     tpos, ln = (np.zeros(max(1, z.value), sa.dtype) for _ in range(2))
     ctx.check(fn(*(head + [_ptr(qpos), _ptr(tpos), _ptr(ln), z.value, C.byref(z)])))
     return qpos[:z.value], tpos[:z.value], ln[:z.value]
+
+
+def kmismatch_device(ctx, d_text, n, d_ends, d_sa, d_table, k, code, d_pat, d_poff, q, e, max_cand, d_qid, d_tpos, d_dist, cap, index_bits,
+                     work=None):
+    """psacx_kmismatch_dev_*: the occurrences of q patterns with at most e substituted bytes (include/psacx.h: "pattern search with
+    mismatches"), everything resident in HBM.  d_ends=None: one text; otherwise the bitmap of string_ends_device.  d_table / k / code
+    as for locate_device (over a set: the table of lookup_table_gsa_device).  d_qid (uint64) / d_tpos (index type) / d_dist (uint8)
+    receive z entries each in the pinned order; d_qid=None is the count query.  max_cand > 0 refuses a batch with more candidates.
+    work, where given, is a list that receives the two work counters.  Returns z; raises PsacxError -2 where z exceeds cap or the
+    candidates max_cand, with the lists untouched and z in the error's attribute z."""
+    fn = getattr(ctx._lib, "psacx_kmismatch_dev_u%d" % index_bits)
+    cd = None if code is None else np.ascontiguousarray(code, dtype=np.uint16)
+    z = C.c_uint64(0)
+    w = (C.c_uint64 * 2)()
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, opt(d_text), int(n), opt(d_ends), opt(d_sa), opt(d_table), int(k), _ptr(cd) if cd is not None else None, opt(d_pat),
+                     opt(d_poff), int(q), int(e), int(max_cand), opt(d_qid), opt(d_tpos), opt(d_dist), int(cap), C.byref(z),
+                     w if work is not None else None))
+    except PsacxError as err:
+        err.z = z.value
+        raise
+    finally:
+        if work is not None:
+            work[:] = [int(w[0]), int(w[1])]
+    return z.value
+
+
+def kmismatch(text, SA, patterns, e, k=0, offsets=None, max_cand=0, ctx=None):
+    """psacx_kmismatch_*: (qid, tpos, dist) of the occurrences of the patterns in the text with at most e substituted bytes: hit i is
+    pattern qid[i] at text[tpos[i]:tpos[i] + len(pattern)], inside one string, with dist[i] <= e differing bytes.  Patterns shorter
+    than e + 1 bytes have no hits.  Order: ascending pattern, then the first piece of the pattern that occurs exactly there, then
+    suffix-array rank.  k > 0 puts the k-mer lookup table in front of the piece searches; max_cand > 0 refuses (PsacxError -2) a
+    batch whose pieces occur more often than that in all.  offsets: text is a string set and SA its generalized suffix array.  Host
+    arrays; everything is staged."""
+    sa = np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise ValueError("kmismatch: SA must be uint32 or uint64")
+    t = _text_bytes(text)
+    if t.size != sa.size:
+        raise ValueError("SA must have one entry per byte of the text")
+    pat, off = pattern_buffer(patterns)
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    ctx = ctx if ctx is not None else Context(0)
+    ctx._pre()
+    fn = getattr(ctx._lib, "psacx_kmismatch_u%d" % (sa.dtype.itemsize * 8))
+    z = C.c_uint64(0)
+    head = [ctx.handle, _ptr(t), t.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(sa),
+            _ptr(pat) if pat.size else None, _ptr(off), int(off.size - 1), int(k), int(e), int(max_cand)]
+    ctx.check(fn(*(head + [None, None, None, 0, C.byref(z)])))
+    qid = np.zeros(max(1, z.value), np.uint64)
+    tpos = np.zeros(max(1, z.value), sa.dtype)
+    dist = np.zeros(max(1, z.value), np.uint8)
+    ctx.check(fn(*(head + [_ptr(qid), _ptr(tpos), _ptr(dist), z.value, C.byref(z)])))
+    return qid[:z.value], tpos[:z.value], dist[:z.value]
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
