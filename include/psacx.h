@@ -163,7 +163,10 @@ int psacx_trim(psacx_ctx* ctx);
  *                     differences of the times are the times of the stages.  0 = the whole call; larger values are refused
  *   KMISMATCH_STOP    timing option (tools/kmismatch_time.py): 1..2 = psacx_kmismatch_dev_* returns PSACX_OK with z = 0 after the piece searches
  *                     and the scan of their counts (1), after the marks (2), synchronised; work is set as far as it is known; the count query is
- *                     the stage after them.  0 = the whole call; larger values are refused                                                      */
+ *                     the stage after them.  0 = the whole call; larger values are refused
+ *   KEDIT_STOP        timing option (tools/kedit_time.py): 1..3 = psacx_kedit_dev_* returns PSACX_OK with z = 0 after the piece searches and
+ *                     the scan of their counts (1), after the verification and the scan of the raw hits (2), after the sort and the unique
+ *                     (3), synchronised; work is set as far as it is known.  0 = the whole call; larger values are refused                     */
 enum {
     PSACX_OPT_RESET = 0, PSACX_OPT_FORCE_DIET, PSACX_OPT_DIET_CAP, PSACX_OPT_ONE_STAGE, PSACX_OPT_TIES_RADIX, PSACX_OPT_NO_ONE_WORD,
     PSACX_OPT_ONE_WORD_ALWAYS, PSACX_OPT_ONE_WORD_MIN, PSACX_OPT_WIDEN_LAST, PSACX_OPT_NO_DIGIT_BYTES, PSACX_OPT_NO_BUCKET_SORT,
@@ -171,6 +174,7 @@ enum {
     PSACX_OPT_NO_SPREAD_CURSORS, PSACX_OPT_LOCATE_SHAPE, PSACX_OPT_LOCATE_COUNT, PSACX_OPT_GENERIC_REBUCKET,
     PSACX_OPT_PLAIN_SIDE_KERNELS, PSACX_OPT_LSD_BUCKET_PASSES, PSACX_OPT_FIRST_LEAD, PSACX_OPT_LZ_SMALL_TILES,
     PSACX_OPT_GRID_CAP, PSACX_OPT_GROUP_COUNTING_ROUNDS, PSACX_OPT_MEMS_STOP, PSACX_OPT_KMISMATCH_STOP,
+    PSACX_OPT_KEDIT_STOP,
     PSACX_OPT_COUNT
 };
 int psacx_configure(psacx_ctx* ctx, int option, uint64_t value);
@@ -1107,6 +1111,75 @@ int psacx_kmismatch_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const u
 int psacx_kmismatch_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
                         const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t e, uint64_t max_cand, uint64_t* qid,
                         uint64_t* tpos, uint8_t* dist, uint64_t cap, uint64_t* z);
+
+/* pattern search with edits ---------------------------------------------------------------
+ * Where a pattern occurs in the indexed text within edit distance e (unit-cost Levenshtein distance: substitutions, insertions and
+ * deletions), which psacx_kmismatch_* does not answer: one inserted or deleted byte costs it every hit behind it.  The reference
+ * has no counterpart.  One GPU.
+ *
+ * Setting, as for psacx_kmismatch_dev_*.  One text S[0..n), or a string set whose suffix i is S[i..end(i)); for a set, d_ends is the
+ * bitmap of psacx_string_ends_dev.  Patterns are pat / poff.  0 <= e <= 15 (PSACX_EINVAL above).
+ *
+ * For pattern j (m_j bytes) and a start t < n let
+ *     D(j, t) = min over 0 <= L <= end(t) - t of ed(P_j, S[t .. t + L))   and   L(j, t) = the smallest L that attains it.
+ * A hit is a quadruple (j, t, L(j, t), D(j, t)) with D(j, t) <= e.  The match lies inside one string: L never passes end(t).  A
+ * pattern with m_j <= e has no hits (every start would be one) and owns no candidate, as for psacx_kmismatch_*.  Every hit is
+ * reported exactly once, in ascending pattern, then ascending t.  With e = 0 the hits are the occurrences of the pattern, sorted by
+ * position.  An exact occurrence at t brings the neighbouring starts along at distances 1 .. e: PSACX_KEDIT_BEST in flags keeps,
+ * for every pattern, only the hits whose distance is the smallest among that pattern's hits, in the same order.  Unknown flag bits
+ * return PSACX_EINVAL.
+ *
+ * Pieces and candidates are those of psacx_kmismatch_dev_*: pattern j is cut at b_i = floor(i m_j / (e + 1)), the pieces are searched
+ * exactly, and rank r of piece i is a candidate with s = SA[r] and diagonal t0 = s - b_i.  An alignment with at most e edits leaves
+ * one piece unedited (pigeonhole), and that piece lies off its diagonal by at most the number of insertions and deletions before it,
+ * so the starts examined for a candidate are t in [max(start of s's string, t0 - e), min(s, t0 + e)], at most 2e + 1.  D <= e
+ * implies L <= m_j + e, so the text up to min(end(t), t + m_j + e) decides D and L whenever D <= e: two candidates that reach the same
+ * (j, t) agree, and the raw hits (candidate, start) become the hits by a plain unique.
+ *
+ * psacx_kedit_dev_*: d_table / k / code as for psacx_kmismatch_dev_*; any other mix returns PSACX_EINVAL.
+ *  - Output: z quadruples, d_qid (the pattern, uint64), d_tpos = t and d_len = L (index type) and d_dist = D (uint8).
+ *  - d_qid == NULL is the count query; all four lists must be NULL, or none of them (PSACX_EINVAL).
+ *  - z > cap returns PSACX_ERANGE with *z valid and nothing written to the lists.  *z is always set.
+ *  - work may be NULL.  Otherwise work[0] is the number of candidates and work[1] the number of raw hits before the unique.  Both
+ *    are functions of the inputs alone.
+ *  - With max_cand > 0 and work[0] > max_cand the call returns PSACX_ERANGE before anything sized by the candidates is allocated;
+ *    *z = 0 and work[0] is valid.  Memory sized by the raw hits is allocated only once they are counted.
+ *  - poff[0] != 0 or a descending pair returns PSACX_EINVAL, found on the device before any result is written.  q == 0 or n == 0
+ *    gives z = 0.  n beyond the index type returns PSACX_ERANGE, and so does q >= 2^32 with the 32-bit index type (the pattern
+ *    number is a key word of the sort).
+ *  - Totality, whatever SA and table hold: nothing is read or written out of range (d_ends inside its (n >> 5) + 1 words); every
+ *    quadruple reported is a true hit with exactly that L and D, because the verification reads the text and not the index;
+ *    completeness and the order need a correct SA (and table); every hit is reported once regardless.  No input is written.
+ *  - Workgroups own 1024 candidate numbers each, whatever the pieces are.  One lane per candidate fetches SA[r] and runs one
+ *    right-to-left pass of the edit-distance recurrence with a free end over the band of the 4 EB + 1 diagonals around t0, EB >= e
+ *    one of 1, 2, 4, 8, 15 at compile time, so the band is registers; the lane leaves when every cell of its row exceeds e.  The
+ *    result is a mask of the starts with D <= e.  The raw pairs (j, t) are sorted by the rank-pair sort, equal neighbours dropped by
+ *    the ordered compaction, and a forward pass over the distinct pairs alone gives L and D.
+ *  - Scratch.  The ctx slab holds the three words of the searches and the block sums of the scans at its base and, between two of
+ *    the scans, the buffers of the rank-pair sort over the raw hits (the statistics of the context are not touched by it).  Beside the slab and for the time of the call, with
+ *    Q = q (e + 1), c candidates, r raw hits and u distinct hits: the piece offsets and candidate starts, 16 (Q + 1) bytes, and the
+ *    piece intervals, 2 Q entries; once c has passed max_cand, a mask and a count per candidate, 12 c + 8; once r is counted, two
+ *    entries, a mark byte and 8 / 1024 bytes of tile counts per raw hit; with PSACX_KEDIT_BEST 9 bytes, two entries and a mark byte
+ *    per distinct hit and 4 q.  Each part is rounded up to 256 bytes.  Where that fails the call returns PSACX_ENOMEM and the
+ *    outputs are untouched.
+ * psacx_kedit_*: the host-pointer form, as psacx_kmismatch_* is that of psacx_kmismatch_dev_*: offsets == NULL means one text (m is
+ * ignored); it stages the arrays, builds the bitmap and the table when k > 0, calls the device form and frees what it allocated on
+ * every path.  qid == NULL is the count query, z > cap returns PSACX_ERANGE with *z valid. */
+#define PSACX_KEDIT_BEST 1u
+int psacx_kedit_dev_u32(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint32_t* d_SA,
+                        const uint32_t* d_table, uint32_t k, const uint16_t code[256], const uint8_t* d_pat, const uint64_t* d_poff,
+                        uint64_t q, uint32_t e, uint64_t max_cand, uint32_t flags, uint64_t* d_qid, uint32_t* d_tpos, uint32_t* d_len,
+                        uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
+int psacx_kedit_dev_u64(psacx_ctx* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const uint64_t* d_SA,
+                        const uint64_t* d_table, uint32_t k, const uint16_t code[256], const uint8_t* d_pat, const uint64_t* d_poff,
+                        uint64_t q, uint32_t e, uint64_t max_cand, uint32_t flags, uint64_t* d_qid, uint64_t* d_tpos, uint64_t* d_len,
+                        uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
+int psacx_kedit_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                    const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t e, uint64_t max_cand, uint32_t flags,
+                    uint64_t* qid, uint32_t* tpos, uint32_t* len, uint8_t* dist, uint64_t cap, uint64_t* z);
+int psacx_kedit_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                    const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t e, uint64_t max_cand, uint32_t flags,
+                    uint64_t* qid, uint64_t* tpos, uint64_t* len, uint8_t* dist, uint64_t cap, uint64_t* z);
 
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP

@@ -1185,4 +1185,79 @@ mismatch_lists<index_t> kmismatch(suffix_array<char, index_t, true, false>& sa, 
     return psacx::kmismatch_of(sa, text, &soff, patterns, e, k);
 }
 
+// Where the patterns occur in the text within edit distance e (psacx.h: "pattern search with edits"): hit i is pattern qid[i] against
+// the len[i] bytes from text position tpos[i] (a position of the strings laid back to back, for a set), inside one string, at
+// unit-cost Levenshtein distance dist[i] <= e: the smallest over all lengths from that start, and len[i] the shortest length that
+// attains it.  Patterns of at most e bytes have no hits.  Order: ascending pattern, then ascending position.  best: only the hits
+// of the smallest distance of every pattern.  k > 0 puts the k-mer lookup table in front of the piece searches.  One rank only, as
+// kmismatch.
+template <typename index_t>
+struct edit_lists {
+    std::vector<uint64_t> qid;
+    std::vector<index_t> tpos;
+    std::vector<index_t> len;
+    std::vector<uint8_t> dist;
+};
+
+namespace psacx {
+
+template <typename index_t>
+edit_lists<index_t> kedit_of(suffix_array<char, index_t, true, false>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff,
+                             const std::vector<std::string>& patterns, unsigned int e, unsigned int k, bool best) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, const uint8_t* p, const uint64_t* po,
+                       uint64_t q, uint32_t k, uint32_t e, uint32_t f, uint64_t* qi, uint32_t* tp, uint32_t* l, uint8_t* d, uint64_t cap, uint64_t* z) {
+            return psacx_kedit_u32(c, t, n, o, m, s, p, po, q, k, e, 0, f, qi, tp, l, d, cap, z);
+        }
+        static int run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, const uint8_t* p, const uint64_t* po,
+                       uint64_t q, uint32_t k, uint32_t e, uint32_t f, uint64_t* qi, uint64_t* tp, uint64_t* l, uint8_t* d, uint64_t cap, uint64_t* z) {
+            return psacx_kedit_u64(c, t, n, o, m, s, p, po, q, k, e, 0, f, qi, tp, l, d, cap, z);
+        }
+    };
+    if (sa.multi_context()) throw std::runtime_error("psacx: kedit needs a single-rank communicator (the search runs on one GPU)");
+    if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n)
+        throw std::runtime_error("kedit: the suffix array holds no SA of this text");
+    std::vector<uint8_t> pat;
+    std::vector<uint64_t> poff(1, 0);
+    for (std::size_t i = 0; i < patterns.size(); ++i) {
+        pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+        poff.push_back((uint64_t)pat.size());
+    }
+    const W* s = reinterpret_cast<const W*>(sa.local_SA.data());
+    const uint64_t* o = soff ? soff->data() : (const uint64_t*)0;
+    const uint64_t m = soff ? (uint64_t)soff->size() - 1 : 0, q = (uint64_t)patterns.size();
+    const uint32_t f = best ? PSACX_KEDIT_BEST : 0u;
+    uint64_t z = 0;
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, pat.data(), poff.data(), q, k, e, f, (uint64_t*)0, (W*)0, (W*)0, (uint8_t*)0, 0, &z));
+    std::vector<uint64_t> qid(z + 1);
+    std::vector<W> tpos(z + 1), len(z + 1);
+    std::vector<uint8_t> dist(z + 1);
+    check(sa.context(), Call::run(sa.context(), text.data(), sa.n, o, m, s, pat.data(), poff.data(), q, k, e, f, qid.data(), tpos.data(), len.data(), dist.data(), z,
+                                  &z));
+    edit_lists<index_t> out;
+    out.qid.assign(qid.begin(), qid.begin() + z);
+    out.tpos.assign(tpos.begin(), tpos.begin() + z);
+    out.len.assign(len.begin(), len.begin() + z);
+    out.dist.assign(dist.begin(), dist.begin() + z);
+    return out;
+}
+
+} // namespace psacx
+
+template <typename index_t, typename Iterator>
+edit_lists<index_t> kedit(suffix_array<char, index_t, true, false>& sa, Iterator begin, Iterator end, const std::vector<std::string>& patterns,
+                          unsigned int e, unsigned int k = 0, bool best = false) {
+    return psacx::kedit_of(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, patterns, e, k, best);
+}
+
+template <typename index_t>
+edit_lists<index_t> kedit(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, const std::vector<std::string>& patterns,
+                          unsigned int e, unsigned int k = 0, bool best = false) {
+    std::vector<uint8_t> text; std::vector<uint64_t> soff;
+    psacx::flatten_set(ss, text, soff);
+    return psacx::kedit_of(sa, text, &soff, patterns, e, k, best);
+}
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -19,6 +19,7 @@ PSACX_MATCH_SUFFIXES = 1
 PSACX_OVERLAP_WHOLE = 1
 PSACX_REPEATS_RIGHT, PSACX_REPEATS_MAXIMAL, PSACX_REPEATS_SUPERMAXIMAL = 0, 1, 2
 PSACX_MEMS_SUPER = 1
+PSACX_KEDIT_BEST = 1
 
 # psacx_configure options (include/psacx.h); Context.configure(force_diet=1, ...) takes them by name
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
@@ -28,7 +29,7 @@ OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_rad
            "grid_cap": 25}
 # options that pin the form of one kernel for A/B runs and parity tests (the enum of include/psacx.h goes on behind GRID_CAP);
 # Context.configure takes them by name like the ones above
-KERNEL_OPTIONS = {"group_counting_rounds": 26, "mems_stop": 27, "kmismatch_stop": 28}
+KERNEL_OPTIONS = {"group_counting_rounds": 26, "mems_stop": 27, "kmismatch_stop": 28, "kedit_stop": 29}
 MULTI_OPTIONS = {"layout": 1, "slab": 2, "output_slack": 3, "trace": 4, "wire_piece": 5, "pieces": 6, "check_chunks": 7, "global_refine_sort": 8,
                  "one_stage": 9, "two_word": 10, "one_word": 11, "no_slices": 12, "slice_wide": 13, "slice_shape": 14}
 MULTI_FORCE_WIRE, MULTI_NO_RCCL, MULTI_SHM = 1, 2, 4
@@ -64,6 +65,7 @@ EXPORTS = [
     "psacx_bwt_u32", "psacx_bwt_u64", "psacx_repeats_u32", "psacx_repeats_u64",
     "psacx_mems_dev_u32", "psacx_mems_dev_u64", "psacx_mems_u32", "psacx_mems_u64",
     "psacx_kmismatch_dev_u32", "psacx_kmismatch_dev_u64", "psacx_kmismatch_u32", "psacx_kmismatch_u64",
+    "psacx_kedit_dev_u32", "psacx_kedit_dev_u64", "psacx_kedit_u32", "psacx_kedit_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -185,6 +187,9 @@ def load():
         getattr(lib, "psacx_kmismatch_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, u32, u64, vp, vp, vp, u64,
                                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_kmismatch_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, u32, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_kedit_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, u32, u64, u32, vp, vp, vp, vp, u64,
+                                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_kedit_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, u32, u64, u32, vp, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

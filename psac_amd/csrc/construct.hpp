@@ -531,6 +531,45 @@ int prepare_range_min(psacx_ctx* c, Work<T>& w, uint64_t queries, uint64_t n, co
     return PSACX_OK;
 }
 
+// The sort of pair_sort_dev for a caller inside the library that wants the sorted keys alone (kedit.hip: the raw hits): n >= 1 pairs
+// (b1, b2) sorted in place on their low key_bits bits; the payloads the passes carry stay in the slab and no permutation is handed out.
+// Lays its buffers out from the base of the ctx slab, clears its error words and waits.  The statistics and the profiling state of the
+// context are left as they were: psacx_get_stats still shows the last construction and the counters of the last search.
+template <typename T>
+int pair_sort_keys_dev(psacx_ctx* c, T* d_b1, T* d_b2, uint64_t n, uint32_t key_bits) {
+    if (!c || !d_b1 || !d_b2 || n == 0) return PSACX_EINVAL;
+    if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
+    PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
+    auto layout = [&](Arena& a, SortBufs<T>& alt, SortScratch& sc, T*& vtmp) {
+        alt.k1 = a.take<T>(n); alt.k2 = a.take<T>(n); alt.v = a.take<T>(n); vtmp = a.take<T>(n);
+        sc.take(a, n);
+    };
+    SortBufs<T> alt; SortScratch sc; T* vtmp;
+    Arena dry(nullptr);
+    layout(dry, alt, sc, vtmp);
+    PSACX_TRY(ensure_slab(c, dry.off + 4096));
+    Arena ar(c->slab);
+    layout(ar, alt, sc, vtmp);
+    sc.bind_pinned(c);
+    PSACX_HIP(c, hipMemsetAsync(sc.d_err, 0, 64 * sizeof(unsigned), c->stream));
+    const psacx_stats stats = c->stats;
+    const bool profile = c->profile;
+    c->profile = false;
+    SortBufs<T> in{d_b1, d_b2, vtmp}, res;
+    int rc = pair_sort<T>(c, sc, in, alt, n, true, key_bits, key_bits, nullptr, &res, nullptr);
+    c->stats = stats;
+    c->profile = profile;
+    PSACX_TRY(rc);
+    if (res.k1 != d_b1) {
+        PSACX_HIP(c, hipMemcpyAsync(d_b1, res.k1, n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+        PSACX_HIP(c, hipMemcpyAsync(d_b2, res.k2, n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    }
+    PSACX_HIP(c, hipMemcpyAsync(c->pinned, sc.d_err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (*reinterpret_cast<unsigned*>(c->pinned)) return PSACX_EDEVICE;
+    return PSACX_OK;
+}
+
 } // namespace psacx
 
 #include "first_round.hpp"

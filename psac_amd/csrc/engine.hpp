@@ -76,6 +76,7 @@ struct Knobs {
     int locate_shape = 0;        // PSACX_OPT_LOCATE_SHAPE: 2 = eight lanes per pattern in locate_kernel, else one pattern per lane (search.hpp; A/B runs)
     bool locate_count = false;    // PSACX_OPT_LOCATE_COUNT: locate_kernel counts the SA entries and text words it fetches (psacx_stats.locate_fetches)
     unsigned mems_stop = 0;       // PSACX_OPT_MEMS_STOP: psacx_mems_dev_* returns after this stage with z = 0 (tools/mems_time.py times the stages by it)
+    unsigned kedit_stop = 0;      // PSACX_OPT_KEDIT_STOP: psacx_kedit_dev_* returns after this stage with z = 0 (tools/kedit_time.py times the stages by it)
     unsigned kmismatch_stop = 0;  // PSACX_OPT_KMISMATCH_STOP: psacx_kmismatch_dev_* returns after this stage with z = 0 (tools/kmismatch_time.py times the stages by it)
     unsigned grid_cap = 0;        // PSACX_OPT_GRID_CAP: grid_for cuts every grid to at most this many workgroups, not n_cu * per_cu (tests: the second and
                                   // later trips of the grid-stride loops at a few thousand items; 0 = the default bound)

@@ -36,7 +36,8 @@ static_assert(OCC_TILE == (int)SELECT_TILE_MAX, "a tile of candidates is a tile 
 
 // boff[j (e + 1) + i] = poff[j] + floor(i m_j / (e + 1)) for j < q, i <= e, and boff[q (e + 1)] = poff[q]; E1 = e + 1.  The boundaries
 // start at 0 and ascend iff poff does: boff[j E1] = poff[j], and the search that takes them checks that (search_offsets_kernel).
-__global__ __launch_bounds__(256) void kmm_pieces_kernel(const uint64_t* __restrict__ poff, uint64_t q, uint32_t E1, uint64_t* __restrict__ boff) {
+// (static: kmismatch.hip and kedit.hip both launch it)
+static __global__ __launch_bounds__(256) void kmm_pieces_kernel(const uint64_t* __restrict__ poff, uint64_t q, uint32_t E1, uint64_t* __restrict__ boff) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, Q = q * E1;
     for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x <= Q; x += stride) {
         const uint64_t j = x / E1, i = x - j * E1;

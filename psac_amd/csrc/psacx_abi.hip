@@ -137,6 +137,7 @@ int psacx_configure(psacx_ctx* c, int option, uint64_t value) {
     case PSACX_OPT_GRID_CAP: if (value > 65535) return PSACX_EINVAL; k.grid_cap = (unsigned)value; return PSACX_OK;
     case PSACX_OPT_MEMS_STOP: if (value > 3) return PSACX_EINVAL; k.mems_stop = (unsigned)value; return PSACX_OK;
     case PSACX_OPT_KMISMATCH_STOP: if (value > 2) return PSACX_EINVAL; k.kmismatch_stop = (unsigned)value; return PSACX_OK;
+    case PSACX_OPT_KEDIT_STOP: if (value > 3) return PSACX_EINVAL; k.kedit_stop = (unsigned)value; return PSACX_OK;
     case PSACX_OPT_FIRST_LEAD: if (value > 64) return PSACX_EINVAL; k.first_lead = (unsigned)value; return PSACX_OK;
     default: return PSACX_EINVAL;
     }
@@ -162,6 +163,7 @@ int psacx_configure_from_env(psacx_ctx* c) {
     if (const char* e = psacx_debug_env("PSACX_GRID_CAP")) (void)psacx_configure(c, PSACX_OPT_GRID_CAP, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_MEMS_STOP")) (void)psacx_configure(c, PSACX_OPT_MEMS_STOP, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_KMISMATCH_STOP")) (void)psacx_configure(c, PSACX_OPT_KMISMATCH_STOP, strtoull(e, nullptr, 10));
+    if (const char* e = psacx_debug_env("PSACX_KEDIT_STOP")) (void)psacx_configure(c, PSACX_OPT_KEDIT_STOP, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_ONE_WORD_MIN")) (void)psacx_configure(c, PSACX_OPT_ONE_WORD_MIN, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_ISA_UPDATE")) (void)psacx_configure(c, PSACX_OPT_ISA_UPDATE, e[0] == 's' ? 1 : 2);
     if (const char* e = psacx_debug_env("PSACX_LOCATE_SHAPE")) (void)psacx_configure(c, PSACX_OPT_LOCATE_SHAPE, e[0] == 'g' ? 2 : 1);

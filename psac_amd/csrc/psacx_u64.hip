@@ -24,4 +24,7 @@ int construct_gsa_host_u64(psacx_ctx* c, const uint8_t* t, uint64_t n, const uin
 int pair_sort_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t* idx, uint64_t n, uint32_t bits) {
     return pair_sort_dev<uint64_t>(c, b1, b2, idx, n, bits);
 }
+int pair_sort_keys_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits) {
+    return pair_sort_keys_dev<uint64_t>(c, b1, b2, n, bits);
+}
 }

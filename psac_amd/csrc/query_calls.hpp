@@ -1,4 +1,4 @@
-// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, and check.hip and
+// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, kedit.hip, and check.hip and
 // ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
 // that moves in one place alone does not compile.
 #pragma once
@@ -44,6 +44,18 @@ template <typename T>
 int kmismatch_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table, uint32_t k,
                   const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t e, uint64_t max_cand, uint64_t* d_qid,
                   T* d_tpos, uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
+
+// kedit.hip: psacx_kedit_dev_* itself (kernels in kedit.hpp; waits), instantiated there for both widths
+template <typename T>
+int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table, uint32_t k,
+              const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t e, uint64_t max_cand, uint32_t flags,
+              uint64_t* d_qid, T* d_tpos, T* d_len, uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
+
+// psacx_u32.hip / psacx_u64.hip: pair_sort_keys_dev of construct.hpp: n >= 1 pairs (b1, b2) sorted in place on their low `bits` bits by the
+// rank-pair sort, whose buffers it lays out from the base of the ctx slab; waits; leaves the statistics and the profiling state of the
+// context as they were (kedit.hip sorts its raw hits by it)
+int pair_sort_keys_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits);
+int pair_sort_keys_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits);
 
 constexpr uint64_t RMQ_MAX_N = 1ull << 48;             // 64^PYR_MAX: the top level of the range-minimum index is one group
 

@@ -278,6 +278,15 @@ class SuffixArray(object):
             raise ValueError("kmismatch needs construct or construct_ss first")
         return kmismatch(self._text, self.local_SA, patterns, e, k=k, offsets=self._text_off, max_cand=max_cand, ctx=self.ctx)
 
+    def kedit(self, patterns, e, k=0, max_cand=0, best=False):
+        """(qid, tpos, len, dist) of the places where the patterns occur within edit distance e in the text (or string set) of the last
+        construct / construct_ss: kedit() over its arrays."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("kedit needs a single-rank context (the search runs on one GPU)")
+        if getattr(self, "_text", None) is None or self._text.size != self.n or self.local_SA.size != self.n:
+            raise ValueError("kedit needs construct or construct_ss first")
+        return kedit(self._text, self.local_SA, patterns, e, k=k, offsets=self._text_off, max_cand=max_cand, best=best, ctx=self.ctx)
+
     def construct_device(self, d_text, n, d_sa, d_isa, d_lcp=None, fast_resolval=True, k=0, profile=False, d_lc=None):
         """Same with every buffer already resident in HBM (raw device addresses)."""
         args = [self.ctx.handle, C.c_void_p(d_text), int(n), int(k), self._flags(fast_resolval, profile),
@@ -970,6 +979,64 @@ def kmismatch(text, SA, patterns, e, k=0, offsets=None, max_cand=0, ctx=None):
     dist = np.zeros(max(1, z.value), np.uint8)
     ctx.check(fn(*(head + [_ptr(qid), _ptr(tpos), _ptr(dist), z.value, C.byref(z)])))
     return qid[:z.value], tpos[:z.value], dist[:z.value]
+
+
+KEDIT_BEST = 1
+
+
+def kedit_device(ctx, d_text, n, d_ends, d_sa, d_table, k, code, d_pat, d_poff, q, e, max_cand, flags, d_qid, d_tpos, d_len, d_dist, cap,
+                 index_bits, work=None):
+    """psacx_kedit_dev_*: where q patterns occur within edit distance e (include/psacx.h: "pattern search with edits"), everything
+    resident in HBM.  The arguments of kmismatch_device, and flags (KEDIT_BEST: only the hits of the smallest distance of every
+    pattern) and d_len (index type) beside d_qid (uint64) / d_tpos (index type) / d_dist (uint8), which receive z entries each in
+    ascending (pattern, position); d_qid=None is the count query.  work, where given, is a list that receives the candidates and
+    the raw hits.  Returns z; raises PsacxError -2 where z exceeds cap or the candidates max_cand, with the lists untouched and z in
+    the error's attribute z."""
+    fn = getattr(ctx._lib, "psacx_kedit_dev_u%d" % index_bits)
+    cd = None if code is None else np.ascontiguousarray(code, dtype=np.uint16)
+    z = C.c_uint64(0)
+    w = (C.c_uint64 * 2)()
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, opt(d_text), int(n), opt(d_ends), opt(d_sa), opt(d_table), int(k), _ptr(cd) if cd is not None else None, opt(d_pat),
+                     opt(d_poff), int(q), int(e), int(max_cand), int(flags), opt(d_qid), opt(d_tpos), opt(d_len), opt(d_dist), int(cap), C.byref(z),
+                     w if work is not None else None))
+    except PsacxError as err:
+        err.z = z.value
+        raise
+    finally:
+        if work is not None:
+            work[:] = [int(w[0]), int(w[1])]
+    return z.value
+
+
+def kedit(text, SA, patterns, e, k=0, offsets=None, max_cand=0, best=False, ctx=None):
+    """psacx_kedit_*: (qid, tpos, len, dist) of the places where the patterns occur in the text within edit distance e: hit i is
+    pattern qid[i] against text[tpos[i]:tpos[i] + len[i]], inside one string, at unit-cost Levenshtein distance dist[i] <= e, the
+    smallest over all lengths from that start, and len[i] the shortest length that attains it.  Patterns of at most e bytes have no
+    hits.  Order: ascending pattern, then ascending position.  best: only the hits of the smallest distance of every pattern.  k,
+    max_cand, offsets as for kmismatch.  Host arrays; everything is staged."""
+    sa = np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise ValueError("kedit: SA must be uint32 or uint64")
+    t = _text_bytes(text)
+    if t.size != sa.size:
+        raise ValueError("SA must have one entry per byte of the text")
+    pat, off = pattern_buffer(patterns)
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    ctx = ctx if ctx is not None else Context(0)
+    ctx._pre()
+    fn = getattr(ctx._lib, "psacx_kedit_u%d" % (sa.dtype.itemsize * 8))
+    z = C.c_uint64(0)
+    head = [ctx.handle, _ptr(t), t.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(sa),
+            _ptr(pat) if pat.size else None, _ptr(off), int(off.size - 1), int(k), int(e), int(max_cand), KEDIT_BEST if best else 0]
+    ctx.check(fn(*(head + [None, None, None, None, 0, C.byref(z)])))
+    qid = np.zeros(max(1, z.value), np.uint64)
+    tpos, ln = (np.zeros(max(1, z.value), sa.dtype) for _ in range(2))
+    dist = np.zeros(max(1, z.value), np.uint8)
+    ctx.check(fn(*(head + [_ptr(qid), _ptr(tpos), _ptr(ln), _ptr(dist), z.value, C.byref(z)])))
+    return qid[:z.value], tpos[:z.value], ln[:z.value], dist[:z.value]
 
 
 def check_device(ctx, d_text, n, d_sa, d_isa, d_lcp, index_bits):
