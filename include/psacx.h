@@ -1181,6 +1181,94 @@ int psacx_kedit_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint6
                     const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t k, uint32_t e, uint64_t max_cand, uint32_t flags,
                     uint64_t* qid, uint64_t* tpos, uint64_t* len, uint8_t* dist, uint64_t cap, uint64_t* z);
 
+/* document counts and document lists ------------------------------------------------------
+ * In how many strings of a set, and in which, the suffixes of an interval [lb, ub) of the generalized suffix array start: the
+ * document frequency of a pattern, a repeat or a seed, and each string once however often it repeats the pattern, which
+ * psacx_occurrences_dev_* (one entry per occurrence) does not give.  The reference has no counterpart.  One GPU.
+ *
+ * Setting, as for psacx_repeats_dev_* over a set: m strings back to back, offsets[0..m], SA and LCP as psacx_construct_gsa_dev_*
+ * leaves them: suffixes end with their strings, equal suffixes stand in text order, LCP is cut at string ends.  L[r] = LCP[r] with
+ * L[0] read as 0.  doc(r) is the string that holds SA[r]: the largest s < m with offsets[s] <= SA[r], searched and never trusted, as
+ * in psacx_occurrences_dev_*.  "All ones" is the largest value of the index type.
+ *
+ * Index, two arrays:
+ *     prev[r], n entries: the largest p < r with doc(p) == doc(r), or all ones if there is none;
+ *     dup[i], n + 1 entries: dup[i] = sum over x < i of h[x], where h[x] counts the ranks r with p = prev[r] not all ones whose FIRST
+ *     minimum of L[p+1 .. r] (both ends included) lies at x: the arg rule of psacx_rmq_dev_*.  h[0] = 0 and dup[n] = n - (the number of
+ *     strings that own a rank).
+ *
+ * Counts.  For an LCP-interval the number of distinct strings is
+ *     docs(lb, ub) = (ub - lb) - (dup[ub] - dup[lb + 1]).
+ * An LCP-interval has lb < ub <= n and, with l = min L[lb+1 .. ub-1] (all ones if ub == lb + 1), (lb == 0 or L[lb] < l) and (ub == n or
+ * L[ub] < l).  This is Hui's counting of duplicate pairs at their lowest common ancestor: a pair (p, r) with both ends inside has its
+ * minimum strictly inside (lb, ub), a pair with one end outside crosses a boundary value that is strictly smaller, so its first minimum
+ * lies at or outside a boundary.  Every singleton and [0, n) are LCP-intervals, and so is every non-empty interval that psacx_locate_gsa_* /
+ * psacx_match_gsa_* / psacx_repeats_* / psacx_mems_* return.  The intervals of psacx_overlaps_dev_* are NOT: their right boundary
+ * equals the inner value, and the formula may count a pair that crosses it.  Callers with such intervals, or with arbitrary ones, use
+ * the list call, whose total is exact for any interval.
+ *
+ * Lists.  For ANY interval [lb, ub) with lb <= ub <= n, the ranks r in it with prev[r] < lb or prev[r] all ones are the first
+ * occurrence of each string in the interval; the list holds them in ascending r.
+ *
+ * psacx_doc_index_dev_*: d_index is the index of psacx_rmq_index_dev_* over d_LCP.
+ *  - d_prev or d_dup may be NULL (d_LCP and d_index are not read without d_dup); both NULL returns PSACX_EINVAL.
+ *  - n == 0 is PSACX_OK; otherwise m == 0 or m > n returns PSACX_EINVAL.  n beyond the index type or beyond 2^48 returns PSACX_ERANGE.
+ *  - No input is written.  An SA entry >= n counts for the last string (the search of the offsets decides, nothing is read out of range).
+ *  - Stages: one key (doc(r), r) per rank, one lane each, by a binary search over the offsets; the rank-pair sort on the bits of m - 1 of
+ *    the first word (stable; the ranks of a string stay in order); prev scattered from neighbours of equal doc, where an adjacent pair
+ *    (p = r - 1) adds to h[r] without a search; every other pair runs the range-minimum search over L[p+1 .. r] on sixteen lanes and one
+ *    lane adds to h[x] by an atomic; the exclusive scan of h in d_dup.
+ *  - Scratch.  The ctx slab holds the buffers of the rank-pair sort and then the block sums of the scan.  Beside the slab and for the
+ *    time of the call: the two key words, 2 n entries.  Where that fails the call returns PSACX_ENOMEM and the outputs are untouched.
+ *  - After psacx_profile(ctx, 1) the call leaves the times of its stages in psacx_stats: ms_kmer the keys, ms_sort_scatter the sort,
+ *    ms_rebucket prev and the pairs, ms_finalize the scan (tools/doc_time.py).
+ * psacx_doc_count_dev_*: one interval per lane, two fetches.  docs_j = 0 unless lb_j < ub_j <= n; otherwise
+ *     docs_j = (ub - lb) - min(sat(dup[ub] - dup[lb+1]), ub - lb - 1),   sat = the difference, or 0 if it is negative.
+ *  - Totality: whatever dup holds, 1 <= docs_j <= ub - lb, and nothing is read outside its n + 1 entries.
+ *  - Nothing is allocated.  q == 0 is PSACX_OK.
+ * psacx_doc_list_dev_*: d_start receives q + 1 exclusive prefix sums (64 bits) of the list lengths, start[q] = *total;
+ * sid[start_j + t] = doc(r_t) and pos[start_j + t] = SA[r_t] for the t-th listed rank of interval j.
+ *  - d_sid == NULL (then d_pos must be NULL, PSACX_EINVAL otherwise) is the size query.  d_pos may be NULL on its own.
+ *  - *total > cap returns PSACX_ERANGE with start and *total valid and nothing written to the lists.  *total is always set.
+ *  - Intervals that are not lb_j <= ub_j <= n count 0.
+ *  - Candidates are the ranks of all intervals.  With max_cand > 0 and more candidates the call returns PSACX_ERANGE before anything sized
+ *    by them is allocated, with *total = 0 and start untouched (the convention of psacx_kmismatch_dev_*).
+ *  - Workgroups own 1024 candidates each, whatever the intervals are: one prev fetch and one mark byte per candidate, then the ordered
+ *    compaction; the listed ranks fetch SA and search the offsets.
+ *  - Totality: a prev entry that is garbage only changes which ranks are listed.  SA entries >= n give sid = m, as in
+ *    psacx_occurrences_dev_*.  Nothing is read or written out of range; no input is written.
+ *  - Scratch.  The ctx slab holds the block sums of the scans.  Beside the slab and for the time of the call: 8 (q + 1) bytes of candidate
+ *    starts and, once the candidates have passed max_cand, per tile of 1024 candidates 1024 mark bytes, 8 bytes of tile counts and 64 of
+ *    run counts.  Where that fails the call returns PSACX_ENOMEM and the outputs are untouched.
+ * psacx_doc_count_* / psacx_doc_list_*: the host-pointer forms.  They stage the arrays, check the offsets as psacx_repeats_* does
+ * (PSACX_EINVAL), build the range-minimum index (the count) and the doc index, call the device forms and free what they allocated on
+ * every path.  psacx_doc_list_* needs no LCP; sid == NULL is the size query, *total > cap returns PSACX_ERANGE with start and *total
+ * valid. */
+int psacx_doc_index_dev_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint32_t* d_SA, const uint32_t* d_LCP,
+                            const uint32_t* d_index, uint32_t* d_prev, uint32_t* d_dup);
+int psacx_doc_index_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint64_t* d_SA, const uint64_t* d_LCP,
+                            const uint64_t* d_index, uint64_t* d_prev, uint64_t* d_dup);
+int psacx_doc_count_dev_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* d_dup, const uint32_t* d_lb, const uint32_t* d_ub, uint64_t q,
+                            uint32_t* d_docs);
+int psacx_doc_count_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_dup, const uint64_t* d_lb, const uint64_t* d_ub, uint64_t q,
+                            uint64_t* d_docs);
+int psacx_doc_list_dev_u32(psacx_ctx* ctx, const uint32_t* d_SA, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint32_t* d_prev,
+                           const uint32_t* d_lb, const uint32_t* d_ub, uint64_t q, uint64_t max_cand, uint64_t* d_start, uint32_t* d_sid,
+                           uint32_t* d_pos, uint64_t cap, uint64_t* total);
+int psacx_doc_list_dev_u64(psacx_ctx* ctx, const uint64_t* d_SA, uint64_t n, const uint64_t* d_offsets, uint64_t m, const uint64_t* d_prev,
+                           const uint64_t* d_lb, const uint64_t* d_ub, uint64_t q, uint64_t max_cand, uint64_t* d_start, uint64_t* d_sid,
+                           uint64_t* d_pos, uint64_t cap, uint64_t* total);
+int psacx_doc_count_u32(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA, const uint32_t* LCP,
+                        const uint32_t* lb, const uint32_t* ub, uint64_t q, uint32_t* docs);
+int psacx_doc_count_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA, const uint64_t* LCP,
+                        const uint64_t* lb, const uint64_t* ub, uint64_t q, uint64_t* docs);
+int psacx_doc_list_u32(psacx_ctx* ctx, const uint32_t* SA, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* lb,
+                       const uint32_t* ub, uint64_t q, uint64_t max_cand, uint64_t* start, uint32_t* sid, uint32_t* pos, uint64_t cap,
+                       uint64_t* total);
+int psacx_doc_list_u64(psacx_ctx* ctx, const uint64_t* SA, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* lb,
+                       const uint64_t* ub, uint64_t q, uint64_t max_cand, uint64_t* start, uint64_t* sid, uint64_t* pos, uint64_t cap,
+                       uint64_t* total);
+
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP
  * (suffix_array.hpp:183-194, :217-228; src/psac.cpp:85-93 block-decomposes the input).  A psacx_multi stands for the

@@ -1041,6 +1041,99 @@ repeat_intervals<index_t> repeats(suffix_array<char, index_t, true, false>& sa, 
     return psacx::repeats_of(sa, text, &soff, kind, min_len, min_occ, max_occ);
 }
 
+// Document counts and document lists (psacx.h: "document counts and document lists") over the set of construct_ss.
+// doc_count: the number of distinct strings among the suffixes local_SA[lb[j] .. ub[j]), for LCP-intervals: what locate / match /
+// repeats / mems return, singletons and [0, n); the intervals of overlaps() are none, doc_list serves them.  Needs the LCP.
+// doc_list: each of those strings once, for ANY interval: sid[start[j] .. start[j + 1]) in the order of their first rank, pos where
+// that suffix starts.  max_cand > 0 refuses a batch whose intervals hold more ranks.
+// common_repeats: repeats(), then doc_count(), then a filter on the host (the repeats are not filtered on the device): the repeats
+// that occur in at least min_docs strings, and in at most max_docs where max_docs > 0, with their counts.  The longest substring
+// common to at least min_docs strings is the row of the largest len.  One rank only, as repeats.
+template <typename index_t>
+struct doc_lists {
+    std::vector<std::size_t> start;
+    std::vector<index_t> sid, pos;
+};
+
+template <typename index_t>
+struct common_repeat_intervals {
+    std::vector<index_t> lb, ub, len, docs;
+};
+
+namespace psacx {
+
+template <typename index_t, bool LCP>
+std::vector<uint64_t> doc_offsets(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, const char* what, std::size_t lbs, std::size_t ubs) {
+    static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+    if (sa.multi_context()) throw std::runtime_error(std::string("psacx: ") + what + " needs a single-rank communicator (the index is built on one GPU)");
+    if (sa.n == 0 || ss.sum_sizes != sa.n || sa.local_SA.size() != sa.n) throw std::runtime_error(std::string(what) + ": string set does not match the suffix array");
+    if (lbs != ubs) throw std::runtime_error(std::string(what) + ": lb and ub differ in length");
+    std::vector<uint64_t> soff(1, 0);
+    for (std::size_t s = 0; s < ss.sizes.size(); ++s) soff.push_back(soff.back() + ss.sizes[s]);
+    return soff;
+}
+
+} // namespace psacx
+
+template <typename index_t>
+std::vector<index_t> doc_count(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, const std::vector<index_t>& lb,
+                               const std::vector<index_t>& ub) {
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* s, const uint32_t* l, const uint32_t* a, const uint32_t* b,
+                       uint64_t q, uint32_t* d) { return psacx_doc_count_u32(c, n, o, m, s, l, a, b, q, d); }
+        static int run(psacx_ctx* c, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* s, const uint64_t* l, const uint64_t* a, const uint64_t* b,
+                       uint64_t q, uint64_t* d) { return psacx_doc_count_u64(c, n, o, m, s, l, a, b, q, d); }
+    };
+    const std::vector<uint64_t> soff = psacx::doc_offsets(sa, ss, "doc_count", lb.size(), ub.size());
+    if (sa.local_LCP.size() != sa.n) throw std::runtime_error("doc_count: the suffix array holds no LCP");
+    std::vector<index_t> docs(lb.size(), 0);
+    psacx::check(sa.context(), Call::run(sa.context(), sa.n, soff.data(), (uint64_t)soff.size() - 1, reinterpret_cast<const W*>(sa.local_SA.data()),
+                                         reinterpret_cast<const W*>(sa.local_LCP.data()), reinterpret_cast<const W*>(lb.data()),
+                                         reinterpret_cast<const W*>(ub.data()), (uint64_t)lb.size(), reinterpret_cast<W*>(docs.data())));
+    return docs;
+}
+
+template <typename index_t, bool LCP>
+doc_lists<index_t> doc_list(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, const std::vector<index_t>& lb,
+                            const std::vector<index_t>& ub, std::size_t max_cand = 0) {
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    struct Call {
+        static int run(psacx_ctx* c, const uint32_t* s, uint64_t n, const uint64_t* o, uint64_t m, const uint32_t* a, const uint32_t* b, uint64_t q, uint64_t mc,
+                       uint64_t* st, uint32_t* sid, uint32_t* pos, uint64_t cap, uint64_t* tot) { return psacx_doc_list_u32(c, s, n, o, m, a, b, q, mc, st, sid, pos, cap, tot); }
+        static int run(psacx_ctx* c, const uint64_t* s, uint64_t n, const uint64_t* o, uint64_t m, const uint64_t* a, const uint64_t* b, uint64_t q, uint64_t mc,
+                       uint64_t* st, uint64_t* sid, uint64_t* pos, uint64_t cap, uint64_t* tot) { return psacx_doc_list_u64(c, s, n, o, m, a, b, q, mc, st, sid, pos, cap, tot); }
+    };
+    const std::vector<uint64_t> soff = psacx::doc_offsets(sa, ss, "doc_list", lb.size(), ub.size());
+    const W* s = reinterpret_cast<const W*>(sa.local_SA.data());
+    const W* a = reinterpret_cast<const W*>(lb.data());
+    const W* b = reinterpret_cast<const W*>(ub.data());
+    const uint64_t q = (uint64_t)lb.size(), m = (uint64_t)soff.size() - 1;
+    std::vector<uint64_t> start(q + 1, 0);
+    uint64_t total = 0;
+    psacx::check(sa.context(), Call::run(sa.context(), s, sa.n, soff.data(), m, a, b, q, (uint64_t)max_cand, start.data(), (W*)0, (W*)0, 0, &total));
+    std::vector<W> sid(total + 1), pos(total + 1);
+    psacx::check(sa.context(), Call::run(sa.context(), s, sa.n, soff.data(), m, a, b, q, (uint64_t)max_cand, start.data(), sid.data(), pos.data(), total, &total));
+    doc_lists<index_t> out;
+    out.start.assign(start.begin(), start.end());
+    out.sid.assign(sid.begin(), sid.begin() + total);
+    out.pos.assign(pos.begin(), pos.begin() + total);
+    return out;
+}
+
+template <typename index_t>
+common_repeat_intervals<index_t> common_repeats(suffix_array<char, index_t, true, false>& sa, simple_dstringset& ss, std::size_t min_docs,
+                                                std::size_t max_docs = 0, repeat_kind kind = repeats_right, std::size_t min_len = 1) {
+    const repeat_intervals<index_t> r = repeats(sa, ss, kind, min_len);
+    const std::vector<index_t> docs = doc_count(sa, ss, r.lb, r.ub);
+    common_repeat_intervals<index_t> out;
+    for (std::size_t k = 0; k < docs.size(); ++k) {
+        if ((std::size_t)docs[k] < min_docs || (max_docs && (std::size_t)docs[k] > max_docs)) continue;
+        out.lb.push_back(r.lb[k]); out.ub.push_back(r.ub[k]); out.len.push_back(r.len[k]); out.docs.push_back(docs[k]);
+    }
+    return out;
+}
+
 // The maximal exact matches of a batch of patterns against the text (psacx.h: "maximal exact matches"): match i is
 // pattern bytes [qpos[i], qpos[i] + len[i]) -- qpos counts the bytes of the patterns laid back to back -- equal to the text at
 // tpos[i], at least min_len long and extensible on neither side inside its pattern and its string.  max_occ > 0 keeps matches whose

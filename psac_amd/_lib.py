@@ -66,6 +66,8 @@ EXPORTS = [
     "psacx_mems_dev_u32", "psacx_mems_dev_u64", "psacx_mems_u32", "psacx_mems_u64",
     "psacx_kmismatch_dev_u32", "psacx_kmismatch_dev_u64", "psacx_kmismatch_u32", "psacx_kmismatch_u64",
     "psacx_kedit_dev_u32", "psacx_kedit_dev_u64", "psacx_kedit_u32", "psacx_kedit_u64",
+    "psacx_doc_index_dev_u32", "psacx_doc_index_dev_u64", "psacx_doc_count_dev_u32", "psacx_doc_count_dev_u64",
+    "psacx_doc_list_dev_u32", "psacx_doc_list_dev_u64", "psacx_doc_count_u32", "psacx_doc_count_u64", "psacx_doc_list_u32", "psacx_doc_list_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -190,6 +192,11 @@ def load():
         getattr(lib, "psacx_kedit_dev_" + suf).argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, u32, u64, u32, vp, vp, vp, vp, u64,
                                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_kedit_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, u32, u64, u32, vp, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_doc_index_dev_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, vp]
+        getattr(lib, "psacx_doc_count_dev_" + suf).argtypes = [vp, u64, vp, vp, vp, u64, vp]
+        getattr(lib, "psacx_doc_list_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_doc_count_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, u64, vp]
+        getattr(lib, "psacx_doc_list_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

@@ -1,7 +1,7 @@
 // locate -- batched pattern search on the MI355X engine, the counterpart of the reference's
 // `desa-main -f <text> -c -q <patterns>` (the reference's src/desa_main.cpp):
 //   locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--longest [--suffixes] [--max-len L]]
-//          [--index 32|64|auto] [--device N] [-o file]
+//          [--docs] [--doc-list [LIMIT]] [--index 32|64|auto] [--device N] [-o file]
 // The text goes up once; the suffix array is constructed in HBM (psacx_construct_dev_*), the lookup table for -k K > 0 is built
 // there (psacx_lookup_table_dev_*) and the patterns are located there (psacx_locate_dev_*).  Prints "lb ub" per pattern -- the
 // occurrences are SA[lb..ub) -- to stdout or the file of -o, and "SA time:" / "Table time:" / "Locate time: <ms> ms" to stderr.
@@ -15,6 +15,9 @@
 // "len lb ub" per query -- the prefix of len bytes occurs at SA[lb..ub) -- and "Match time:" instead of "Locate time:".
 // --suffixes makes every byte of every pattern a query (the rest of its pattern from there on: the matching statistics, one line
 // per byte in the order of the patterns), --max-len L cuts every query to L bytes.  --occ lists the occurrences of the prefixes.
+// --set --docs prints, behind "lb ub", in how many strings the pattern occurs (the LCP comes with the construction, then
+// psacx_rmq_index_dev_*, psacx_doc_index_dev_*, psacx_doc_count_dev_*; "Docs time:").  --set --doc-list [LIMIT] prints behind that each such
+// string once, as string:offset-in-string of its first suffix in SA order, at most LIMIT per pattern if LIMIT > 0 (psacx_doc_list_dev_*).
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -29,11 +32,12 @@ using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: locate -f <text> -q <patterns, one per line> [-k K] [--set] [--occ [LIMIT]] [--longest [--suffixes] [--max-len L]]\n"
-                 "              [--index 32|64|auto] [--device N] [-o <file>]\n"
+                 "              [--docs] [--doc-list [LIMIT]] [--index 32|64|auto] [--device N] [-o <file>]\n"
                  "Locates every pattern in the suffix array of the text (MI355X engine): prints lb ub per pattern, the occurrences are SA[lb..ub).\n"
                  "--set: the strings of -f are its lines, and no pattern matches across two of them.  --occ [LIMIT]: print the occurrences too.\n"
                  "--longest: print len lb ub of the longest prefix of every pattern that occurs; --suffixes: of every suffix of every pattern;\n"
-                 "--max-len L: of at most L bytes of each.\n";
+                 "--max-len L: of at most L bytes of each.\n"
+                 "--set --docs: print in how many strings each pattern occurs; --set --doc-list [LIMIT]: print each of them once.\n";
 }
 
 static int table(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* sa, uint32_t k, uint32_t* tab, uint16_t* code, uint32_t* sg, uint64_t* e) {
@@ -63,7 +67,8 @@ static int locate(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* en
 // longest: --longest, with mflags (PSACX_MATCH_SUFFIXES for --suffixes) and max_len
 template <typename IT>
 static int run(const std::string& text, const std::vector<uint64_t>& soff, const std::string& pat, const std::vector<uint64_t>& poff, uint32_t k,
-               bool occ, uint64_t limit, bool longest, uint32_t mflags, uint64_t max_len, int device, std::ostream& out) {
+               bool occ, uint64_t limit, bool longest, uint32_t mflags, uint64_t max_len, bool docs, bool doc_lists, uint64_t dlimit, int device,
+               std::ostream& out) {
     const uint64_t n = text.size(), q = poff.size() - 1, m = soff.empty() ? 0 : soff.size() - 1;
     const uint64_t e = longest && (mflags & PSACX_MATCH_SUFFIXES) ? poff[q] : q;      // results: one per pattern, or one per byte of the patterns
     const bool set = m != 0;
@@ -76,7 +81,8 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
     uint64_t* d_soff = set ? (uint64_t*)s.dev((m + 1) * sizeof(uint64_t)) : nullptr;
     must(c, psacx_copy_h2d(c, d_text, text.data(), n));
     if (set) must(c, psacx_copy_h2d(c, d_soff, soff.data(), (m + 1) * sizeof(uint64_t)));
-    must(c, construct(c, d_text, n, d_soff, m, 0, d_sa, d_isa, (IT*)nullptr));
+    IT* d_lcp = docs ? (IT*)s.dev(n * sizeof(IT)) : nullptr;
+    must(c, construct(c, d_text, n, d_soff, m, docs ? PSACX_LCP : 0, d_sa, d_isa, d_lcp));
     std::cerr << "SA time: " << ms_since(t0) << " ms" << std::endl;
     uint32_t* d_ends = nullptr;
     if (set) {
@@ -100,8 +106,8 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
         std::cerr << "Table time: " << ms_since(t1) << " ms" << std::endl;
         std::cerr << "Table entries: " << entries << std::endl;
     }
-    std::vector<IT> len(longest ? e : 0), lb(e), ub(e), pos, sid;
-    std::vector<uint64_t> start(e + 1, 0);
+    std::vector<IT> len(longest ? e : 0), lb(e), ub(e), pos, sid, ndocs(docs ? e : 0), dsid, dpos;
+    std::vector<uint64_t> start(e + 1, 0), dstart(e + 1, 0);
     if (q) {
         uint8_t* d_pat = (uint8_t*)s.dev(pat.size() + 1);
         uint64_t* d_poff = (uint64_t*)s.dev((q + 1) * sizeof(uint64_t));
@@ -136,10 +142,45 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
             if (total) must(c, psacx_copy_d2h(c, pos.data(), d_pos, total * sizeof(IT)));
             if (set) { sid.resize(total); if (total) must(c, psacx_copy_d2h(c, sid.data(), d_sid, total * sizeof(IT))); }
         }
+        if (docs || doc_lists) {
+            auto t4 = std::chrono::steady_clock::now();
+            // one build of the doc index: dup for the counts, prev for the lists, whichever are asked for
+            IT* d_index = nullptr;
+            if (docs) { uint64_t entries = 0; d_index = rmq_index_of<IT>(s, d_lcp, n, &entries); }
+            IT* d_dup = docs ? (IT*)s.dev((n + 1) * sizeof(IT)) : nullptr;
+            IT* d_prev = doc_lists ? (IT*)s.dev(n * sizeof(IT)) : nullptr;
+            must(c, doc_index(c, n, d_soff, m, d_sa, d_lcp, d_index, d_prev, d_dup));
+            if (docs) {
+                IT* d_docs = (IT*)s.dev(e * sizeof(IT) + 1);
+                must(c, doc_count(c, n, d_dup, d_lb, d_ub, e, d_docs));
+                if (e) must(c, psacx_copy_d2h(c, ndocs.data(), d_docs, e * sizeof(IT)));
+            }
+            if (doc_lists) {
+                uint64_t* d_dstart = (uint64_t*)s.dev((e + 1) * sizeof(uint64_t));
+                uint64_t total = 0;
+                must(c, doc_list(c, d_sa, n, d_soff, m, d_prev, d_lb, d_ub, e, 0, d_dstart, (IT*)nullptr, (IT*)nullptr, 0, &total));
+                IT* d_dsid = (IT*)s.dev(total * sizeof(IT) + 1);
+                IT* d_dpos = (IT*)s.dev(total * sizeof(IT) + 1);
+                must(c, doc_list(c, d_sa, n, d_soff, m, d_prev, d_lb, d_ub, e, 0, d_dstart, d_dsid, d_dpos, total, &total));
+                dsid.resize(total); dpos.resize(total);
+                must(c, psacx_copy_d2h(c, dstart.data(), d_dstart, (e + 1) * sizeof(uint64_t)));
+                if (total) must(c, psacx_copy_d2h(c, dsid.data(), d_dsid, total * sizeof(IT)));
+                if (total) must(c, psacx_copy_d2h(c, dpos.data(), d_dpos, total * sizeof(IT)));
+            }
+            std::cerr << "Docs time: " << ms_since(t4) << " ms" << std::endl;
+        }
     }
     for (uint64_t i = 0; i < e; ++i) {
         if (longest) out << (uint64_t)len[i] << ' ';
         out << (uint64_t)lb[i] << ' ' << (uint64_t)ub[i];
+        if (docs) out << ' ' << (uint64_t)ndocs[i];
+        if (doc_lists) {
+            const uint64_t upto = dlimit && dstart[i] + dlimit < dstart[i + 1] ? dstart[i] + dlimit : dstart[i + 1];
+            for (uint64_t t = dstart[i]; t < upto; ++t) {
+                const std::size_t sd = (std::size_t)dsid[t];
+                out << ' ' << (uint64_t)dsid[t] << ':' << (uint64_t)dpos[t] - (sd < soff.size() ? soff[sd] : 0);
+            }
+        }
         if (occ)
             for (uint64_t t = start[i]; t < start[i + 1]; ++t) {
                 out << ' ';
@@ -154,8 +195,8 @@ int main(int argc, char** argv) {
     std::string file, queries, outfile, index = "auto";
     int device = 0;
     long k = 0;
-    bool set = false, occ = false, longest = false, suffixes = false;
-    unsigned long long limit = 0, max_len = 0;
+    bool set = false, occ = false, longest = false, suffixes = false, docs = false, doc_lists = false;
+    unsigned long long limit = 0, max_len = 0, dlimit = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* name) -> const char* {
@@ -176,10 +217,16 @@ int main(int argc, char** argv) {
             occ = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') limit = strtoull(argv[++i], nullptr, 10);
         }
+        else if (a == "--docs") docs = true;
+        else if (a == "--doc-list") {
+            doc_lists = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dlimit = strtoull(argv[++i], nullptr, 10);
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { std::cerr << "error: unknown argument " << a << std::endl; usage(); return EXIT_FAILURE; }
     }
     if (file.empty() || queries.empty() || k < 0 || !index_known(index)) { usage(); return EXIT_FAILURE; }
+    if ((docs || doc_lists) && !set) { std::cerr << "error: --docs and --doc-list belong to --set" << std::endl; usage(); return EXIT_FAILURE; }
     if (!longest && (suffixes || max_len)) { std::cerr << "error: --suffixes and --max-len belong to --longest" << std::endl; usage(); return EXIT_FAILURE; }
     std::string text, lines;
     if (!read_file(file, text)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
@@ -205,8 +252,8 @@ int main(int argc, char** argv) {
             if (!f) { std::cerr << "error: cannot write " << outfile << std::endl; return EXIT_FAILURE; }
         }
         std::ostream& out = outfile.empty() ? std::cout : f;
-        const int rc = narrow ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out)
-                             : run<uint64_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, device, out);
+        const int rc = narrow ? run<uint32_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, docs, doc_lists, dlimit, device, out)
+                             : run<uint64_t>(text, soff, pat, poff, (uint32_t)k, occ, limit, longest, suffixes ? PSACX_MATCH_SUFFIXES : 0u, max_len, docs, doc_lists, dlimit, device, out);
         out.flush();
         if (!out) { std::cerr << "error: cannot write the results" << std::endl; return EXIT_FAILURE; }
         return rc;

@@ -1,6 +1,6 @@
 // Shared by the query command lines (locate, lce, overlaps, lz77, repeats, mems, kmismatch): the error rule, a wall clock, the readers of their
 // inputs, the --index choice, the owner of the ctx and the device memory of a run, and the u32 / u64 overload pairs of the calls that
-// more than one of them makes (construction, index, occurrences, the table over a text or a set, longest match, BWT).  read_file is the one of bench_common.hpp.
+// more than one of them makes (construction, index, occurrences, the table over a text or a set, longest match, BWT, document counts and lists).  read_file is the one of bench_common.hpp.
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -113,6 +113,37 @@ inline IT* rmq_index_of(Session& s, const IT* d_values, uint64_t n, uint64_t* en
     IT* d_index = (IT*)s.dev(*entries * sizeof(IT));
     must(s.c, rmq_index(s.c, d_values, n, d_index, entries));
     return d_index;
+}
+
+inline int doc_index(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* sa, const uint32_t* lcp, const uint32_t* index, uint32_t* prev,
+                     uint32_t* dup) { return psacx_doc_index_dev_u32(c, n, off, m, sa, lcp, index, prev, dup); }
+inline int doc_index(psacx_ctx* c, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* sa, const uint64_t* lcp, const uint64_t* index, uint64_t* prev,
+                     uint64_t* dup) { return psacx_doc_index_dev_u64(c, n, off, m, sa, lcp, index, prev, dup); }
+inline int doc_count(psacx_ctx* c, uint64_t n, const uint32_t* dup, const uint32_t* lb, const uint32_t* ub, uint64_t q, uint32_t* docs) {
+    return psacx_doc_count_dev_u32(c, n, dup, lb, ub, q, docs);
+}
+inline int doc_count(psacx_ctx* c, uint64_t n, const uint64_t* dup, const uint64_t* lb, const uint64_t* ub, uint64_t q, uint64_t* docs) {
+    return psacx_doc_count_dev_u64(c, n, dup, lb, ub, q, docs);
+}
+inline int doc_list(psacx_ctx* c, const uint32_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint32_t* prev, const uint32_t* lb, const uint32_t* ub,
+                    uint64_t q, uint64_t max_cand, uint64_t* start, uint32_t* sid, uint32_t* pos, uint64_t cap, uint64_t* total) {
+    return psacx_doc_list_dev_u32(c, sa, n, off, m, prev, lb, ub, q, max_cand, start, sid, pos, cap, total);
+}
+inline int doc_list(psacx_ctx* c, const uint64_t* sa, uint64_t n, const uint64_t* off, uint64_t m, const uint64_t* prev, const uint64_t* lb, const uint64_t* ub,
+                    uint64_t q, uint64_t max_cand, uint64_t* start, uint64_t* sid, uint64_t* pos, uint64_t cap, uint64_t* total) {
+    return psacx_doc_list_dev_u64(c, sa, n, off, m, prev, lb, ub, q, max_cand, start, sid, pos, cap, total);
+}
+
+// the doc counts of q intervals in HBM, from LCP and its index: dup in memory of the session, then one launch; docs comes back
+template <typename IT>
+inline void doc_counts_of(Session& s, uint64_t n, const uint64_t* d_soff, uint64_t m, const IT* d_sa, const IT* d_lcp, const IT* d_index, const IT* d_lb,
+                          const IT* d_ub, uint64_t q, std::vector<IT>& docs) {
+    IT* d_dup = (IT*)s.dev((n + 1) * sizeof(IT));
+    IT* d_docs = (IT*)s.dev(q * sizeof(IT) + 1);
+    must(s.c, doc_index(s.c, n, d_soff, m, d_sa, d_lcp, d_index, (IT*)nullptr, d_dup));
+    must(s.c, doc_count(s.c, n, d_dup, d_lb, d_ub, q, d_docs));
+    docs.assign(q, 0);
+    if (q) must(s.c, psacx_copy_d2h(s.c, docs.data(), d_docs, q * sizeof(IT)));
 }
 
 } // namespace query_cli

@@ -1,12 +1,16 @@
 // repeats -- the right-maximal, maximal or supermaximal repeats of a text or a set of strings, and its BWT, on the MI355X engine:
 //   repeats -f <text> [--set] [--index 32|64|auto] [--kind right|maximal|super] [-l MINLEN] [--min-occ K] [--max-occ K]
-//           [--list [LIMIT]] [--bwt OUT] [--device N]
+//           [--list [LIMIT]] [--bwt OUT] [--min-docs D [--max-docs D]] [--device N]
 // The text goes up once; with --set its lines are the strings of a set (laid back to back, as gsac reads them).  SA and LCP are
 // constructed in HBM (psacx_construct_dev_* / psacx_construct_gsa_dev_* with PSACX_LCP), the range-minimum index of LCP and the BWT
 // are built beside them (psacx_rmq_index_dev_*, psacx_bwt_dev_*), and one call enumerates the repeats (psacx_repeats_dev_*).  Prints
 // "z: <repeats>" to stdout and "SA time:" / "Index time:" / "BWT time:" / "Repeats time: <ms> ms" to stderr.  --list prints one line
 // "lb ub len first-occurrence" per repeat (at most LIMIT of them), --bwt writes the n bytes of the BWT to OUT and prints
 // "primary: <rank>".
+// --set --min-docs D [--max-docs D] keeps the repeats that occur in at least D (and at most --max-docs) strings of the set
+// (psacx_doc_index_dev_*, psacx_doc_count_dev_*, "Docs time:"; the filter runs on the host): z counts those, --list prints them with a fifth
+// column, the number of strings, and a last line "longest: lb ub len pos docs" names the longest repeat kept (the first of them in the
+// order of the list; "longest: none" if none is kept).
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -21,10 +25,12 @@ using namespace query_cli;
 
 static void usage() {
     std::cerr << "USAGE: repeats -f <text> [--set] [--index 32|64|auto] [--kind right|maximal|super] [-l MINLEN] [--min-occ K] [--max-occ K]\n"
-                 "               [--list [LIMIT]] [--bwt OUT] [--device N]\n"
+                 "               [--list [LIMIT]] [--bwt OUT] [--min-docs D [--max-docs D]] [--device N]\n"
                  "Prints the number z of repeats of the kind (default maximal) that are at least MINLEN long and occur between\n"
                  "--min-occ and --max-occ times (MI355X engine).  --set reads one string per line.  --list prints \"lb ub len pos\" per\n"
-                 "repeat: it is the len bytes at pos and occurs at SA[lb .. ub).  --bwt writes the SA-aligned BWT and prints the primary.\n";
+                 "repeat: it is the len bytes at pos and occurs at SA[lb .. ub).  --bwt writes the SA-aligned BWT and prints the primary.\n"
+                 "--set --min-docs D [--max-docs D]: only the repeats that occur in D or more (and at most --max-docs) strings, with that\n"
+                 "number as a fifth column, and a line \"longest: lb ub len pos docs\" for the longest of them.\n";
 }
 
 static int repeats(psacx_ctx* c, uint64_t n, const uint32_t* lcp, const uint32_t* index, const uint8_t* b, const uint32_t* f, uint32_t kind, uint64_t l,
@@ -38,7 +44,7 @@ static int repeats(psacx_ctx* c, uint64_t n, const uint64_t* lcp, const uint64_t
 
 struct Options {
     uint32_t kind;
-    uint64_t min_len, min_occ, max_occ, limit;
+    uint64_t min_len, min_occ, max_occ, limit, min_docs, max_docs;
     bool list;
     std::string bwt_out;
     int device;
@@ -81,12 +87,22 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
     uint64_t z = 0;
     must(c, repeats(c, n, d_lcp, d_index, d_bwt, d_first, o.kind, o.min_len, o.min_occ, o.max_occ, (IT*)nullptr, (IT*)nullptr, (IT*)nullptr, 0, &z));
     IT *d_lb = nullptr, *d_ub = nullptr, *d_len = nullptr;
-    if (o.list) {
+    const bool by_docs = o.min_docs != 0;
+    if (o.list || by_docs) {
         d_lb = (IT*)s.dev(z * sizeof(IT)); d_ub = (IT*)s.dev(z * sizeof(IT)); d_len = (IT*)s.dev(z * sizeof(IT));
         must(c, repeats(c, n, d_lcp, d_index, d_bwt, d_first, o.kind, o.min_len, o.min_occ, o.max_occ, d_lb, d_ub, d_len, z, &z));
     }
     std::cerr << "Repeats time: " << ms_since(t3) << " ms" << std::endl;
-    std::cout << "z: " << z << '\n';
+    std::vector<IT> docs;
+    std::vector<uint64_t> kept;                            // with --min-docs: the repeats that pass, in the order of the list
+    if (by_docs) {
+        auto t4 = std::chrono::steady_clock::now();
+        doc_counts_of<IT>(s, n, d_soff, m, d_sa, d_lcp, d_index, d_lb, d_ub, z, docs);
+        std::cerr << "Docs time: " << ms_since(t4) << " ms" << std::endl;
+        for (uint64_t k = 0; k < z; ++k)
+            if ((uint64_t)docs[k] >= o.min_docs && (o.max_docs == 0 || (uint64_t)docs[k] <= o.max_docs)) kept.push_back(k);
+    }
+    std::cout << "z: " << (by_docs ? (uint64_t)kept.size() : z) << '\n';
     if (!o.bwt_out.empty()) {
         std::string b(n, '\0');
         must(c, psacx_copy_d2h(c, &b[0], d_bwt, n));
@@ -96,26 +112,38 @@ static int run(const std::string& text, const std::vector<uint64_t>& soff, const
         if (!f) throw std::runtime_error("cannot write " + o.bwt_out);
         std::cout << "primary: " << primary << '\n';
     }
-    if (o.list && z) {
+    if ((o.list || by_docs) && z) {
         std::vector<IT> lb(z), ub(z), len(z), sa(n);
         must(c, psacx_copy_d2h(c, lb.data(), d_lb, z * sizeof(IT)));
         must(c, psacx_copy_d2h(c, ub.data(), d_ub, z * sizeof(IT)));
         must(c, psacx_copy_d2h(c, len.data(), d_len, z * sizeof(IT)));
         must(c, psacx_copy_d2h(c, sa.data(), d_sa, n * sizeof(IT)));
-        const uint64_t shown = o.limit && o.limit < z ? o.limit : z;
-        for (uint64_t k = 0; k < shown; ++k) {
+        auto line = [&](uint64_t k) {
             uint64_t pos = (uint64_t)sa[lb[k]];                 // the first occurrence in the text
             for (uint64_t r = (uint64_t)lb[k]; r < (uint64_t)ub[k]; ++r) if ((uint64_t)sa[r] < pos) pos = (uint64_t)sa[r];
-            std::cout << (uint64_t)lb[k] << ' ' << (uint64_t)ub[k] << ' ' << (uint64_t)len[k] << ' ' << pos << '\n';
+            std::cout << (uint64_t)lb[k] << ' ' << (uint64_t)ub[k] << ' ' << (uint64_t)len[k] << ' ' << pos;
+            if (by_docs) std::cout << ' ' << (uint64_t)docs[k];
+            std::cout << '\n';
+        };
+        const uint64_t have = by_docs ? (uint64_t)kept.size() : z;
+        const uint64_t shown = o.limit && o.limit < have ? o.limit : have;
+        if (o.list)
+            for (uint64_t k = 0; k < shown; ++k) line(by_docs ? kept[k] : k);
+        if (by_docs && !kept.empty()) {
+            uint64_t best = kept[0];
+            for (std::size_t i = 1; i < kept.size(); ++i) if ((uint64_t)len[kept[i]] > (uint64_t)len[best]) best = kept[i];
+            std::cout << "longest: ";
+            line(best);
         }
     }
+    if (by_docs && kept.empty()) std::cout << "longest: none\n";
     return 0;
 }
 
 int main(int argc, char** argv) {
     std::string file, index = "auto", kind = "maximal";
     Options o;
-    o.kind = PSACX_REPEATS_MAXIMAL; o.min_len = 1; o.min_occ = 2; o.max_occ = 0; o.limit = 0; o.list = false; o.device = 0;
+    o.kind = PSACX_REPEATS_MAXIMAL; o.min_len = 1; o.min_occ = 2; o.max_occ = 0; o.limit = 0; o.list = false; o.device = 0; o.min_docs = o.max_docs = 0;
     bool set = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -136,6 +164,8 @@ int main(int argc, char** argv) {
         else if (a == "--max-occ") o.max_occ = count("--max-occ");
         else if (a == "--list") { o.list = true; if (i + 1 < argc && number(argv[i + 1])) o.limit = strtoull(argv[++i], nullptr, 10); }
         else if (a == "--bwt") o.bwt_out = need("--bwt");
+        else if (a == "--min-docs") o.min_docs = count("--min-docs");
+        else if (a == "--max-docs") o.max_docs = count("--max-docs");
         else if (a == "--device") o.device = atoi(need("--device"));
         else if (a == "--index") index = need("--index");
         else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -146,6 +176,7 @@ int main(int argc, char** argv) {
     else if (kind == "super" || kind == "supermaximal") o.kind = PSACX_REPEATS_SUPERMAXIMAL;
     else { usage(); return EXIT_FAILURE; }
     if (file.empty() || !index_known(index)) { usage(); return EXIT_FAILURE; }
+    if ((o.min_docs || o.max_docs) && (!set || !o.min_docs)) { std::cerr << "error: --min-docs belongs to --set, --max-docs to --min-docs" << std::endl; usage(); return EXIT_FAILURE; }
     std::string raw, text;
     if (!read_file(file, raw)) { std::cerr << "error: cannot open " << file << std::endl; return EXIT_FAILURE; }
     std::vector<uint64_t> soff;

@@ -535,8 +535,10 @@ int prepare_range_min(psacx_ctx* c, Work<T>& w, uint64_t queries, uint64_t n, co
 // (b1, b2) sorted in place on their low key_bits bits; the payloads the passes carry stay in the slab and no permutation is handed out.
 // Lays its buffers out from the base of the ctx slab, clears its error words and waits.  The statistics and the profiling state of the
 // context are left as they were: psacx_get_stats still shows the last construction and the counters of the last search.
+// key_bits2: the key bits of the second word; 0 orders the pairs by their first word alone and keeps equal ones in the order they came
+// in (docs.hip: the second word is the rank, which ascends already).
 template <typename T>
-int pair_sort_keys_dev(psacx_ctx* c, T* d_b1, T* d_b2, uint64_t n, uint32_t key_bits) {
+int pair_sort_keys_dev(psacx_ctx* c, T* d_b1, T* d_b2, uint64_t n, uint32_t key_bits, uint32_t key_bits2) {
     if (!c || !d_b1 || !d_b2 || n == 0) return PSACX_EINVAL;
     if (sizeof(T) == 4 && n > 0xFFFFFFFEull) return PSACX_ERANGE;
     PSACX_TRY(ensure_pinned(c, PINNED_SORT_BYTES + 4096));
@@ -556,7 +558,7 @@ int pair_sort_keys_dev(psacx_ctx* c, T* d_b1, T* d_b2, uint64_t n, uint32_t key_
     const bool profile = c->profile;
     c->profile = false;
     SortBufs<T> in{d_b1, d_b2, vtmp}, res;
-    int rc = pair_sort<T>(c, sc, in, alt, n, true, key_bits, key_bits, nullptr, &res, nullptr);
+    int rc = pair_sort<T>(c, sc, in, alt, n, true, key_bits, key_bits2, nullptr, &res, nullptr);
     c->stats = stats;
     c->profile = profile;
     PSACX_TRY(rc);

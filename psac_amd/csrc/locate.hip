@@ -269,6 +269,7 @@ int occurrences_dev(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_o
 
 // the scan for callers outside this file (query_calls.hpp)
 int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len) { return exclusive_scan_dev<uint64_t>(c, d_a, len); }
+int exclusive_scan_u32_dev(psacx_ctx* c, uint32_t* d_a, uint64_t len) { return exclusive_scan_dev<uint32_t>(c, d_a, len); }
 uint64_t exclusive_scan_slab_bytes(uint64_t len) {
     return (len + 256 * LOCATE_SCAN_ITEMS - 1) / (256 * LOCATE_SCAN_ITEMS) * sizeof(unsigned long long) + 4096;
 }

@@ -34,6 +34,31 @@ __device__ __forceinline__ uint64_t occ_last_le(P a, uint64_t cnt, uint64_t o) {
     return lo;
 }
 
+// The walk of a workgroup of 256 threads over the slots [o0, o1) of its tile, for kernels that number slots through start[0 .. q], the
+// scan of q counts that ends with the number of slots (o1 at most that): f(o, x, first) once for every slot o, by one thread, where x
+// is the interval that holds o and first = start[x].  One search in start[] per stretch of OCC_CHUNK intervals, one LDS search per slot
+// (the comment of occ_expand_kernel below has the reasons).  s_start: OCC_CHUNK + 1 words of LDS.  Starts that do not ascend end the walk.
+template <typename F>
+__device__ __forceinline__ void occ_tile_walk(const uint64_t* __restrict__ start, uint64_t q, uint64_t o0, uint64_t o1, uint64_t* s_start, F f) {
+    uint64_t open = o0;                                                     // the first slot not visited yet (the same in every thread)
+    while (open < o1) {
+        const uint64_t j0 = occ_last_le(start, q + 1, open);                // (start[q] > open, so j0 < q and interval j0 holds `open`)
+        if (j0 >= q) break;
+        const uint64_t cnt = q - j0 < OCC_CHUNK ? q - j0 : OCC_CHUNK;
+        __syncthreads();
+        for (uint64_t i = threadIdx.x; i <= cnt; i += blockDim.x) s_start[i] = start[j0 + i];
+        __syncthreads();
+        const uint64_t upto = s_start[cnt] < o1 ? s_start[cnt] : o1;
+        if (upto <= open) break;
+        for (uint64_t o = o0 + threadIdx.x; o < upto; o += blockDim.x) {
+            if (o < open) continue;
+            const uint64_t i = occ_last_le(s_start, cnt, o);
+            f(o, j0 + i, s_start[i]);
+        }
+        open = upto;
+    }
+}
+
 // pos[start_j + t] = SA[lb_j + t] for t < c_j, and sid[] = the string holding it (m for a pos >= n) where sid != nullptr.
 // A workgroup owns the output slots [o0, o1) of its tile, whatever the counts are: it finds the pattern that holds its first
 // open slot by one binary search in start[] (the last j with start[j] <= slot: runs of empty intervals before it are skipped),

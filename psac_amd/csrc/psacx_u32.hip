@@ -25,6 +25,9 @@ int pair_sort_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint32_t* idx, u
     return pair_sort_dev<uint32_t>(c, b1, b2, idx, n, bits);
 }
 int pair_sort_keys_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits) {
-    return pair_sort_keys_dev<uint32_t>(c, b1, b2, n, bits);
+    return pair_sort_keys_dev<uint32_t>(c, b1, b2, n, bits, bits);
+}
+int pair_sort_first_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits) {
+    return pair_sort_keys_dev<uint32_t>(c, b1, b2, n, bits, 0);
 }
 }

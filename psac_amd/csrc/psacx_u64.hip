@@ -25,6 +25,9 @@ int pair_sort_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t* idx, u
     return pair_sort_dev<uint64_t>(c, b1, b2, idx, n, bits);
 }
 int pair_sort_keys_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits) {
-    return pair_sort_keys_dev<uint64_t>(c, b1, b2, n, bits);
+    return pair_sort_keys_dev<uint64_t>(c, b1, b2, n, bits, bits);
+}
+int pair_sort_first_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits) {
+    return pair_sort_keys_dev<uint64_t>(c, b1, b2, n, bits, 0);
 }
 }

@@ -1,4 +1,4 @@
-// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, kedit.hip, and check.hip and
+// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, kedit.hip, docs.hip, and check.hip and
 // ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
 // that moves in one place alone does not compile.
 #pragma once
@@ -16,6 +16,7 @@ int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint
 // a caller that keeps scratch of its own in the slab leaves the first exclusive_scan_slab_bytes(len) bytes to the scan and sizes the
 // slab before it places anything
 int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len);
+int exclusive_scan_u32_dev(psacx_ctx* c, uint32_t* d_a, uint64_t len);           // (32-bit entries whose sum stays below 2^32: docs.hip)
 uint64_t exclusive_scan_slab_bytes(uint64_t len);
 
 // locate.hip: psacx_locate_dev_* itself, and with d_ends psacx_locate_gsa_dev_* (uses the first words of the ctx slab; waits), instantiated
@@ -56,6 +57,10 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
 // context as they were (kedit.hip sorts its raw hits by it)
 int pair_sort_keys_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits);
 int pair_sort_keys_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits);
+// the same sort on the low `bits` bits of the first word alone: pairs of equal first words stay in the order they came in (docs.hip sorts
+// the ranks by their string by it)
+int pair_sort_first_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits);
+int pair_sort_first_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits);
 
 constexpr uint64_t RMQ_MAX_N = 1ull << 48;             // 64^PYR_MAX: the top level of the range-minimum index is one group
 

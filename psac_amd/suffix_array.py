@@ -259,6 +259,35 @@ class SuffixArray(object):
             raise ValueError("repeats needs construct or construct_ss with lcp=True first")
         return repeats(self._text, self.local_SA, self.local_LCP, kind, min_len, min_occ, max_occ, offsets=self._text_off, ctx=self.ctx)
 
+    def _doc_ready(self, what, need_lcp):
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("%s needs a single-rank context (the index is built on one GPU)" % what)
+        if getattr(self, "string_offsets", None) is None or self.local_SA.size != self.n or (need_lcp and (not self.lcp or self.local_LCP.size != self.n)):
+            raise ValueError("%s needs construct_ss%s first" % (what, " with lcp=True" if need_lcp else ""))
+
+    def doc_count(self, lb, ub):
+        """The number of distinct strings in each LCP-interval [lb[j], ub[j]) of the string set of the last construct_ss (which needs
+        lcp=True): doc_count() over its arrays."""
+        self._doc_ready("doc_count", True)
+        return doc_count(self.local_SA, self.local_LCP, self.string_offsets, lb, ub, ctx=self.ctx)
+
+    def doc_list(self, lb, ub, max_cand=0):
+        """(start, sid, pos): each string of the intervals [lb[j], ub[j]) once, over the string set of the last construct_ss:
+        doc_list() over its arrays."""
+        self._doc_ready("doc_list", False)
+        return doc_list(self.local_SA, self.string_offsets, lb, ub, max_cand=max_cand, ctx=self.ctx)
+
+    def common_repeats(self, min_docs, max_docs=0, kind="right", min_len=1):
+        """(lb, ub, length, docs) of the repeats of the string set of the last construct_ss (which needs lcp=True) that occur in at
+        least min_docs strings (and in at most max_docs where max_docs > 0): repeats(), then doc_count(), then a filter.  The filter
+        runs on the host in numpy; the repeats are not filtered on the device.  The longest substring common to at least min_docs
+        strings is the row at the argmax of length."""
+        self._doc_ready("common_repeats", True)
+        lb, ub, ln = self.repeats(kind, min_len=min_len)
+        docs = self.doc_count(lb, ub)
+        keep = (docs >= min_docs) & ((docs <= max_docs) if max_docs else True)
+        return lb[keep], ub[keep], ln[keep], docs[keep]
+
     def mems(self, patterns, min_len, k=0, max_occ=0, super=False):
         """(qpos, tpos, len) of the maximal exact matches of the patterns against the text or string set of the last construct /
         construct_ss (which needs lcp=True): mems() over its arrays."""
@@ -869,6 +898,87 @@ def repeats(text, SA, LCP, kind="maximal", min_len=1, min_occ=2, max_occ=0, offs
     lb, ub, ln = (np.zeros(max(1, z.value), sa.dtype) for _ in range(3))
     ctx.check(fn(*(head + [_ptr(lb), _ptr(ub), _ptr(ln), z.value, C.byref(z)])))
     return lb[:z.value], ub[:z.value], ln[:z.value]
+
+
+def doc_index_device(ctx, n, d_off, m, d_sa, d_lcp, d_index, d_prev, d_dup, index_bits):
+    """psacx_doc_index_dev_*: the document index of a string set resident in HBM (include/psacx.h: "document counts and document
+    lists"): d_prev receives n entries, d_dup n + 1; either may be None (d_lcp and d_index, the index of rmq_index_device over it, are
+    read for d_dup alone)."""
+    fn = getattr(ctx._lib, "psacx_doc_index_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, int(n), opt(d_off), int(m), opt(d_sa), opt(d_lcp), opt(d_index), opt(d_prev), opt(d_dup)))
+
+
+def doc_count_device(ctx, n, d_dup, d_lb, d_ub, q, d_docs, index_bits):
+    """psacx_doc_count_dev_*: d_docs[j] = the number of distinct strings in the LCP-interval [lb_j, ub_j), from d_dup of
+    doc_index_device; 0 unless lb_j < ub_j <= n."""
+    fn = getattr(ctx._lib, "psacx_doc_count_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, int(n), opt(d_dup), opt(d_lb), opt(d_ub), int(q), opt(d_docs)))
+
+
+def doc_list_device(ctx, d_sa, n, d_off, m, d_prev, d_lb, d_ub, q, max_cand, d_start, d_sid, d_pos, cap, index_bits):
+    """psacx_doc_list_dev_*: each string of the intervals [lb_j, ub_j) once, from d_prev of doc_index_device.  d_start receives q + 1
+    uint64 (the exclusive prefix sums of the list lengths), d_sid the strings and d_pos (may be None) the positions of their first
+    ranks, in rank order.  d_sid=None is the size query.  Returns the total; raises PsacxError -2 where it exceeds cap (d_start valid,
+    lists untouched, the total in the error's attribute total) or where the intervals hold more than max_cand > 0 ranks."""
+    fn = getattr(ctx._lib, "psacx_doc_list_dev_u%d" % index_bits)
+    total = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, opt(d_sa), int(n), opt(d_off), int(m), opt(d_prev), opt(d_lb), opt(d_ub), int(q), int(max_cand), opt(d_start),
+                     opt(d_sid), opt(d_pos), int(cap), C.byref(total)))
+    except PsacxError as e:
+        e.total = total.value
+        raise
+    return total.value
+
+
+def _doc_args(SA, offsets, lb, ub, what):
+    sa = np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("%s needs SA as uint32 or uint64" % what)
+    so = np.ascontiguousarray(offsets, dtype=np.uint64)
+    a, b = np.ascontiguousarray(lb, dtype=sa.dtype), np.ascontiguousarray(ub, dtype=sa.dtype)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("lb and ub must be two flat arrays of one length")
+    return sa, so, a, b
+
+
+def doc_count(SA, LCP, offsets, lb, ub, ctx=None):
+    """psacx_doc_count_*: the number of distinct strings of the set (offsets: its m + 1 string offsets) among the suffixes
+    SA[lb[j]:ub[j]], for LCP-intervals: what locate / match / repeats / mems return, singletons and [0, n).  The intervals of overlaps()
+    are none: use doc_list for them.  Host arrays; everything is staged for the call."""
+    sa, so, a, b = _doc_args(SA, offsets, lb, ub, "doc_count")
+    lcp = np.ascontiguousarray(LCP)
+    if lcp.dtype != sa.dtype or lcp.size != sa.size:
+        raise ValueError("SA and LCP must have the same type and length")
+    out = np.zeros(a.size, sa.dtype)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_doc_count_u%d" % (sa.dtype.itemsize * 8))
+    ctx._pre()
+    ctx.check(fn(ctx.handle, sa.size, _ptr(so), so.size - 1, _ptr(sa), _ptr(lcp), _ptr(a), _ptr(b), a.size, _ptr(out)))
+    return out
+
+
+def doc_list(SA, offsets, lb, ub, max_cand=0, ctx=None):
+    """psacx_doc_list_*: (start, sid, pos) -- the strings that own a suffix in SA[lb[j]:ub[j]] are sid[start[j]:start[j + 1]], each once,
+    in the order of their first rank, and pos is where that suffix starts.  Any interval.  max_cand > 0 refuses (PsacxError -2) a batch
+    whose intervals hold more ranks.  Host arrays; everything is staged for the call."""
+    sa, so, a, b = _doc_args(SA, offsets, lb, ub, "doc_list")
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_doc_list_u%d" % (sa.dtype.itemsize * 8))
+    start = np.zeros(a.size + 1, np.uint64)
+    total = C.c_uint64(0)
+    head = [ctx.handle, _ptr(sa), sa.size, _ptr(so), so.size - 1, _ptr(a), _ptr(b), a.size, int(max_cand), _ptr(start)]
+    ctx._pre()
+    ctx.check(fn(*(head + [None, None, 0, C.byref(total)])))
+    sid, pos = (np.zeros(max(1, total.value), sa.dtype) for _ in range(2))
+    ctx.check(fn(*(head + [_ptr(sid), _ptr(pos), total.value, C.byref(total)])))
+    return start, sid[:total.value], pos[:total.value]
 
 
 MEMS_SUPER = _lib.PSACX_MEMS_SUPER
