@@ -97,6 +97,9 @@ typedef struct psacx_stats {
     uint64_t group_sort;           /* the one-word prefix sort of the last construction: 0 = LSD passes on every digit inside the 256 buckets, 1 = upper digits most
                                       significant first and the groups of the last 16 prefix bits sorted on chip, 2 = that form entered, a group longer
                                       than its cap found, the remaining digits sorted LSD inside the partition reached */
+    uint64_t tie_form;             /* the side stream the tie stage of the last construction's one-word first round looked for its groups in: 0 = none (it compared
+                                      the records, or the first round did not keep one-word records), 1 = a tie byte per record, 2 = the tie bits of the group sort
+                                      (PSACX_OPT_PLAIN_SIDE_KERNELS = 2 pins the bytes) */
     uint64_t grid_cuts;            /* launches of grid-stride kernels since the context was created whose grid came out smaller than the workgroups their items
                                       asked for, by the default bound of a few workgroups per CU or by PSACX_OPT_GRID_CAP: some workgroup of such a launch takes a
                                       second trip through its loop.  Never cleared; filled by psacx_get_stats. */
@@ -147,6 +150,8 @@ int psacx_trim(psacx_ctx* ctx);
  *   GENERIC_REBUCKET  the first round on one-word records runs the generic rebucket kernel, not its 32-bit form (A/B runs)
  *   PLAIN_SIDE_KERNELS the tile histograms of the top digit and the tie scan of the one-word first round run their one-tile-per-workgroup
  *                     kernels (top_digit_hist_kernel, tie_resolve_1w_kernel), not the persistent ones (parity tests, A/B runs)
+ *                     2 = TIE_BYTES: the persistent kernels, but the group form of the prefix sort leaves a tie byte per record and the tie scan reads
+ *                     those, not the tie bits (psacx_stats.tie_form; parity tests, A/B runs; PSACX_TIE_BYTES in the debug shim); larger values are refused
  *   LSD_BUCKET_PASSES the one-word prefix sort of the first round sorts every digit below the top one by LSD passes inside the 256 buckets, not the
  *                     upper digits most significant first and the last 16 bits on chip (psacx_stats.group_sort; parity tests, A/B runs)
  *   GROUP_COUNTING_ROUNDS the group form orders the last 16 prefix bits of every batch by two or three stable counting rounds, not by one round and the

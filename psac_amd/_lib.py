@@ -20,6 +20,7 @@ PSACX_OVERLAP_WHOLE = 1
 PSACX_REPEATS_RIGHT, PSACX_REPEATS_MAXIMAL, PSACX_REPEATS_SUPERMAXIMAL = 0, 1, 2
 PSACX_MEMS_SUPER = 1
 PSACX_KEDIT_BEST = 1
+PSACX_SIDE_PLAIN, PSACX_SIDE_TIE_BYTES = 1, 2       # values of the option plain_side_kernels; Stats.tie_form: 0 none, 1 tie bytes, 2 tie bits
 
 # psacx_configure options (include/psacx.h); Context.configure(force_diet=1, ...) takes them by name
 OPTIONS = {"reset": 0, "force_diet": 1, "diet_cap": 2, "one_stage": 3, "ties_radix": 4, "no_one_word": 5, "one_word_always": 6, "one_word_min": 7,
@@ -97,7 +98,7 @@ class Stats(C.Structure):
                 ("scatter_bytes", C.c_uint64 * 3), ("hist_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64), ("onew_passes", C.c_uint64),
                 ("heavy_rounds", C.c_uint64), ("heavy_records", C.c_uint64), ("light_records", C.c_uint64), ("level_gathers", C.c_uint64),
                 ("ms_host", C.c_double * 9), ("locate_fetches", C.c_uint64 * 2), ("rebucket_1w", C.c_uint64),
-                ("group_sort", C.c_uint64), ("grid_cuts", C.c_uint64)]
+                ("group_sort", C.c_uint64), ("tie_form", C.c_uint64), ("grid_cuts", C.c_uint64)]
 
 
 class PsacxError(RuntimeError):

@@ -66,6 +66,8 @@ struct Knobs {
                                   // (sa_kernels.hpp; parity suite and A/B runs)
     bool plain_side_kernels = false; // PSACX_OPT_PLAIN_SIDE_KERNELS: top_digit_hist_kernel and tie_resolve_1w_kernel (a workgroup per tile), not the persistent
                                   // top_digit_hist_waves_kernel and tie_resolve_1w_waves_kernel (sa_kernels.hpp; parity tests and A/B runs)
+    bool tie_bytes = false;       // PSACX_OPT_PLAIN_SIDE_KERNELS = 2: the persistent kernels, but the group form of the prefix sort leaves a tie byte per record and
+                                  // the tie scan reads bytes, not the tie bits (tie_bits.hpp; psacx_stats.tie_form; parity tests and A/B runs)
     bool lsd_bucket_passes = false; // PSACX_OPT_LSD_BUCKET_PASSES: the one-word prefix sort runs LSD passes on all digits inside the 256 buckets, not the group form
                                   // (onew_bucket_passes: upper digits most significant first, the last 16 bits on chip; parity tests and A/B runs)
     bool group_counting_rounds = false; // PSACX_OPT_GROUP_COUNTING_ROUNDS: group_sort16_kernel orders every batch by stable counting rounds, not by one round and the ranks
@@ -1010,7 +1012,10 @@ constexpr int PSACX_RETRY_1STAGE = 1002;
 // -- written by the pass on the top digit and by every bucket pass but the last; the tile histograms then read it instead of the records.
 inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long long* h_tabs, const OneWordLayout& lay, uint64_t* cur, uint64_t* oth, uint64_t* sa_out,
                               unsigned sfield, unsigned low, unsigned lo1, uint64_t nrec, uint64_t** s1, OneWordView* view_out = nullptr, uint8_t* dig = nullptr,
-                              uint64_t in_pad = 0, uint8_t* tie_bytes = nullptr, unsigned long long* h_word = nullptr) {
+                              uint64_t in_pad = 0, uint8_t* tie_bytes = nullptr, unsigned long long* h_word = nullptr, bool* tie_bits = nullptr) {
+    // tie_bits (with tie_bytes): the caller's tie scan reads either side stream.  The group sort then leaves tie BITS in the first nrec / 8 bytes of
+    // tie_bytes (tie_bits.hpp) and *tie_bits says so; everything else that writes the side stream -- the LSD last pass, also behind a group longer than
+    // GROUP_CAP -- writes bytes, and so does the group sort under PSACX_OPT_PLAIN_SIDE_KERNELS (1: the plain tie scan reads bytes; 2: pins the bytes)
     // tie_bytes (with view_out): the last pass leaves the LOWEST byte of the prefix bits of the record at every place there: two neighbours that
     // tie on the prefix agree in it, two that do not agree in it once in 256 -- the tie stage reads these bytes instead of the records
     // in_pad: in the input of the FIRST pass the records of bucket b lie b * in_pad places further than bucket_off says (prefix_sort_1w)
@@ -1025,6 +1030,7 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
     SlabInfo* slab_info = reinterpret_cast<SlabInfo*>(scratch + lay.slab_info);
     tb.slab_info = slab_info;
     *s1 = cur;
+    if (tie_bits) *tie_bits = false;
     if (view_out) { view_out->off = d_tabs; view_out->low = low; view_out->sfield = sfield; view_out->lo1 = lo1; }
     PSACX_HIP(c, hipMemcpyAsync(d_tabs, h_tabs, 2 * (RADIX + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
     if (lay.total_slabs == 0) return PSACX_OK;
@@ -1134,12 +1140,20 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
         ProfScope ps(c, TC_SORT_SCATTER2);
         // (persistent waves, five workgroups of 256 per CU -- 96 VGPRs, 82 in the form of counting rounds only: five waves per SIMD; 20 KB of LDS each)
         const dim3 grid((unsigned)grid_for(c, ngroups, 256, 5));
-        if (c->knobs.group_counting_rounds)
+        const bool bits = tie_bits && !c->knobs.plain_side_kernels && !c->knobs.tie_bytes;
+        if (bits) PSACX_HIP(c, hipMemsetAsync(tie_bytes, 0, (size_t)((nrec + 63) / 64) * 8, c->stream));          // (the waves OR their bits into the words)
+        if (bits && c->knobs.group_counting_rounds)
+            hipLaunchKernelGGL((group_sort16_kernel<256, false, true>), grid, dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
+        else if (bits)
+            hipLaunchKernelGGL((group_sort16_kernel<256, true, true>), grid, dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
+        else if (c->knobs.group_counting_rounds)
             hipLaunchKernelGGL((group_sort16_kernel<256, false>), grid, dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
         else
             hipLaunchKernelGGL((group_sort16_kernel<256, true>), grid, dim3(256), 0, c->stream, cur, gbase, ngroups, nrec, (int)sfield, tie_bytes);
         PSACX_HIP(c, hipGetLastError());
-        c->stats.scatter_launches[2] += 1; c->stats.scatter_records[2] += nrec; c->stats.scatter_bytes[2] += 17ull * nrec;      // (record read and written, tie byte)
+        if (bits) *tie_bits = true;
+        // (record read and written, tie byte -- with the tie bits 16 + 1/8 at most, counted as 17 all the same: DESIGN.md section 6)
+        c->stats.scatter_launches[2] += 1; c->stats.scatter_records[2] += nrec; c->stats.scatter_bytes[2] += 17ull * nrec;
         c->stats.onew_passes += 1;
     }
     c->stats.group_sort = 1;
@@ -1151,7 +1165,8 @@ inline int onew_bucket_passes(psacx_ctx* c, char* scratch, const unsigned long l
 // dig: n bytes (rounded up to 16) of scratch for the digit bytes between the passes (onew_bucket_passes), or null
 inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t* a, uint64_t* sa_out, uint64_t n, unsigned lo1, unsigned lead,
                           psacx_round* rs, uint64_t** s1, const uint8_t* text, uint64_t n_text, const CodeTable& tab, const KeyShape& ks, bool probe,
-                          OneWordView* view_out = nullptr, uint8_t* dig = nullptr, uint64_t pad = 0, uint8_t* tie_bytes = nullptr) {
+                          OneWordView* view_out = nullptr, uint8_t* dig = nullptr, uint64_t pad = 0, uint8_t* tie_bytes = nullptr, bool* tie_bits = nullptr) {
+    // tie_bits: see onew_bucket_passes -- the side stream may come back as tie bits, and *tie_bits says whether it did
     // pad (even; k0 must hold n + 256 * pad words): the pass on the top digit writes bucket b's records b * pad places further -- into k0, so that
     // only the first bucket pass reads the padded layout -- because output fronts a multiple of 2^27 bytes apart (2^32 records of 8 bytes in 256
     // equal buckets) alias in the memory channels (tools/ubench_fronts.hip)
@@ -1217,8 +1232,8 @@ inline int prefix_sort_1w(psacx_ctx* c, SortScratch& sc, uint64_t* k0, uint64_t*
     }
     // the buckets (the tables of the first pass in the scratch are dead once its scatter has run: same stream)
     uint64_t* cur = nullptr;
-    if (pad) PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, k0, a, sa_out, sfield, low, lo1, n, &cur, view_out, dig, pad, tie_bytes, h_word));
-    else PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, a, k0, sa_out, sfield, low, lo1, n, &cur, view_out, dig, 0, tie_bytes, h_word));
+    if (pad) PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, k0, a, sa_out, sfield, low, lo1, n, &cur, view_out, dig, pad, tie_bytes, h_word, tie_bits));
+    else PSACX_TRY(onew_bucket_passes(c, scratch, h_tabs, lay, a, k0, sa_out, sfield, low, lo1, n, &cur, view_out, dig, 0, tie_bytes, h_word, tie_bits));
     *s1 = cur;          // (without pad: k0 after an odd number of bucket passes, `a` after an even number; with pad the other way round)
     if (rs) { rs->sort_passes = (uint32_t)((low + RADIX_BITS - 1) / RADIX_BITS + 1); rs->sort_passes_skipped = 0; }
     return PSACX_OK;

@@ -20,6 +20,7 @@ template <typename T> struct FirstSorted {
     T* onew_w1;              // ... and word 1 of the suffixes that tie on the leading bits is here
     bool packed1;            // the one-word sort ran: word 1 comes back without its bits below the prefix
     uint8_t* tie_bytes;      // ... and left the lowest byte of every record's prefix bits here (engine.hpp: onew_bucket_passes)
+    bool tie_bits;           // ... or, from the group sort, a bit per place in its first n / 8 bytes: the places p - 1 and p tie (tie_bits.hpp)
 };
 
 // (64-bit words, at most 2^32 characters: the list comes with its entries' bucket numbers counted from 0, in the idle upper half of the
@@ -141,7 +142,13 @@ int resolve_prefix_ties(psacx_ctx* c, Work<T>& w, const uint8_t* d_text, uint64_
             // last pass: persistent waves, a tile of 64 x 32 places each per trip, four workgroups per CU (sa_kernels.hpp;
             // PSACX_OPT_PLAIN_SIDE_KERNELS pins the workgroup-per-tile kernel)
             const uint64_t nwt = (n + (uint64_t)WAVE * TI - 1) / ((uint64_t)WAVE * TI);
-            if (s.onew && s.tie_bytes && !kn.plain_side_kernels)
+            const uint64_t nbt = (n + (uint64_t)WAVE * 64 - 1) / ((uint64_t)WAVE * 64);          // (with the tie bits: a word per lane)
+            c->stats.tie_form = !s.onew ? 0 : s.tie_bits ? 2 : s.tie_bytes ? 1 : 0;
+            if (s.onew && s.tie_bytes && s.tie_bits)
+                hipLaunchKernelGGL((tie_resolve_1w_waves_kernel<TB, TI, TG, true>), dim3((unsigned)grid_for(c, nbt * WAVE, TB, 4)), dim3(TB), 0, c->stream,
+                                   reinterpret_cast<uint64_t*>(S1), reinterpret_cast<uint64_t*>(free_k1), reinterpret_cast<uint64_t*>(S2), n, s.view, d_text, n,
+                                   tab, ks, d_big, (const uint8_t*)s.tie_bytes, nbt);
+            else if (s.onew && s.tie_bytes && !kn.plain_side_kernels)
                 hipLaunchKernelGGL((tie_resolve_1w_waves_kernel<TB, TI, TG>), dim3((unsigned)grid_for(c, nwt * WAVE, TB, 4)), dim3(TB), 0, c->stream,
                                    reinterpret_cast<uint64_t*>(S1), reinterpret_cast<uint64_t*>(free_k1), reinterpret_cast<uint64_t*>(S2), n, s.view, d_text, n,
                                    tab, ks, d_big, (const uint8_t*)s.tie_bytes, nwt);
@@ -255,7 +262,7 @@ int first_sort_two_stage(psacx_ctx* c, Work<T>& w, const uint8_t* d_text, uint64
             const int rc1 = prefix_sort_1w(c, w.sc, reinterpret_cast<uint64_t*>(in1.k1), reinterpret_cast<uint64_t*>(alt1.k1),
                                            reinterpret_cast<uint64_t*>(d_sa), n, lo1, lead, r0, &s1, d_text, n, sh.tab, sh.ks, !kn.one_word_always,
                                            keep ? &s.view : nullptr, dig,
-                                           (in1.k1 == w.x.k1 && onew_pad_total<T>(n)) ? ONEW_PAD : (uint64_t)0, s.tie_bytes);
+                                           (in1.k1 == w.x.k1 && onew_pad_total<T>(n)) ? ONEW_PAD : (uint64_t)0, s.tie_bytes, &s.tie_bits);
             if (rc1 == PSACX_RETRY_1STAGE) return rc1;          // (nearly every suffix ties on the prefix: one sort over both words; nothing was written)
             if (rc1 == PSACX_RETRY_1W) {          // (a repetitive text, or no room for the bucket tables: nothing was written)
                 one_word = false;

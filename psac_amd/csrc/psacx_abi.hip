@@ -130,7 +130,7 @@ int psacx_configure(psacx_ctx* c, int option, uint64_t value) {
     case PSACX_OPT_LOCATE_SHAPE: if (value > 2) return PSACX_EINVAL; k.locate_shape = (int)value; return PSACX_OK;
     case PSACX_OPT_LOCATE_COUNT: k.locate_count = value != 0; return PSACX_OK;
     case PSACX_OPT_GENERIC_REBUCKET: k.generic_rebucket = value != 0; return PSACX_OK;
-    case PSACX_OPT_PLAIN_SIDE_KERNELS: k.plain_side_kernels = value != 0; return PSACX_OK;
+    case PSACX_OPT_PLAIN_SIDE_KERNELS: if (value > 2) return PSACX_EINVAL; k.plain_side_kernels = value == 1; k.tie_bytes = value == 2; return PSACX_OK;
     case PSACX_OPT_LSD_BUCKET_PASSES: k.lsd_bucket_passes = value != 0; return PSACX_OK;
     case PSACX_OPT_GROUP_COUNTING_ROUNDS: k.group_counting_rounds = value != 0; return PSACX_OK;
     case PSACX_OPT_LZ_SMALL_TILES: k.lz_small_tiles = value != 0; return PSACX_OK;
@@ -158,6 +158,7 @@ int psacx_configure_from_env(psacx_ctx* c) {
         {"PSACX_LZ_SMALL_TILES", PSACX_OPT_LZ_SMALL_TILES}, {"PSACX_GROUP_COUNTING_ROUNDS", PSACX_OPT_GROUP_COUNTING_ROUNDS}};
     (void)psacx_configure(c, PSACX_OPT_RESET, 0);
     for (const auto& f : flags) if (psacx_debug_env(f.name)) (void)psacx_configure(c, f.option, 1);
+    if (psacx_debug_env("PSACX_TIE_BYTES") && !psacx_debug_env("PSACX_PLAIN_SIDE_KERNELS")) (void)psacx_configure(c, PSACX_OPT_PLAIN_SIDE_KERNELS, 2);
     if (const char* e = psacx_debug_env("PSACX_DIET_CAP")) (void)psacx_configure(c, PSACX_OPT_DIET_CAP, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_FIRST_LEAD")) (void)psacx_configure(c, PSACX_OPT_FIRST_LEAD, strtoull(e, nullptr, 10));
     if (const char* e = psacx_debug_env("PSACX_GRID_CAP")) (void)psacx_configure(c, PSACX_OPT_GRID_CAP, strtoull(e, nullptr, 10));

@@ -16,6 +16,7 @@
 #include "dev_common.hpp"
 #include "sort_scratch.hpp"
 #include "group_rank.hpp"
+#include "tie_bits.hpp"
 
 namespace psacx {
 
@@ -1070,14 +1071,41 @@ __device__ __forceinline__ bool group_rank_rows(uint64_t (&r)[GROUP_CAP / WAVE],
 // a bucket too large for that, and a single group of more than GROUP_RANK_BATCH records, takes the way of the other form.
 // !RANK (PSACX_OPT_GROUP_COUNTING_ROUNDS): batches of at most GROUP_CAP records, ordered by stable 8-bit counting rounds -- two rounds for one
 // group, a third on the digit above for a batch of several groups (that digit numbers the groups of a bucket).
-// Both leave the stable order by the 16 bits inside every group, so the same records and tie bytes.
+// Both leave the stable order by the 16 bits inside every group, so the same records and tie bytes (or tie bits: BITS, below).
 // A group longer than GROUP_CAP is left as it is: the caller checks the largest group before it launches.
 // ---------------------------------------------------------------------------
 // (GROUP_CAP: sort_scratch.hpp -- the layouts of the group form depend on it)
-template <int BLOCK, bool RANK = true>
+// BITS: no tie bytes.  tie_bytes is an array of zeroed 64-bit words instead, and bit p of it (tie_bits.hpp) is set iff the records the kernel leaves
+// at the places p - 1 and p lie in one batch and agree above their suffix field -- what the tie scan otherwise finds out by comparing neighbouring
+// bytes and then the records of every pair that agrees in them.  When a batch is written back every lane holds the record of its place: the
+// record before it is one lane move away (lane 0: the last lane of the row before), one ballot per row gives 64 bits, and the rows of a batch
+// are put together to whole words in scalar registers, word k of the batch in lane k.  A batch starts at any place, so its first and last word
+// may be shared with the batches of other waves: every word that has a bit set is merged with an atomic OR, whose result does not depend on the order of
+// the waves; words without a set bit (six in ten on random text) are not touched.  1/8 byte per record, and most of it never leaves the chip.
+__device__ __forceinline__ unsigned lane_before_rotating(unsigned v) {          // lane l takes v of lane l - 1, lane 0 that of lane 63
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x13C /* wave_ror:1 */, 0xF, 0xF, false);
+}
+// v of lane `lane` = value (the same in every lane: a scalar register).  lane: 0 .. 7, a constant once the caller's loop over the rows is unrolled -- the
+// instruction takes one scalar register only, so the lane is part of it
+template <int LANE>
+__device__ __forceinline__ void set_lane_at(unsigned& v, unsigned value) { asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(value), "n"(LANE)); }
+__device__ __forceinline__ void set_lane(unsigned& v, unsigned value, int lane) {
+    switch (lane) {
+    case 0: set_lane_at<0>(v, value); break;
+    case 1: set_lane_at<1>(v, value); break;
+    case 2: set_lane_at<2>(v, value); break;
+    case 3: set_lane_at<3>(v, value); break;
+    case 4: set_lane_at<4>(v, value); break;
+    case 5: set_lane_at<5>(v, value); break;
+    case 6: set_lane_at<6>(v, value); break;
+    default: set_lane_at<7>(v, value); break;
+    }
+}
+template <int BLOCK, bool RANK = true, bool BITS = false>
 __global__ __launch_bounds__(BLOCK, RANK ? 5 : 1) void group_sort16_kernel(uint64_t* __restrict__ recs, const unsigned long long* __restrict__ starts, uint64_t ngroups,
                                                              uint64_t nrec, int sfield, uint8_t* __restrict__ tie_bytes) {
     constexpr int NW = BLOCK / WAVE, ROWS = GROUP_CAP / WAVE;
+    static_assert(ROWS == 8, "set_lane: the words of a batch in the lanes 0 .. 8");
     constexpr unsigned BATCH = RANK ? GROUP_RANK_BATCH : (unsigned)GROUP_CAP;          // records of a batch of several groups
     static_assert(GROUP_RANK_BATCH == 6 * WAVE, "group_rank_rows is instantiated for one to six rows");
     __shared__ unsigned s_cnt[NW][RADIX];
@@ -1165,12 +1193,44 @@ __global__ __launch_bounds__(BLOCK, RANK ? 5 : 1) void group_sort16_kernel(uint6
                     if ((unsigned)i < rows && (unsigned)(i * WAVE) + lane < count) r[i] = stage[(unsigned)(i * WAVE) + lane];
                 xrun_order();
             }
+            unsigned long long mine = 0;          // BITS: the tie bits of the batch, word k of them in lane k, and where that word lies
+            uint64_t word0 = 0;
+            if constexpr (BITS) {
+                const uint64_t first = wave_uniform64(a);
+                const unsigned ucount = (unsigned)__builtin_amdgcn_readfirstlane((int)count), urows = (unsigned)__builtin_amdgcn_readfirstlane((int)rows);
+                unsigned tl = lane;
+                asm volatile("" : "+v"(tl));          // (nothing of what follows is computed ahead of the batch and kept in registers through its ordering)
+                unsigned mine_lo = 0, mine_hi = 0;          // lane k: word k of the batch, counted from the word of its first place
+                uint64_t carry = 0;                         // what the row before leaves for the word behind its own
+                const unsigned below = 1u << (sfield - 32);          // two upper halves tie when they differ below this (tie_pair_high)
+                const unsigned sh = (unsigned)first & 63u, tail = ucount & 63u;
+                const uint64_t last_row = tail ? (1ull << tail) - 1ull : ~0ull;          // (the lanes behind the batch hold zeros)
+#pragma unroll
+                for (int i = 0; i < ROWS; ++i) {
+                    if ((unsigned)i < urows) {
+                        const unsigned hi = (unsigned)(r[i] >> 32);
+                        const unsigned turn = i > 0 && tl == (unsigned)(WAVE - 1) ? (unsigned)(r[i > 0 ? i - 1 : 0] >> 32) : hi;
+                        uint64_t row = __ballot((lane_before_rotating(turn) ^ hi) < below);
+                        if ((unsigned)i + 1 == urows) row &= last_row;
+                        if (i == 0) row &= ~1ull;                                         // the first place of a batch: no bit
+                        const uint64_t word = carry | row << sh;                          // (tie_row_low, tie_row_high)
+                        carry = row >> 1 >> (63u - sh);
+                        set_lane(mine_lo, (unsigned)word, i);
+                        set_lane(mine_hi, (unsigned)(word >> 32), i);
+                    }
+                }
+                if (tl == urows) { mine_lo = (unsigned)carry; mine_hi = (unsigned)(carry >> 32); }
+                mine = (unsigned long long)mine_hi << 32 | mine_lo;
+                word0 = (first >> 6) + tl;
+            }
 #pragma unroll
             for (int i = 0; i < ROWS; ++i)
                 if ((unsigned)(i * WAVE) + lane < count) {
                     recs[a + (unsigned)(i * WAVE) + lane] = r[i];
-                    tie_bytes[a + (unsigned)(i * WAVE) + lane] = (uint8_t)(r[i] >> sfield);
+                    if constexpr (!BITS) tie_bytes[a + (unsigned)(i * WAVE) + lane] = (uint8_t)(r[i] >> sfield);
                 }
+            // (a set bit belongs to a place below nrec, so its word lies inside the array; lanes above the batch's words hold nothing)
+            if constexpr (BITS) if (mine) atomicOr(reinterpret_cast<unsigned long long*>(tie_bytes) + word0, mine);
         }
     }
 }

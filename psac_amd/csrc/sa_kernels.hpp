@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "dev_common.hpp"
 #include "rebucket_1w_math.hpp"
+#include "tie_bits.hpp"
 
 namespace psacx {
 
@@ -2307,19 +2308,25 @@ __device__ __forceinline__ void window_low_and_word2_wide(const uint8_t* __restr
 //  - the windows of the tied suffixes are read by window_low_and_word2_wide (4.57 -> 4.02 ms together with the next item);
 //  - a tile that lies inside one bucket of the top digit asks the bucket table once (TileBucket), not once per candidate and group;
 //  - the record behind a group's eight places is read only when all eight tie.
-template <int BLOCK, int ITEMS, int G>
+// BITS: tb holds the tie bits the group sort left (tie_bits.hpp; radix.hpp: group_sort16_kernel<.., BITS>), not a byte per place: bit p says that the
+// places p - 1 and p tie, so there are no candidates to list and no records to load for them.  A tile is the 64 x 64 places of one word per
+// lane (ntiles counts those); the words of the next tile are asked for ahead of this one's; a place whose bit is clear and whose successor's
+// bit is set leads a group (tie_leaders: bit 0 of the word behind comes from the next lane, for the last lane from memory), and the leaders go
+// into the same list in LDS, in place order.  The group pass is the one above, so a run of eight or more set bits -- nine members -- raises
+// `big` as there.  R, W1, S2 and big come out as from the bytes.
+template <int BLOCK, int ITEMS, int G, bool BITS = false>
 __global__ __launch_bounds__(BLOCK, 4) void tie_resolve_1w_waves_kernel(uint64_t* __restrict__ R, uint64_t* __restrict__ W1, uint64_t* __restrict__ S2,
                                                                      uint64_t n, OneWordView ow, const uint8_t* __restrict__ text, uint64_t n_text,
                                                                      CodeTable tab, KeyShape ks, unsigned long long* __restrict__ big,
                                                                      const uint8_t* __restrict__ tb, uint64_t ntiles) {
     typedef uint64_t T;
-    constexpr int NW = BLOCK / WAVE, WT = WAVE * ITEMS;          // WT: places of a tile
+    constexpr int NW = BLOCK / WAVE, WT = WAVE * (BITS ? 64 : ITEMS);          // WT: places of a tile
     static_assert(ITEMS == 32, "a thread takes the 32 bytes of its places as two 16-byte pieces");
-    static_assert(G == 8, "eight lanes per group");
+    static_assert(G == 8 && (unsigned)G == TIE_GROUP_MAX, "eight lanes per group");
     static_assert(WT < 65536, "pairs and places of a tile as 16-bit entries");
     __shared__ uint16_t ctab[256];
     __shared__ unsigned long long s_off[257];
-    __shared__ uint16_t cands[NW][WT + 2];           // the candidate pairs of every wave's tile, ascending
+    __shared__ uint16_t cands[NW][BITS ? 2 : WT + 2];           // the candidate pairs of every wave's tile, ascending (none with BITS)
     __shared__ uint16_t leaders[NW][WT / 2 + 2];     // the first places of its groups, ascending (of the tile before, until its groups are ordered)
     for (int i = threadIdx.x; i < 256; i += BLOCK) ctab[i] = tab.c[i];
     for (int i = threadIdx.x; i < 257; i += BLOCK) s_off[i] = ow.off[i];
@@ -2397,12 +2404,56 @@ __global__ __launch_bounds__(BLOCK, 4) void tie_resolve_1w_waves_kernel(uint64_t
     };
     const uint64_t nwaves = (uint64_t)gridDim.x * NW;
     uint64_t tile = (uint64_t)blockIdx.x * NW + wave;
-    uint4 a0, a1;
-    unsigned ax;
-    fetch(tile, a0, a1, ax);
     uint64_t pwb = 0;               // the tile before: its first place, its bucket and the number of its groups, their leaders in ll
     TileBucket ptk = {true, 0u, 0ull};
     unsigned pnl = 0;
+    if constexpr (BITS) {
+        const unsigned long long* __restrict__ const words = reinterpret_cast<const unsigned long long*>(tb);
+        const uint64_t nwords = (n + 63) / 64;
+        // the word of this lane's 64 places in a tile; ext (the last lane): bit 0 of the word behind the tile, 0 where there is none
+        auto fetch_word = [&](uint64_t t, uint64_t& w, unsigned& ext) {
+            w = 0; ext = 0;
+            if (t >= ntiles) return;
+            const uint64_t i = t * WAVE + lane;
+            if (i < nwords) w = words[i];
+            if (lane == WAVE - 1 && i + 1 < nwords) ext = (unsigned)words[i + 1] & 1u;
+        };
+        uint64_t aw;
+        unsigned ax;
+        fetch_word(tile, aw, ax);
+        while (tile < ntiles) {
+            const uint64_t next = tile + nwaves;
+            uint64_t bw;
+            unsigned bx;
+            fetch_word(next, bw, bx);
+            const unsigned long long any_big = __hip_atomic_load(big, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t wb = tile * WT;
+            unsigned next0 = shfl<unsigned>((unsigned)aw & 1u, (int)((lane + 1) & (WAVE - 1)));
+            if (lane == WAVE - 1) next0 = ax;
+            uint64_t lead = tie_leaders(aw, next0);
+            const unsigned cnt = (unsigned)__builtin_popcountll(lead);
+            const unsigned incl = wave_scan_inclusive<unsigned>(cnt, OpSum());
+            const unsigned nl = (unsigned)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
+            order_groups(pwb, ptk, any_big ? 0u : pnl);          // (ll holds the leaders of the tile before until here)
+            xrun_order();
+            if (nl) {
+                unsigned o = incl - cnt;
+                while (lead) {
+                    ll[o++] = (uint16_t)(lane * 64u + (unsigned)__builtin_ctzll(lead));
+                    lead &= lead - 1;
+                }
+            }
+            xrun_order();
+            pwb = wb; ptk = tile_bucket(wb); pnl = nl;
+            aw = bw; ax = bx;
+            tile = next;
+        }
+        order_groups(pwb, ptk, __hip_atomic_load(big, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0u : pnl);
+        return;
+    }
+    uint4 a0, a1;
+    unsigned ax;
+    fetch(tile, a0, a1, ax);
     while (tile < ntiles) {
         const uint64_t next = tile + nwaves;
         uint4 b0, b1;
