@@ -1274,6 +1274,95 @@ int psacx_doc_list_u64(psacx_ctx* ctx, const uint64_t* SA, uint64_t n, const uin
                        const uint64_t* ub, uint64_t q, uint64_t max_cand, uint64_t* start, uint64_t* sid, uint64_t* pos, uint64_t cap,
                        uint64_t* total);
 
+/* FM-index ---------------------------------------------------------------------------------
+ * A compressed full-text index: backward search on the Burrows-Wheeler transform counts patterns without text or suffix array, and a
+ * sampled suffix array gives their positions.  After the build the caller may free text and SA and keep the index, a fraction of
+ * their size.  The reference has no counterpart.  One GPU.
+ *
+ * Setting, as for psacx_bwt_dev_*: one text S[0..n), or m strings back to back.  bwt and first are exactly what psacx_bwt_dev_* writes:
+ * cyclic per string, first[r] set iff SA[r] starts a string.  One text is a set of one string and passes its first bitmap too.
+ *
+ * Symbols.  code[256] maps the bytes that occur to 1 .. sigma in byte order; bytes that do not occur are coded 0.  Code 0 is also the
+ * STOP symbol: w[r] = 0 if first[r], else code[bwt[r]].  bits = ceil(log2(sigma + 1)), from 1 to 9: with sigma = 256 the codes need 9
+ * bits and do not fit a byte.
+ * Counts.  cnt[c] = the ranks r with code[S[SA[r]]] == c (the text bytes of code c); C[c] = the sum of cnt[d] over d < c;
+ * E[c] = the strings whose last byte has code c = #{r : first[r] and code[bwt[r]] == c}.
+ * LF.  For a rank r with w[r] = c != 0: LF(r) = C[c] + E[c] + rank_c(r), rank_c(r) = #{x < r : w[x] == c}; then SA[LF(r)] = SA[r] - 1.
+ * The E[c] suffixes that are the last byte of a string alone have no predecessor rank and are the smallest suffixes that start with c;
+ * without E[c], "iss" in mississippi comes out as [1, 3) instead of [2, 4).
+ * Backward search of P[0..L).  L == 0 gives [0, n).  A byte coded 0 gives a miss.  The FIRST step, on the last byte c, is
+ * [C[c], C[c] + cnt[c]): pushing [0, n) through LF would lose the E[c] one-byte suffixes ("ippi" would miss).  Every further step maps
+ * both bounds by C[c] + E[c] + rank_c(.).  An empty interval ends the search.
+ * Result.  For a pattern that occurs (inside one string) the result is exactly the interval of psacx_locate_dev_* /
+ * psacx_locate_gsa_dev_*.  A miss is pinned to lb = ub = 0: this is NOT locate's insertion point.  STOP makes matches across two
+ * strings impossible without any bitmap test.
+ * Samples.  With a sample rate s >= 1, rank r is marked iff first[r] or SA[r] % s == 0, and val[rank_marks(r)] = SA[r], entries of the
+ * index type.  From any rank fewer than s LF steps reach a marked rank x, and SA[r] = val[rank_marks(x)] + steps.  s == 0: no samples,
+ * the index counts only.
+ *
+ * The index is one opaque array of 64-bit words in HBM and a host descriptor, psacx_fm_info, which the build fills and every query
+ * takes back (the convention of code[256] / sigma of the lookup table).  With cells = (n >> 6) + 1 the blob holds, in this order: a
+ * binary wavelet matrix over w, bits levels of cells cells of 16 bytes {ones in front of this cell, 64 bits}, most significant bit
+ * first, so that one rank is one 16-byte load; 544 words of tables (the zeros per level, C, and C + E - the start of the symbol behind
+ * the last level, so that a bound costs `bits` dependent cells and one add); with s > 0 the marks, cells cells of the same form, and val:
+ *     words = 2 * bits * cells + 544 + (s ? 2 * cells : 0) + ceil(sizeof(T) * marks / 8),
+ * at most 16 * bits * cells + 16 * cells [if s] + sizeof(T) * marks + 16 KiB bytes: 0.75 bytes per character for DNA counting (sigma 4
+ * and STOP give 3 bits).  The layout may change between versions of the library; a blob is not a file format.
+ *
+ * psacx_fm_index_dev_*: d_SA is read only with sample > 0.  d_fm == NULL is the size query: it fills *info (words among it) and writes
+ * nothing else; it reads d_bwt, d_first and, with sample > 0, d_SA.
+ *  - n == 0 is PSACX_OK (an index whose every search misses).  n beyond the index type or beyond 2^48 returns PSACX_ERANGE.
+ *  - d_first == NULL, info == NULL, d_bwt == NULL with n > 0, or sample > 0 with d_SA == NULL return PSACX_EINVAL.
+ *  - Stages, all streaming: a histogram of the bytes and of the last bytes of the strings gives the codes and the tables; the codes w as
+ *    16 bits; per level one ballot per wave gives the cell word and its count, the scan gives the directory, and a stable partition sends
+ *    each code to bit ? Z + rank1(r) : r - rank1(r) of the next level's order; marks and val the same way.
+ *  - Scratch.  The ctx slab holds the block sums of the scans, the histogram and one count per cell.  Beside the slab and for the time of
+ *    the call: two arrays of n 16-bit codes.  Where that fails the call returns PSACX_ENOMEM with d_fm and *info untouched.
+ *  - After psacx_profile(ctx, 1) the build leaves the times of its stages in psacx_stats: ms_kmer the histogram, the mark count and the
+ *    codes, ms_sort_scatter the levels, ms_rebucket the marks and samples (tools/fm_time.py).
+ * psacx_fm_count_dev_*: one pattern per lane, d_pat / d_poff as psacx_locate_dev_* takes them (malformed offsets: PSACX_EINVAL, nothing
+ * written).  lb_j, ub_j as under "Result".  A descriptor whose bits / words do not follow from its n, sigma, sample and marks for this
+ * index type, or with a code beyond sigma, returns PSACX_EINVAL.  q == 0 is PSACX_OK.
+ * psacx_fm_occurrences_dev_*: the contract of psacx_occurrences_dev_* (limit; d_pos == NULL is the size query; *total > cap returns
+ * PSACX_ERANGE with start and *total valid and the lists untouched; d_sid optional, with d_offsets), where SA[r] is replaced by the LF
+ * walk from r to a marked rank.  An index built with sample == 0 returns PSACX_EINVAL.
+ * Totality, whatever the blob holds: nothing is read outside its `words` words; every search ends after L steps; every walk ends after
+ * at most min(sample, n) steps, and a walk that met no mark gives all ones (sid = m); every interval has 0 <= lb <= ub <= n; no input
+ * is written.
+ * psacx_fm_search_*: the host-pointer form.  It stages text and SA, builds the bitmap of the string ends (offsets == NULL: one text), the
+ * BWT and the index, answers and frees what it allocated on every path.  lb / ub receive the intervals.  pos == NULL counts only (no
+ * samples are built; start, sid, cap and total are not used).  With pos: start (q + 1 entries), total and sample > 0 are required,
+ * *total > cap returns PSACX_ERANGE with lb, ub, start and *total valid. */
+typedef struct psacx_fm_info {
+    uint64_t n;            /* ranks */
+    uint64_t words;        /* 64-bit words of the blob */
+    uint64_t sample;       /* the sample rate s, 0 = counts only */
+    uint64_t marks;        /* marked ranks = entries of val */
+    uint32_t sigma;        /* distinct bytes */
+    uint32_t bits;         /* levels of the wavelet matrix */
+    uint16_t code[256];    /* byte -> 1 .. sigma, 0 = does not occur */
+} psacx_fm_info;
+int psacx_fm_index_dev_u32(psacx_ctx* ctx, uint64_t n, const uint8_t* d_bwt, const uint32_t* d_first, const uint32_t* d_SA, uint64_t sample,
+                           uint64_t* d_fm, psacx_fm_info* info);
+int psacx_fm_index_dev_u64(psacx_ctx* ctx, uint64_t n, const uint8_t* d_bwt, const uint32_t* d_first, const uint64_t* d_SA, uint64_t sample,
+                           uint64_t* d_fm, psacx_fm_info* info);
+int psacx_fm_count_dev_u32(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint8_t* d_pat, const uint64_t* d_poff,
+                           uint64_t q, uint32_t* d_lb, uint32_t* d_ub);
+int psacx_fm_count_dev_u64(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint8_t* d_pat, const uint64_t* d_poff,
+                           uint64_t q, uint64_t* d_lb, uint64_t* d_ub);
+int psacx_fm_occurrences_dev_u32(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint64_t* d_offsets, uint64_t m,
+                                 const uint32_t* d_lb, const uint32_t* d_ub, uint64_t q, uint64_t limit, uint64_t* d_start, uint32_t* d_pos,
+                                 uint32_t* d_sid, uint64_t cap, uint64_t* total);
+int psacx_fm_occurrences_dev_u64(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint64_t* d_offsets, uint64_t m,
+                                 const uint64_t* d_lb, const uint64_t* d_ub, uint64_t q, uint64_t limit, uint64_t* d_start, uint64_t* d_pos,
+                                 uint64_t* d_sid, uint64_t cap, uint64_t* total);
+int psacx_fm_search_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
+                        uint64_t sample, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t* lb, uint32_t* ub, uint64_t limit,
+                        uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total);
+int psacx_fm_search_u64(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint64_t* SA,
+                        uint64_t sample, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub, uint64_t limit,
+                        uint64_t* start, uint64_t* pos, uint64_t* sid, uint64_t cap, uint64_t* total);
+
 /* several GPUs -------------------------------------------------------------------
  * The reference's suffix_array<> IS distributed: every MPI rank holds one block of the text and of SA / ISA / LCP
  * (suffix_array.hpp:183-194, :217-228; src/psac.cpp:85-93 block-decomposes the input).  A psacx_multi stands for the

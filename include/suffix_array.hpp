@@ -1353,4 +1353,149 @@ edit_lists<index_t> kedit(suffix_array<char, index_t, true, false>& sa, simple_d
     return psacx::kedit_of(sa, text, &soff, patterns, e, k, best);
 }
 
+// The FM-index of the text or string set of a suffix array (psacx.h: "FM-index"), resident in HBM.  It is built from the suffix array
+// and the bytes it was constructed from -- fm_index(sa, begin, end) for one text, fm_index(sa, ss) for a string set -- and owns nothing
+// but its blob, its descriptor, the string offsets and a context of its own on the device of `sa`: text and suffix array may go once it stands.
+// count: element i = [lb, ub) of patterns[i], the interval of locate where it occurs and (0, 0) where it does not.  locate: the
+// occurrence lists of occurrences(), from the sampled suffix array (sample > 0; sample == 0 builds an index that counts only).
+template <typename index_t>
+class fm_index {
+    typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
+    static int build(psacx_ctx* c, uint64_t n, const uint8_t* b, const uint32_t* f, const uint32_t* s, uint64_t r, uint64_t* fm, psacx_fm_info* i) { return psacx_fm_index_dev_u32(c, n, b, f, s, r, fm, i); }
+    static int build(psacx_ctx* c, uint64_t n, const uint8_t* b, const uint32_t* f, const uint64_t* s, uint64_t r, uint64_t* fm, psacx_fm_info* i) { return psacx_fm_index_dev_u64(c, n, b, f, s, r, fm, i); }
+    static int bwt_run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* e, const uint32_t* s, uint8_t* b, uint32_t* f) { return psacx_bwt_dev_u32(c, t, n, e, s, b, f, 0); }
+    static int bwt_run(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* e, const uint64_t* s, uint8_t* b, uint32_t* f) { return psacx_bwt_dev_u64(c, t, n, e, s, b, f, 0); }
+    static int count_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint8_t* p, const uint64_t* o, uint64_t q, uint32_t* l, uint32_t* u) { return psacx_fm_count_dev_u32(c, fm, i, p, o, q, l, u); }
+    static int count_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint8_t* p, const uint64_t* o, uint64_t q, uint64_t* l, uint64_t* u) { return psacx_fm_count_dev_u64(c, fm, i, p, o, q, l, u); }
+    static int occ_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint64_t* o, uint64_t m, const uint32_t* l, const uint32_t* u, uint64_t q, uint64_t lim,
+                       uint64_t* st, uint32_t* p, uint32_t* s, uint64_t cap, uint64_t* tot) { return psacx_fm_occurrences_dev_u32(c, fm, i, o, m, l, u, q, lim, st, p, s, cap, tot); }
+    static int occ_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint64_t* o, uint64_t m, const uint64_t* l, const uint64_t* u, uint64_t q, uint64_t lim,
+                       uint64_t* st, uint64_t* p, uint64_t* s, uint64_t cap, uint64_t* tot) { return psacx_fm_occurrences_dev_u64(c, fm, i, o, m, l, u, q, lim, st, p, s, cap, tot); }
+
+    struct held {                                                // device buffers that go on every path
+        psacx_ctx* c; std::vector<void*> v;
+        explicit held(psacx_ctx* ctx) : c(ctx) {}
+        ~held() { for (std::size_t i = 0; i < v.size(); ++i) (void)psacx_dev_free(c, v[i]); }
+        void* dev(const void* src, uint64_t bytes) {
+            void* p = 0;
+            psacx::check(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1));
+            v.push_back(p);
+            if (src && bytes) psacx::check(c, psacx_copy_h2d(c, p, src, bytes));
+            return p;
+        }
+    };
+
+    psacx_ctx* c_;
+    uint64_t* d_fm_;
+    uint64_t* d_off_;
+    uint64_t m_;
+    psacx_fm_info info_;
+
+    template <bool LCP, bool LC>
+    void make(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff, std::size_t sample) {
+        static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
+        if (sa.multi_context()) throw std::runtime_error("psacx: fm_index needs a single-rank communicator (the index is built on one GPU)");
+        if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n) throw std::runtime_error("fm_index: text does not match the suffix array");
+        psacx::check(0, psacx_create(&c_, sa.comm.device(), 0));     // a context of its own: the index outlives `sa`
+        const uint64_t n = (uint64_t)sa.n;
+        held h(c_);
+        const uint8_t* d_text = (const uint8_t*)h.dev(text.data(), n);
+        const W* d_sa = (const W*)h.dev(sa.local_SA.data(), n * sizeof(W));
+        uint8_t* d_bwt = (uint8_t*)h.dev(0, n);
+        uint32_t* d_first = (uint32_t*)h.dev(0, ((n >> 5) + 1) * 4);
+        uint32_t* d_ends = 0;
+        if (soff) {
+            m_ = (uint64_t)soff->size() - 1;
+            void* p = 0;
+            psacx::check(c_, psacx_dev_alloc(c_, &p, (m_ + 1) * 8));
+            d_off_ = (uint64_t*)p;                               // (kept: the lists name the string of a position by it)
+            psacx::check(c_, psacx_copy_h2d(c_, d_off_, soff->data(), (m_ + 1) * 8));
+            d_ends = (uint32_t*)h.dev(0, ((n >> 5) + 1) * 4);
+            uint64_t words = 0;
+            psacx::check(c_, psacx_string_ends_dev(c_, d_off_, m_, n, d_ends, &words));
+        }
+        psacx::check(c_, bwt_run(c_, d_text, n, d_ends, d_sa, d_bwt, d_first));
+        const W* sa_in = sample ? d_sa : (const W*)0;
+        psacx::check(c_, build(c_, n, d_bwt, d_first, sa_in, (uint64_t)sample, (uint64_t*)0, &info_));
+        void* p = 0;
+        psacx::check(c_, psacx_dev_alloc(c_, &p, info_.words * 8));
+        d_fm_ = (uint64_t*)p;
+        psacx::check(c_, build(c_, n, d_bwt, d_first, sa_in, (uint64_t)sample, d_fm_, &info_));
+    }
+    void drop() {
+        if (d_fm_) (void)psacx_dev_free(c_, d_fm_);
+        if (d_off_) (void)psacx_dev_free(c_, d_off_);
+        d_fm_ = 0; d_off_ = 0;
+        if (c_) psacx_destroy(c_);
+        c_ = 0;
+    }
+    fm_index(const fm_index&);                                   // (one owner of the blob)
+    fm_index& operator=(const fm_index&);
+
+public:
+    template <bool LCP, bool LC, typename Iterator>
+    fm_index(suffix_array<char, index_t, LCP, LC>& sa, Iterator begin, Iterator end, std::size_t sample = 32) : c_(0), d_fm_(0), d_off_(0), m_(0) {
+        try { make(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, sample); } catch (...) { drop(); throw; }
+    }
+    template <bool LCP>
+    fm_index(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, std::size_t sample = 32) : c_(0), d_fm_(0), d_off_(0), m_(0) {
+        std::vector<uint8_t> text; std::vector<uint64_t> soff;
+        psacx::flatten_set(ss, text, soff);
+        try { make(sa, text, &soff, sample); } catch (...) { drop(); throw; }
+    }
+    ~fm_index() { drop(); }
+
+    std::size_t bytes() const { return (std::size_t)info_.words * 8; }          // the index in HBM
+    std::size_t size() const { return (std::size_t)info_.n; }
+    const psacx_fm_info& info() const { return info_; }
+
+    std::vector<std::pair<index_t, index_t> > count(const std::vector<std::string>& patterns) const {
+        std::vector<uint8_t> pat;
+        std::vector<uint64_t> off(1, 0);
+        for (std::size_t i = 0; i < patterns.size(); ++i) {
+            pat.insert(pat.end(), patterns[i].begin(), patterns[i].end());
+            off.push_back(pat.size());
+        }
+        const uint64_t q = (uint64_t)patterns.size();
+        std::vector<W> lb(q), ub(q);
+        held h(c_);
+        const uint8_t* d_pat = (const uint8_t*)h.dev(pat.data(), pat.size());
+        const uint64_t* d_poff = (const uint64_t*)h.dev(off.data(), (q + 1) * 8);
+        W* d_lb = (W*)h.dev(0, q * sizeof(W));
+        W* d_ub = (W*)h.dev(0, q * sizeof(W));
+        psacx::check(c_, count_run(c_, d_fm_, &info_, d_pat, d_poff, q, d_lb, d_ub));
+        if (q) {
+            psacx::check(c_, psacx_copy_d2h(c_, lb.data(), d_lb, q * sizeof(W)));
+            psacx::check(c_, psacx_copy_d2h(c_, ub.data(), d_ub, q * sizeof(W)));
+        }
+        std::vector<std::pair<index_t, index_t> > out(patterns.size());
+        for (std::size_t i = 0; i < patterns.size(); ++i) out[i] = std::make_pair((index_t)lb[i], (index_t)ub[i]);
+        return out;
+    }
+
+    occurrence_lists<index_t> locate(const std::vector<std::string>& patterns, std::size_t limit = 0) const {
+        const std::vector<std::pair<index_t, index_t> > iv = count(patterns);
+        const uint64_t q = (uint64_t)iv.size();
+        std::vector<W> lb(q), ub(q);
+        for (std::size_t i = 0; i < iv.size(); ++i) { lb[i] = (W)iv[i].first; ub[i] = (W)iv[i].second; }
+        occurrence_lists<index_t> out;
+        out.start.assign(q + 1, 0);
+        held h(c_);
+        const W* d_lb = (const W*)h.dev(lb.data(), q * sizeof(W));
+        const W* d_ub = (const W*)h.dev(ub.data(), q * sizeof(W));
+        uint64_t* d_start = (uint64_t*)h.dev(0, (q + 1) * 8);
+        uint64_t total = 0;
+        psacx::check(c_, occ_run(c_, d_fm_, &info_, d_off_, m_, d_lb, d_ub, q, (uint64_t)limit, d_start, (W*)0, (W*)0, 0, &total));
+        out.pos.assign(total, 0);
+        if (d_off_) out.sid.assign(total, 0);
+        W* d_pos = (W*)h.dev(0, total * sizeof(W));
+        W* d_sid = d_off_ ? (W*)h.dev(0, total * sizeof(W)) : (W*)0;
+        psacx::check(c_, occ_run(c_, d_fm_, &info_, d_off_, m_, d_lb, d_ub, q, (uint64_t)limit, d_start, d_pos, d_sid, total, &total));
+        psacx::check(c_, psacx_copy_d2h(c_, out.start.data(), d_start, (q + 1) * 8));
+        if (total) psacx::check(c_, psacx_copy_d2h(c_, out.pos.data(), d_pos, total * sizeof(W)));
+        if (total && d_off_) psacx::check(c_, psacx_copy_d2h(c_, out.sid.data(), d_sid, total * sizeof(W)));
+        return out;
+    }
+};
+
 #endif // PSACX_SUFFIX_ARRAY_HPP

@@ -69,6 +69,8 @@ EXPORTS = [
     "psacx_kedit_dev_u32", "psacx_kedit_dev_u64", "psacx_kedit_u32", "psacx_kedit_u64",
     "psacx_doc_index_dev_u32", "psacx_doc_index_dev_u64", "psacx_doc_count_dev_u32", "psacx_doc_count_dev_u64",
     "psacx_doc_list_dev_u32", "psacx_doc_list_dev_u64", "psacx_doc_count_u32", "psacx_doc_count_u64", "psacx_doc_list_u32", "psacx_doc_list_u64",
+    "psacx_fm_index_dev_u32", "psacx_fm_index_dev_u64", "psacx_fm_count_dev_u32", "psacx_fm_count_dev_u64",
+    "psacx_fm_occurrences_dev_u32", "psacx_fm_occurrences_dev_u64", "psacx_fm_search_u32", "psacx_fm_search_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -99,6 +101,12 @@ class Stats(C.Structure):
                 ("heavy_rounds", C.c_uint64), ("heavy_records", C.c_uint64), ("light_records", C.c_uint64), ("level_gathers", C.c_uint64),
                 ("ms_host", C.c_double * 9), ("locate_fetches", C.c_uint64 * 2), ("rebucket_1w", C.c_uint64),
                 ("group_sort", C.c_uint64), ("tie_form", C.c_uint64), ("grid_cuts", C.c_uint64)]
+
+
+class FmInfo(C.Structure):
+    """psacx_fm_info: the host descriptor of an FM-index; the build fills it and every query takes it back."""
+    _fields_ = [("n", C.c_uint64), ("words", C.c_uint64), ("sample", C.c_uint64), ("marks", C.c_uint64),
+                ("sigma", C.c_uint32), ("bits", C.c_uint32), ("code", C.c_uint16 * 256)]
 
 
 class PsacxError(RuntimeError):
@@ -198,6 +206,12 @@ def load():
         getattr(lib, "psacx_doc_list_dev_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_doc_count_" + suf).argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, u64, vp]
         getattr(lib, "psacx_doc_list_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_fm_index_dev_" + suf).argtypes = [vp, u64, vp, vp, vp, u64, vp, C.POINTER(FmInfo)]
+        getattr(lib, "psacx_fm_count_dev_" + suf).argtypes = [vp, vp, C.POINTER(FmInfo), vp, vp, u64, vp, vp]
+        getattr(lib, "psacx_fm_occurrences_dev_" + suf).argtypes = [vp, vp, C.POINTER(FmInfo), vp, u64, vp, vp, u64, u64, vp, vp, vp, u64,
+                                                                    C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_fm_search_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64,
+                                                           C.POINTER(C.c_uint64)]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

@@ -1,6 +1,6 @@
-// Shared by the query command lines (locate, lce, overlaps, lz77, repeats, mems, kmismatch): the error rule, a wall clock, the readers of their
+// Shared by the query command lines (locate, lce, overlaps, lz77, repeats, mems, kmismatch, kedit, fmindex): the error rule, a wall clock, the readers of their
 // inputs, the --index choice, the owner of the ctx and the device memory of a run, and the u32 / u64 overload pairs of the calls that
-// more than one of them makes (construction, index, occurrences, the table over a text or a set, longest match, BWT, document counts and lists).  read_file is the one of bench_common.hpp.
+// more than one of them makes (construction, index, occurrences, the table over a text or a set, longest match, BWT, document counts and lists, the FM-index).  read_file is the one of bench_common.hpp.
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -57,6 +57,11 @@ struct Session {
     explicit Session(int device) : c(nullptr) { must(nullptr, psacx_create(&c, device, nullptr)); }
     ~Session() { for (std::size_t i = 0; i < held.size(); ++i) (void)psacx_dev_free(c, held[i]); psacx_destroy(c); }
     void* dev(uint64_t bytes) { void* p = nullptr; must(c, psacx_dev_alloc(c, &p, bytes ? bytes : 1)); held.push_back(p); return p; }
+    // gives one buffer back before the run ends (fmindex drops text and SA once its index stands)
+    void release(void* p) {
+        for (std::size_t i = 0; i < held.size(); ++i)
+            if (held[i] == p) { held.erase(held.begin() + i); (void)psacx_dev_free(c, p); return; }
+    }
 private:
     Session(const Session&);
     Session& operator=(const Session&);
@@ -104,6 +109,27 @@ inline int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends,
 }
 inline int bwt(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, uint8_t* b, uint32_t* f, uint64_t* p) {
     return psacx_bwt_dev_u64(c, t, n, ends, sa, b, f, p);
+}
+
+inline int fm_build(psacx_ctx* c, uint64_t n, const uint8_t* b, const uint32_t* f, const uint32_t* sa, uint64_t s, uint64_t* fm, psacx_fm_info* i) {
+    return psacx_fm_index_dev_u32(c, n, b, f, sa, s, fm, i);
+}
+inline int fm_build(psacx_ctx* c, uint64_t n, const uint8_t* b, const uint32_t* f, const uint64_t* sa, uint64_t s, uint64_t* fm, psacx_fm_info* i) {
+    return psacx_fm_index_dev_u64(c, n, b, f, sa, s, fm, i);
+}
+inline int fm_count(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t* lb, uint32_t* ub) {
+    return psacx_fm_count_dev_u32(c, fm, i, pat, poff, q, lb, ub);
+}
+inline int fm_count(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t* lb, uint64_t* ub) {
+    return psacx_fm_count_dev_u64(c, fm, i, pat, poff, q, lb, ub);
+}
+inline int fm_occurrences(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint64_t* off, uint64_t m, const uint32_t* lb, const uint32_t* ub,
+                          uint64_t q, uint64_t limit, uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total) {
+    return psacx_fm_occurrences_dev_u32(c, fm, i, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
+}
+inline int fm_occurrences(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint64_t* off, uint64_t m, const uint64_t* lb, const uint64_t* ub,
+                          uint64_t q, uint64_t limit, uint64_t* start, uint64_t* pos, uint64_t* sid, uint64_t cap, uint64_t* total) {
+    return psacx_fm_occurrences_dev_u64(c, fm, i, off, m, lb, ub, q, limit, start, pos, sid, cap, total);
 }
 
 // the range-minimum index of d_values, in memory of the session: the size query, then the build

@@ -1,4 +1,4 @@
-// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, kedit.hip, docs.hip, and check.hip and
+// query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, kedit.hip, docs.hip, fm.hip, and check.hip and
 // ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
 // that moves in one place alone does not compile.
 #pragma once
@@ -51,6 +51,18 @@ template <typename T>
 int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table, uint32_t k,
               const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t e, uint64_t max_cand, uint32_t flags,
               uint64_t* d_qid, T* d_tpos, T* d_len, uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
+
+// fm.hip: psacx_fm_index_dev_* (size query with d_fm == nullptr), psacx_fm_count_dev_* and psacx_fm_occurrences_dev_* themselves (kernels and
+// the layout of the blob in fm.hpp; all wait), instantiated there for both widths
+template <typename T>
+int fm_index_dev(psacx_ctx* c, uint64_t n, const uint8_t* d_bwt, const uint32_t* d_first, const T* d_SA, uint64_t sample, uint64_t* d_fm,
+                 psacx_fm_info* info);
+template <typename T>
+int fm_count_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb,
+                 T* d_ub);
+template <typename T>
+int fm_occurrences_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info, const uint64_t* d_off, uint64_t m, const T* d_lb, const T* d_ub,
+                       uint64_t q, uint64_t limit, uint64_t* d_start, T* d_pos, T* d_sid, uint64_t cap, uint64_t* total);
 
 // psacx_u32.hip / psacx_u64.hip: pair_sort_keys_dev of construct.hpp: n >= 1 pairs (b1, b2) sorted in place on their low `bits` bits by the
 // rank-pair sort, whose buffers it lays out from the base of the ctx slab; waits; leaves the statistics and the profiling state of the

@@ -1,7 +1,7 @@
 // staging.hpp -- device memory of a host-pointer call (psacx_locate_*, psacx_match_*, psacx_rmq_*, psacx_lce_*, psacx_overlaps_*,
-// psacx_lpf_*, psacx_lz77_*, psacx_bwt_*, psacx_repeats_*, psacx_mems_*, psacx_kmismatch_*, psacx_kedit_*, psacx_doc_count_*, psacx_doc_list_*) and of the device forms that need arrays for the time of a
+// psacx_lpf_*, psacx_lz77_*, psacx_bwt_*, psacx_repeats_*, psacx_mems_*, psacx_kmismatch_*, psacx_kedit_*, psacx_doc_count_*, psacx_doc_list_*, psacx_fm_search_*) and of the device forms that need arrays for the time of a
 // call (psacx_lpf_dev_*, psacx_repeats_dev_*: n entries; psacx_mems_dev_*: shell records and mark bytes; psacx_kmismatch_dev_*: piece
-// intervals and mark bytes; psacx_doc_index_dev_*: the key words; psacx_doc_list_dev_*: candidate starts and mark bytes): the arrays are staged in
+// intervals and mark bytes; psacx_doc_index_dev_*: the key words; psacx_doc_list_dev_*: candidate starts and mark bytes; psacx_fm_index_dev_*: two arrays of 16-bit codes): the arrays are staged in
 // memory of their own (the slab belongs to the device forms), and everything allocated is freed on every path.  rc is sticky: after
 // the first failure every later step does nothing.
 #pragma once

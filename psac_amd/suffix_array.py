@@ -288,6 +288,15 @@ class SuffixArray(object):
         keep = (docs >= min_docs) & ((docs <= max_docs) if max_docs else True)
         return lb[keep], ub[keep], ln[keep], docs[keep]
 
+    def fm_index(self, sample=32):
+        """The FMIndex of the text or string set of the last construct / construct_ss: fm_index() over its arrays.  The index owns its
+        memory in HBM alone and stays usable after this object, its text and its arrays are gone; sample=0 builds one that counts only."""
+        if getattr(self.ctx, "nranks", 1) != 1:
+            raise ValueError("fm_index needs a single-rank context (the index is built on one GPU)")
+        if getattr(self, "_text", None) is None or self._text.size != self.n or self.local_SA.size != self.n:
+            raise ValueError("fm_index needs construct or construct_ss first")
+        return fm_index(self._text, self.local_SA, sample=sample, offsets=self._text_off, ctx=self.ctx)
+
     def mems(self, patterns, min_len, k=0, max_occ=0, super=False):
         """(qpos, tpos, len) of the maximal exact matches of the patterns against the text or string set of the last construct /
         construct_ss (which needs lcp=True): mems() over its arrays."""
@@ -979,6 +988,205 @@ def doc_list(SA, offsets, lb, ub, max_cand=0, ctx=None):
     sid, pos = (np.zeros(max(1, total.value), sa.dtype) for _ in range(2))
     ctx.check(fn(*(head + [_ptr(sid), _ptr(pos), total.value, C.byref(total)])))
     return start, sid[:total.value], pos[:total.value]
+
+
+def fm_index_device(ctx, n, d_bwt, d_first, d_sa, sample, d_fm, index_bits):
+    """psacx_fm_index_dev_*: the FM-index of the text or string set whose BWT and first bitmap bwt_device left at d_bwt / d_first
+    (include/psacx.h: "FM-index"), into the 64-bit words at d_fm.  sample > 0 keeps SA[r] of every rank that starts a string or whose
+    position is a multiple of sample (d_sa is read only then); sample == 0 builds an index that counts only.  d_fm=None is the size
+    query.  Returns the descriptor (_lib.FmInfo: n, words, sample, marks, sigma, bits, code), which every query takes back."""
+    fn = getattr(ctx._lib, "psacx_fm_index_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    info = _lib.FmInfo()
+    ctx._pre()
+    ctx.check(fn(ctx.handle, int(n), opt(d_bwt), opt(d_first), opt(d_sa), int(sample), opt(d_fm), C.byref(info)))
+    return info
+
+
+def fm_count_device(ctx, d_fm, info, d_pat, d_poff, q, d_lb, d_ub, index_bits):
+    """psacx_fm_count_dev_*: backward search of q patterns (d_pat / d_poff as locate_device takes them) over the index at d_fm.  d_lb /
+    d_ub receive the interval of locate_device / locate_gsa_device for every pattern that occurs, and lb = ub = 0 (not locate's insertion
+    point) for one that does not."""
+    fn = getattr(ctx._lib, "psacx_fm_count_dev_u%d" % index_bits)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, opt(d_fm), C.byref(info), opt(d_pat), opt(d_poff), int(q), opt(d_lb), opt(d_ub)))
+
+
+def fm_occurrences_device(ctx, d_fm, info, d_off, m, d_lb, d_ub, q, limit, d_start, d_pos, d_sid, cap, index_bits):
+    """psacx_fm_occurrences_dev_*: occurrences_device without a suffix array: every position comes from the walk to a sampled rank of
+    the index at d_fm (built with sample > 0; PsacxError -1 otherwise).  d_pos=None is the size query.  Returns the total; raises
+    PsacxError -2 where it exceeds cap, with d_start valid, d_pos untouched and the total in the error's attribute total."""
+    fn = getattr(ctx._lib, "psacx_fm_occurrences_dev_u%d" % index_bits)
+    total = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, opt(d_fm), C.byref(info), opt(d_off), int(m), opt(d_lb), opt(d_ub), int(q), int(limit), opt(d_start), opt(d_pos),
+                     opt(d_sid), int(cap), C.byref(total)))
+    except PsacxError as e:
+        e.total = total.value
+        raise
+    return total.value
+
+
+def fm_search(text, SA, patterns, sample=32, limit=0, offsets=None, positions=True, ctx=None):
+    """psacx_fm_search_*: (lb, ub) of the patterns by backward search over an FM-index built for the call, and with positions=True
+    (lb, ub, start, pos) -- or (lb, ub, start, pos, sid) with offsets -- where the occurrences of pattern j are pos[start[j]:start[j + 1]]
+    = SA[lb[j]:ub[j]], at most limit of them where limit > 0.  A pattern that does not occur has lb = ub = 0.  Host arrays; everything is
+    staged for the call, and with positions the call runs twice: once to size the lists, once to fill them."""
+    t, sa = _text_bytes(text), np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("fm_search needs SA as uint32 or uint64")
+    if sa.size != t.size:
+        raise ValueError("SA must have one entry per byte of the text")
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    pat, off = pattern_buffer(patterns)
+    q = int(off.size - 1)
+    lb, ub = np.zeros(q, sa.dtype), np.zeros(q, sa.dtype)
+    ctx = ctx if ctx is not None else Context(0)
+    fn = getattr(ctx._lib, "psacx_fm_search_u%d" % (sa.dtype.itemsize * 8))
+    head = [ctx.handle, _ptr(t), t.size, _ptr(so) if so is not None else None, 0 if so is None else so.size - 1, _ptr(sa), int(sample),
+            _ptr(pat) if pat.size else None, _ptr(off), q, _ptr(lb), _ptr(ub), int(limit)]
+    ctx._pre()
+    if not positions:
+        ctx.check(fn(*(head + [None, None, None, 0, None])))
+        return lb, ub
+    start = np.zeros(q + 1, np.uint64)
+    total = C.c_uint64(0)
+    one = np.zeros(1, sa.dtype)
+    rc = fn(*(head + [_ptr(start), _ptr(one), None, 0, C.byref(total)]))
+    if rc != -2 or total.value == 0:
+        ctx.check(rc)
+    pos, sid = np.zeros(max(1, total.value), sa.dtype), np.zeros(max(1, total.value), sa.dtype)
+    if total.value:
+        ctx.check(fn(*(head + [_ptr(start), _ptr(pos), _ptr(sid) if so is not None else None, total.value, C.byref(total)])))
+    pos, sid = pos[:total.value], sid[:total.value]
+    return (lb, ub, start, pos) if so is None else (lb, ub, start, pos, sid)
+
+
+class FMIndex(object):
+    """An FM-index resident in HBM (SuffixArray.fm_index).  It owns the blob, its descriptor and, for a string set, the m + 1 string
+    offsets that name the string of a position; it needs neither the text nor the suffix array it was built from."""
+
+    def __init__(self, ctx, d_fm, info, index_bits, d_off=None, m=0):
+        self.ctx, self.d_fm, self.info, self.index_bits, self.d_off, self.m = ctx, d_fm, info, index_bits, d_off, m
+        self.dtype = np.uint32 if index_bits == 32 else np.uint64
+
+    @property
+    def nbytes(self):
+        return int(self.info.words) * 8
+
+    def _with(self, arrays, body):
+        held = []
+        try:
+            for a in arrays:
+                p = self.ctx.alloc(max(1, a.nbytes))
+                held.append(p)
+                if a.nbytes:
+                    self.ctx.h2d(p, a)
+            return body(*held)
+        finally:
+            for p in held:
+                self.ctx.free(p)
+
+    def count(self, patterns):
+        """(lb, ub): pattern j occurs ub[j] - lb[j] times, at the ranks [lb[j], ub[j]) of the suffix array; lb = ub = 0 where it does not."""
+        if self.d_fm is None:
+            raise ValueError("the index has been freed")
+        pat, off = pattern_buffer(patterns)
+        q = int(off.size - 1)
+        lb, ub = np.zeros(q, self.dtype), np.zeros(q, self.dtype)
+
+        def body(d_pat, d_poff, d_lb, d_ub):
+            fm_count_device(self.ctx, self.d_fm, self.info, d_pat, d_poff, q, d_lb, d_ub, self.index_bits)
+            if q:
+                self.ctx.d2h(lb, d_lb)
+                self.ctx.d2h(ub, d_ub)
+        self._with([pat, off, lb, ub], body)
+        return lb, ub
+
+    def locate(self, patterns, limit=0):
+        """(start, pos) -- (start, pos, sid) for a string set -- the occurrences of pattern j are pos[start[j]:start[j + 1]], in the order
+        of the suffix array, at most limit of them where limit > 0.  Needs an index built with sample > 0."""
+        lb, ub = self.count(patterns)
+        q = int(lb.size)
+        start = np.zeros(q + 1, np.uint64)
+        out = {}
+
+        def body(d_lb, d_ub, d_start):
+            args = (self.ctx, self.d_fm, self.info, self.d_off, self.m, d_lb, d_ub, q, limit, d_start)
+            total = fm_occurrences_device(*(args + (None, None, 0, self.index_bits)))
+            pos, sid = np.zeros(total, self.dtype), np.zeros(total, self.dtype)
+
+            def lists(d_pos, d_sid):
+                fm_occurrences_device(*(args + (d_pos, d_sid if self.d_off else None, total, self.index_bits)))
+                self.ctx.d2h(start, d_start)
+                if total:
+                    self.ctx.d2h(pos, d_pos)
+                    if self.d_off:
+                        self.ctx.d2h(sid, d_sid)
+            self._with([pos, sid], lists)
+            out["pos"], out["sid"] = pos, sid
+        self._with([lb, ub, start], body)
+        return (start, out["pos"], out["sid"]) if self.d_off else (start, out["pos"])
+
+    def free(self):
+        for name in ("d_fm", "d_off"):
+            p = getattr(self, name, None)
+            if p and getattr(self.ctx, "handle", None):
+                self.ctx.free(p)
+            setattr(self, name, None)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def fm_index(text, SA, sample=32, offsets=None, ctx=None):
+    """The FMIndex of a text (or, with offsets, a string set) and its suffix array: text and SA are staged, the bitmap of the string
+    ends, the BWT and the index are built in HBM, and everything but the index is freed again."""
+    t, sa = _text_bytes(text), np.ascontiguousarray(SA)
+    if sa.dtype not in (np.uint32, np.uint64):
+        raise TypeError("fm_index needs SA as uint32 or uint64")
+    if sa.size != t.size:
+        raise ValueError("SA must have one entry per byte of the text")
+    bits, n = sa.dtype.itemsize * 8, int(t.size)
+    so = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    m = 0 if so is None else int(so.size - 1)
+    ctx = ctx if ctx is not None else Context(0)
+    held, keep = [], {}
+
+    def put(arr=None, nbytes=0):
+        p = ctx.alloc(max(1, arr.nbytes if arr is not None else nbytes))
+        held.append(p)
+        if arr is not None and arr.nbytes:
+            ctx.h2d(p, arr)
+        return p
+    try:
+        d_text, d_sa = put(t), put(sa)
+        d_bwt, d_first = put(nbytes=n), put(nbytes=4 * ((n >> 5) + 1))
+        d_ends = None
+        if so is not None:
+            d_off = put(so)
+            d_ends = put(nbytes=4 * ((n >> 5) + 1))
+            string_ends_device(ctx, d_off, m, n, d_ends)
+            held.remove(d_off)
+            keep["off"] = d_off
+        bwt_device(ctx, d_text, n, d_ends, d_sa, d_bwt, d_first, bits, want_primary=False)
+        info = fm_index_device(ctx, n, d_bwt, d_first, d_sa if sample else None, sample, None, bits)
+        keep["fm"] = ctx.alloc(max(8, int(info.words) * 8))
+        info = fm_index_device(ctx, n, d_bwt, d_first, d_sa if sample else None, sample, keep["fm"], bits)
+    except Exception:
+        for p in keep.values():
+            ctx.free(p)
+        raise
+    finally:
+        for p in held:
+            ctx.free(p)
+    return FMIndex(ctx, keep["fm"], info, bits, keep.get("off"), m)
 
 
 MEMS_SUPER = _lib.PSACX_MEMS_SUPER
