@@ -1332,7 +1332,38 @@ int psacx_doc_list_u64(psacx_ctx* ctx, const uint64_t* SA, uint64_t n, const uin
  * psacx_fm_search_*: the host-pointer form.  It stages text and SA, builds the bitmap of the string ends (offsets == NULL: one text), the
  * BWT and the index, answers and frees what it allocated on every path.  lb / ub receive the intervals.  pos == NULL counts only (no
  * samples are built; start, sid, cap and total are not used).  With pos: start (q + 1 entries), total and sample > 0 are required,
- * *total > cap returns PSACX_ERANGE with lb, ub, start and *total valid. */
+ * *total > cap returns PSACX_ERANGE with lb, ub, start and *total valid.
+ *
+ * Text samples and extraction.  The blob replaces the suffix array; with the text samples beside it the index replaces the text too.
+ * The samples are a second array and the blob is what it was without them.  With a rate t >= 1 and blocks = n / t:
+ *     ts[k], k < blocks      = the rank of the suffix at position (k + 1) * t - 1 (the last position of block [k * t, (k + 1) * t));
+ *     ts[blocks + j], j < m  = the rank of the suffix at the last byte of string j,
+ * entries of the index type, blocks + max(m, 1) of them.  From the rank x of the suffix at position p the text to its left comes out
+ * under LF: S[p] is the symbol c with C[c] <= x < C[c + 1], and then S[p - 1] = w[x], x = LF(x), and so on.  w is STOP at the ranks of
+ * string starts, so a walk can not be entered from the next string: hence one sample per string end.
+ * psacx_fm_text_samples_dev_*: one streaming pass over d_SA.  d_offsets == NULL means one text: m is read as 1, its end is n - 1.
+ *  - d_ts == NULL is the size query: it sets *entries and reads nothing.  n == 0 is PSACX_OK and writes nothing.
+ *  - rate == 0, entries == NULL, or with n > 0 and d_ts: d_SA == NULL, m == 0 or m > n return PSACX_EINVAL; offsets that do not start at
+ *    0, end at n and ascend strictly return PSACX_EINVAL before anything is written (psacx_string_ends_dev); n beyond the index type
+ *    returns PSACX_ERANGE.
+ *  - An SA entry at or beyond n is skipped.  No input is written.  Scratch, for a string set only: the bitmap of the string ends in the
+ *    ctx slab.
+ * psacx_fm_extract_dev_*: query i asks for S[pos_i .. pos_i + len_i), clipped at the end of the string that holds pos_i; pos_i >= n
+ * gives length 0.  d_start receives q + 1 entries, the prefix sums of the clipped lengths, d_out[d_start[i] ..) the bytes.  The contract
+ * is that of psacx_fm_occurrences_dev_*: d_out == NULL is the size query; *total > cap returns PSACX_ERANGE with d_start and *total
+ * valid and d_out untouched; q == 0 is PSACX_OK.  d_ts, rate, d_offsets and m are those of psacx_fm_text_samples_dev_*.
+ *  - The descriptor is checked as by every query (PSACX_EINVAL); rate == 0, d_ts == NULL, or with q > 0 a NULL d_pos, d_len or d_start
+ *    return PSACX_EINVAL; so do malformed offsets, before anything is written.
+ *  - Work is balanced by output.  The unit is a segment, the part of one query's range inside one block [k * t, (k + 1) * t): a lane
+ *    starts at the sample of the block's last position, or at the end sample of its string where that comes first, takes the head symbol
+ *    from C and walks fewer than t LF steps to the left, storing the bytes whose position lies inside the query.  One query for a
+ *    whole text runs as wide as a million short ones.
+ *  - Scratch in the ctx slab: the block sums of the scans and q + 1 segment starts.
+ *  - Totality, whatever the blob and d_ts hold: every sample is clamped to n before use; every walk ends after fewer than min(t, n)
+ *    steps; nothing is read outside the `words` words of the blob or outside the `entries` entries of d_ts; nothing is written outside
+ *    d_out[0 .. *total); a segment whose sample is n or heads no symbol, or that meets STOP, a code beyond sigma or a rank of n early,
+ *    writes byte 0 for the positions it did not reach.  No input is written.
+ * There is no host-pointer psacx_fm_extract_*: a call that takes the text in order to return it has no user. */
 typedef struct psacx_fm_info {
     uint64_t n;            /* ranks */
     uint64_t words;        /* 64-bit words of the blob */
@@ -1356,6 +1387,16 @@ int psacx_fm_occurrences_dev_u32(psacx_ctx* ctx, const uint64_t* d_fm, const psa
 int psacx_fm_occurrences_dev_u64(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint64_t* d_offsets, uint64_t m,
                                  const uint64_t* d_lb, const uint64_t* d_ub, uint64_t q, uint64_t limit, uint64_t* d_start, uint64_t* d_pos,
                                  uint64_t* d_sid, uint64_t cap, uint64_t* total);
+int psacx_fm_text_samples_dev_u32(psacx_ctx* ctx, uint64_t n, const uint32_t* d_SA, const uint64_t* d_offsets, uint64_t m, uint64_t rate,
+                                  uint32_t* d_ts, uint64_t* entries);
+int psacx_fm_text_samples_dev_u64(psacx_ctx* ctx, uint64_t n, const uint64_t* d_SA, const uint64_t* d_offsets, uint64_t m, uint64_t rate,
+                                  uint64_t* d_ts, uint64_t* entries);
+int psacx_fm_extract_dev_u32(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint32_t* d_ts, uint64_t rate,
+                             const uint64_t* d_offsets, uint64_t m, const uint32_t* d_pos, const uint32_t* d_len, uint64_t q,
+                             uint64_t* d_start, uint8_t* d_out, uint64_t cap, uint64_t* total);
+int psacx_fm_extract_dev_u64(psacx_ctx* ctx, const uint64_t* d_fm, const psacx_fm_info* info, const uint64_t* d_ts, uint64_t rate,
+                             const uint64_t* d_offsets, uint64_t m, const uint64_t* d_pos, const uint64_t* d_len, uint64_t q,
+                             uint64_t* d_start, uint8_t* d_out, uint64_t cap, uint64_t* total);
 int psacx_fm_search_u32(psacx_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* offsets, uint64_t m, const uint32_t* SA,
                         uint64_t sample, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint32_t* lb, uint32_t* ub, uint64_t limit,
                         uint64_t* start, uint32_t* pos, uint32_t* sid, uint64_t cap, uint64_t* total);

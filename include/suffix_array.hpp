@@ -1358,6 +1358,9 @@ edit_lists<index_t> kedit(suffix_array<char, index_t, true, false>& sa, simple_d
 // but its blob, its descriptor, the string offsets and a context of its own on the device of `sa`: text and suffix array may go once it stands.
 // count: element i = [lb, ub) of patterns[i], the interval of locate where it occurs and (0, 0) where it does not.  locate: the
 // occurrence lists of occurrences(), from the sampled suffix array (sample > 0; sample == 0 builds an index that counts only).
+// With text_rate > 0 the index carries the text samples too and gives the bytes back: extract(pos, len) returns the slices
+// S[pos[i] .. pos[i] + len[i]) back to back, each clipped at the end of its string, with start[i] where slice i begins; text() the
+// strings of the set (one for a text).  Without text samples both throw.
 template <typename index_t>
 class fm_index {
     typedef typename std::conditional<sizeof(index_t) == 4, uint32_t, uint64_t>::type W;
@@ -1371,6 +1374,13 @@ class fm_index {
                        uint64_t* st, uint32_t* p, uint32_t* s, uint64_t cap, uint64_t* tot) { return psacx_fm_occurrences_dev_u32(c, fm, i, o, m, l, u, q, lim, st, p, s, cap, tot); }
     static int occ_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint64_t* o, uint64_t m, const uint64_t* l, const uint64_t* u, uint64_t q, uint64_t lim,
                        uint64_t* st, uint64_t* p, uint64_t* s, uint64_t cap, uint64_t* tot) { return psacx_fm_occurrences_dev_u64(c, fm, i, o, m, l, u, q, lim, st, p, s, cap, tot); }
+
+    static int ts_run(psacx_ctx* c, uint64_t n, const uint32_t* s, const uint64_t* o, uint64_t m, uint64_t r, uint32_t* ts, uint64_t* e) { return psacx_fm_text_samples_dev_u32(c, n, s, o, m, r, ts, e); }
+    static int ts_run(psacx_ctx* c, uint64_t n, const uint64_t* s, const uint64_t* o, uint64_t m, uint64_t r, uint64_t* ts, uint64_t* e) { return psacx_fm_text_samples_dev_u64(c, n, s, o, m, r, ts, e); }
+    static int ext_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint32_t* ts, uint64_t r, const uint64_t* o, uint64_t m, const uint32_t* p, const uint32_t* l,
+                       uint64_t q, uint64_t* st, uint8_t* out, uint64_t cap, uint64_t* tot) { return psacx_fm_extract_dev_u32(c, fm, i, ts, r, o, m, p, l, q, st, out, cap, tot); }
+    static int ext_run(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* i, const uint64_t* ts, uint64_t r, const uint64_t* o, uint64_t m, const uint64_t* p, const uint64_t* l,
+                       uint64_t q, uint64_t* st, uint8_t* out, uint64_t cap, uint64_t* tot) { return psacx_fm_extract_dev_u64(c, fm, i, ts, r, o, m, p, l, q, st, out, cap, tot); }
 
     struct held {                                                // device buffers that go on every path
         psacx_ctx* c; std::vector<void*> v;
@@ -1390,9 +1400,13 @@ class fm_index {
     uint64_t* d_off_;
     uint64_t m_;
     psacx_fm_info info_;
+    W* d_ts_;                                                    // the text samples (text_rate > 0)
+    uint64_t text_rate_, text_entries_;
+    std::vector<uint64_t> soff_;                                 // the offsets on the host: text() asks for every string by them
 
     template <bool LCP, bool LC>
-    void make(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff, std::size_t sample) {
+    void make(suffix_array<char, index_t, LCP, LC>& sa, const std::vector<uint8_t>& text, const std::vector<uint64_t>* soff, std::size_t sample,
+              std::size_t text_rate) {
         static_assert(sizeof(std::size_t) == 8, "size_t must be 64 bit");
         if (sa.multi_context()) throw std::runtime_error("psacx: fm_index needs a single-rank communicator (the index is built on one GPU)");
         if (sa.n == 0 || text.size() != sa.n || sa.local_SA.size() != sa.n) throw std::runtime_error("fm_index: text does not match the suffix array");
@@ -1421,11 +1435,20 @@ class fm_index {
         psacx::check(c_, psacx_dev_alloc(c_, &p, info_.words * 8));
         d_fm_ = (uint64_t*)p;
         psacx::check(c_, build(c_, n, d_bwt, d_first, sa_in, (uint64_t)sample, d_fm_, &info_));
+        if (soff) soff_ = *soff;
+        if (text_rate) {
+            text_rate_ = (uint64_t)text_rate;
+            psacx::check(c_, ts_run(c_, n, (const W*)0, d_off_, m_, text_rate_, (W*)0, &text_entries_));
+            psacx::check(c_, psacx_dev_alloc(c_, &p, text_entries_ * sizeof(W)));
+            d_ts_ = (W*)p;
+            psacx::check(c_, ts_run(c_, n, d_sa, d_off_, m_, text_rate_, d_ts_, &text_entries_));
+        }
     }
     void drop() {
         if (d_fm_) (void)psacx_dev_free(c_, d_fm_);
         if (d_off_) (void)psacx_dev_free(c_, d_off_);
-        d_fm_ = 0; d_off_ = 0;
+        if (d_ts_) (void)psacx_dev_free(c_, d_ts_);
+        d_fm_ = 0; d_off_ = 0; d_ts_ = 0;
         if (c_) psacx_destroy(c_);
         c_ = 0;
     }
@@ -1434,18 +1457,20 @@ class fm_index {
 
 public:
     template <bool LCP, bool LC, typename Iterator>
-    fm_index(suffix_array<char, index_t, LCP, LC>& sa, Iterator begin, Iterator end, std::size_t sample = 32) : c_(0), d_fm_(0), d_off_(0), m_(0) {
-        try { make(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, sample); } catch (...) { drop(); throw; }
+    fm_index(suffix_array<char, index_t, LCP, LC>& sa, Iterator begin, Iterator end, std::size_t sample = 32, std::size_t text_rate = 0)
+        : c_(0), d_fm_(0), d_off_(0), m_(0), d_ts_(0), text_rate_(0), text_entries_(0) {
+        try { make(sa, std::vector<uint8_t>(begin, end), (const std::vector<uint64_t>*)0, sample, text_rate); } catch (...) { drop(); throw; }
     }
     template <bool LCP>
-    fm_index(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, std::size_t sample = 32) : c_(0), d_fm_(0), d_off_(0), m_(0) {
+    fm_index(suffix_array<char, index_t, LCP, false>& sa, simple_dstringset& ss, std::size_t sample = 32, std::size_t text_rate = 0)
+        : c_(0), d_fm_(0), d_off_(0), m_(0), d_ts_(0), text_rate_(0), text_entries_(0) {
         std::vector<uint8_t> text; std::vector<uint64_t> soff;
         psacx::flatten_set(ss, text, soff);
-        try { make(sa, text, &soff, sample); } catch (...) { drop(); throw; }
+        try { make(sa, text, &soff, sample, text_rate); } catch (...) { drop(); throw; }
     }
     ~fm_index() { drop(); }
 
-    std::size_t bytes() const { return (std::size_t)info_.words * 8; }          // the index in HBM
+    std::size_t bytes() const { return (std::size_t)info_.words * 8 + (std::size_t)text_entries_ * sizeof(W); }          // the index in HBM, text samples included
     std::size_t size() const { return (std::size_t)info_.n; }
     const psacx_fm_info& info() const { return info_; }
 
@@ -1495,6 +1520,39 @@ public:
         if (total) psacx::check(c_, psacx_copy_d2h(c_, out.pos.data(), d_pos, total * sizeof(W)));
         if (total && d_off_) psacx::check(c_, psacx_copy_d2h(c_, out.sid.data(), d_sid, total * sizeof(W)));
         return out;
+    }
+
+    std::vector<uint8_t> extract(const std::vector<index_t>& pos, const std::vector<index_t>& len, std::vector<std::size_t>& start) const {
+        if (!d_ts_) throw std::runtime_error("fm_index: the index has no text samples (text_rate == 0)");
+        if (pos.size() != len.size()) throw std::runtime_error("fm_index: extract needs one length per position");
+        const uint64_t q = (uint64_t)pos.size();
+        std::vector<W> p(pos.begin(), pos.end()), l(len.begin(), len.end());
+        start.assign(q + 1, 0);
+        held h(c_);
+        const W* d_pos = (const W*)h.dev(p.data(), q * sizeof(W));
+        const W* d_len = (const W*)h.dev(l.data(), q * sizeof(W));
+        uint64_t* d_start = (uint64_t*)h.dev(0, (q + 1) * 8);
+        uint64_t total = 0;
+        psacx::check(c_, ext_run(c_, d_fm_, &info_, d_ts_, text_rate_, d_off_, m_, d_pos, d_len, q, d_start, (uint8_t*)0, 0, &total));
+        std::vector<uint8_t> out(total);
+        uint8_t* d_out = (uint8_t*)h.dev(0, total);
+        psacx::check(c_, ext_run(c_, d_fm_, &info_, d_ts_, text_rate_, d_off_, m_, d_pos, d_len, q, d_start, d_out, total, &total));
+        std::vector<uint64_t> st(q + 1, 0);
+        psacx::check(c_, psacx_copy_d2h(c_, st.data(), d_start, (q + 1) * 8));
+        start.assign(st.begin(), st.end());
+        if (total) psacx::check(c_, psacx_copy_d2h(c_, out.data(), d_out, total));
+        return out;
+    }
+
+    std::vector<std::string> text() const {
+        std::vector<index_t> pos, len;
+        if (soff_.empty()) { pos.push_back(0); len.push_back((index_t)info_.n); }
+        for (std::size_t j = 0; j + 1 < soff_.size(); ++j) { pos.push_back((index_t)soff_[j]); len.push_back((index_t)(soff_[j + 1] - soff_[j])); }
+        std::vector<std::size_t> start;
+        const std::vector<uint8_t> out = extract(pos, len, start);
+        std::vector<std::string> strings;
+        for (std::size_t j = 0; j + 1 < start.size(); ++j) strings.push_back(std::string(out.begin() + start[j], out.begin() + start[j + 1]));
+        return strings;
     }
 };
 

@@ -71,6 +71,7 @@ EXPORTS = [
     "psacx_doc_list_dev_u32", "psacx_doc_list_dev_u64", "psacx_doc_count_u32", "psacx_doc_count_u64", "psacx_doc_list_u32", "psacx_doc_list_u64",
     "psacx_fm_index_dev_u32", "psacx_fm_index_dev_u64", "psacx_fm_count_dev_u32", "psacx_fm_count_dev_u64",
     "psacx_fm_occurrences_dev_u32", "psacx_fm_occurrences_dev_u64", "psacx_fm_search_u32", "psacx_fm_search_u64",
+    "psacx_fm_text_samples_dev_u32", "psacx_fm_text_samples_dev_u64", "psacx_fm_extract_dev_u32", "psacx_fm_extract_dev_u64",
     "psacx_multi_create", "psacx_multi_unique_id", "psacx_multi_create_rank", "psacx_multi_destroy", "psacx_multi_nranks",
     "psacx_multi_nlocal", "psacx_multi_uses_rccl", "psacx_multi_last_error", "psacx_multi_ctx", "psacx_multi_construct_dev_u32",
     "psacx_multi_construct_dev_u64", "psacx_multi_construct_u32", "psacx_multi_construct_u64", "psacx_multi_get_stats",
@@ -212,6 +213,9 @@ def load():
                                                                     C.POINTER(C.c_uint64)]
         getattr(lib, "psacx_fm_search_" + suf).argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64,
                                                            C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_fm_text_samples_dev_" + suf).argtypes = [vp, u64, vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
+        getattr(lib, "psacx_fm_extract_dev_" + suf).argtypes = [vp, vp, C.POINTER(FmInfo), vp, u64, vp, u64, vp, vp, u64, vp, vp, u64,
+                                                                C.POINTER(C.c_uint64)]
     lib.psacx_string_ends_dev.argtypes = [vp, vp, u64, u64, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u32.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.psacx_check_dev_u64.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(C.c_uint64)]

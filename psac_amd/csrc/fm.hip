@@ -1,6 +1,7 @@
 // fm.hip -- the FM-index in HBM: psacx_fm_index_dev_* builds the blob from the outputs of psacx_bwt_dev_*, psacx_fm_count_dev_* is the
 // backward search, psacx_fm_occurrences_dev_* the occurrence lists through the sampled suffix array, psacx_fm_search_* the host-pointer
-// form (include/psacx.h: "FM-index"; kernels and the layout of the blob in fm.hpp).  The reference has no counterpart.
+// form; psacx_fm_text_samples_dev_* samples the ranks of text positions and psacx_fm_extract_dev_* gives the bytes of the text back from
+// them (include/psacx.h: "FM-index"; kernels and the layout of the blob in fm.hpp).  The reference has no counterpart.
 #include "engine.hpp"
 #include "fm.hpp"
 #include "search.hpp"
@@ -222,6 +223,99 @@ int fm_occurrences_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* 
     return PSACX_OK;
 }
 
+// the rate the kernels of the text samples work with, at most n + 1, and its shift (fm.hpp)
+static uint64_t fm_rate_of(uint64_t rate, uint64_t n, unsigned& shift) {
+    if (rate > n) rate = n + 1;
+    shift = 64;
+    if ((rate & (rate - 1)) == 0) { shift = 0; while ((1ull << shift) < rate) ++shift; }
+    return rate;
+}
+
+// psacx_fm_text_samples_dev_*: one pass over SA.  Scratch in the ctx slab, for a string set only: the word of the offsets' check at its
+// base (string_offsets_valid_dev) and behind it the bitmap of the string ends.
+template <typename T>
+int fm_text_samples_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const uint64_t* d_off, uint64_t m, uint64_t rate, T* d_ts, uint64_t* entries) {
+    if (!c || !entries || rate == 0) return PSACX_EINVAL;
+    PSACX_TRY(index_check_n<T>(n));
+    if (!d_off) m = 1;
+    *entries = n / rate + std::max<uint64_t>(m, 1);
+    if (n == 0 || !d_ts) return PSACX_OK;             // nothing to sample; the size query
+    if (!d_SA || m == 0 || m > n) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    uint32_t* d_ends = nullptr;
+    if (d_off) {
+        auto layout = [&](Arena& a) {
+            (void)a.take<unsigned char>(4096);
+            d_ends = a.take<uint32_t>((n >> 5) + 1);
+        };
+        { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
+        Arena ar(c->slab);
+        layout(ar);
+        PSACX_TRY(string_offsets_valid_dev(c, d_off, m, n));
+        PSACX_TRY(string_ends_bitmap_dev(c, d_off, m, n, d_ends));
+    }
+    unsigned shift;
+    const uint64_t blocks = n / rate, use = fm_rate_of(rate, n, shift);
+    hipLaunchKernelGGL((fm_text_samples_kernel<T>), dim3(grid_for(c, n, 256, 8)), dim3(256), 0, c->stream, n, d_SA, (const uint32_t*)d_ends, d_off, m, use,
+                       shift, blocks, d_ts);
+    PSACX_HIP(c, hipGetLastError());
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    return PSACX_OK;
+}
+
+// psacx_fm_extract_dev_*: the clipped lengths and the segment counts, their two scans, and the walk over tiles of segments.  Scratch in
+// the ctx slab: the block sums of the scans at its base (the word of the offsets' check before them), then the q + 1 segment starts.
+template <typename T>
+int fm_extract_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info, const T* d_ts, uint64_t rate, const uint64_t* d_off, uint64_t m,
+                   const T* d_pos, const T* d_len, uint64_t q, uint64_t* d_start, uint8_t* d_out, uint64_t cap, uint64_t* total) {
+    if (!c || !total) return PSACX_EINVAL;
+    *total = 0;
+    FmLayout Y;
+    CodeTable code;
+    PSACX_TRY(fm_view<T>(info, d_fm, Y, code));
+    if (rate == 0 || !d_ts) return PSACX_EINVAL;
+    if (!d_off) m = 1;
+    else if (Y.n && (m == 0 || m > Y.n)) return PSACX_EINVAL;
+    PSACX_HIP(c, hipSetDevice(c->device));
+    if (q == 0) {
+        if (d_start) { PSACX_HIP(c, hipMemsetAsync(d_start, 0, sizeof(uint64_t), c->stream)); PSACX_HIP(c, hipStreamSynchronize(c->stream)); }
+        return PSACX_OK;
+    }
+    if (!d_pos || !d_len || !d_start) return PSACX_EINVAL;
+    uint64_t* d_segs = nullptr;
+    auto layout = [&](Arena& a) {
+        (void)a.take<unsigned char>(std::max<uint64_t>(exclusive_scan_slab_bytes(q + 1), 4096));
+        d_segs = a.take<uint64_t>(q + 1);
+    };
+    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
+    Arena ar(c->slab);
+    layout(ar);
+    if (d_off && Y.n) PSACX_TRY(string_offsets_valid_dev(c, d_off, m, Y.n));
+    unsigned shift;
+    const uint64_t blocks = Y.n / rate, use = fm_rate_of(rate, Y.n, shift);
+    hipLaunchKernelGGL((fm_extract_counts_kernel<T>), dim3(grid_for(c, q + 1, 256, 8)), dim3(256), 0, c->stream, Y.n, d_off, m, use, shift, d_pos, d_len, q,
+                       d_start, d_segs);
+    PSACX_HIP(c, hipGetLastError());
+    PSACX_TRY(exclusive_scan_u64_dev(c, d_start, q + 1));
+    PSACX_TRY(exclusive_scan_u64_dev(c, d_segs, q + 1));
+    uint64_t nsegs = 0;
+    PSACX_HIP(c, hipMemcpyAsync(total, d_start + q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipMemcpyAsync(&nsegs, d_segs + q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (!d_out) return PSACX_OK;                      // size query
+    if (*total > cap) return PSACX_ERANGE;
+    if (*total == 0) return PSACX_OK;
+    FmDecode dec;
+    std::memset(&dec, 0, sizeof(dec));
+    for (int ch = 0; ch < 256; ++ch) if (info->code[ch]) dec.b[info->code[ch]] = (uint8_t)ch;
+    const uint64_t tiles = (nsegs + OCC_TILE - 1) / OCC_TILE;
+    hipLaunchKernelGGL((fm_extract_kernel<T>), dim3(grid_for(c, tiles * 256, 256, 8)), dim3(256), 0, c->stream, Y, dec, d_ts, blocks, use, shift, d_off, m,
+                       d_pos, q, (const uint64_t*)d_start, (const uint64_t*)d_segs, nsegs, d_out);
+    PSACX_HIP(c, hipGetLastError());
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    return PSACX_OK;
+}
+
 // psacx_fm_search_*: text and SA are staged, the bitmap of the string ends, the BWT and the index are built beside them, the patterns
 // are counted and, with pos, listed.  Everything allocated is freed on every path.  Without pos the index carries no samples.
 template <typename T>
@@ -296,6 +390,15 @@ extern "C" {
     int psacx_fm_occurrences_dev_##S(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* info, const uint64_t* off, uint64_t m, const T* lb, \
                                      const T* ub, uint64_t q, uint64_t limit, uint64_t* start, T* pos, T* sid, uint64_t cap, uint64_t* total) { \
         return fm_occurrences_dev<T>(c, fm, info, off, m, lb, ub, q, limit, start, pos, sid, cap, total);                                       \
+    }                                                                                                                                           \
+    int psacx_fm_text_samples_dev_##S(psacx_ctx* c, uint64_t n, const T* sa, const uint64_t* off, uint64_t m, uint64_t rate, T* ts,            \
+                                      uint64_t* entries) {                                                                                      \
+        return fm_text_samples_dev<T>(c, n, sa, off, m, rate, ts, entries);                                                                     \
+    }                                                                                                                                           \
+    int psacx_fm_extract_dev_##S(psacx_ctx* c, const uint64_t* fm, const psacx_fm_info* info, const T* ts, uint64_t rate, const uint64_t* off,  \
+                                 uint64_t m, const T* pos, const T* len, uint64_t q, uint64_t* start, uint8_t* out, uint64_t cap,               \
+                                 uint64_t* total) {                                                                                             \
+        return fm_extract_dev<T>(c, fm, info, ts, rate, off, m, pos, len, q, start, out, cap, total);                                           \
     }                                                                                                                                           \
     int psacx_fm_search_##S(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* off, uint64_t m, const T* sa, uint64_t sample,       \
                             const uint8_t* pat, const uint64_t* poff, uint64_t q, T* lb, T* ub, uint64_t limit, uint64_t* start, T* pos,        \

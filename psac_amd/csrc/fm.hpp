@@ -1,7 +1,8 @@
 // fm.hpp -- the FM-index of a text or a string set, resident in HBM as one array of 64-bit words: a binary wavelet matrix over the
 // BWT with a STOP symbol, its per-symbol tables, and a sampled suffix array (include/psacx.h: "FM-index").  Backward search counts a
-// pattern without text or SA; the LF walk to a sampled rank gives its positions.  The reference has no counterpart; kernels only, the
-// calls are in fm.hip.
+// pattern without text or SA; the LF walk to a sampled rank gives its positions; the LF walk from the sampled rank of a text position
+// gives the bytes to its left (text samples, at the end of this file).  The reference has no counterpart; kernels only, the calls are in
+// fm.hip.
 //
 // Symbols.  w[r] = 0 (STOP) where first[r], else code[bwt[r]], codes 1 .. sigma in byte order; bits = ceil(log2(sigma + 1)), 1 .. 9.
 //
@@ -241,6 +242,23 @@ __global__ __launch_bounds__(256) void fm_count_kernel(FmLayout Y, CodeTable cod
     }
 }
 
+// The descent that reads the symbol at rank r < n and its rank together: the code w[r], bit by bit from the cells, and in at_r where r
+// stands behind the last level, so that LF(r) = at_r + D[code].  Every position is clamped to n before it selects a cell.
+__device__ __forceinline__ unsigned fm_symbol_rank(const FmLayout& Y, const uint64_t* s_tab, uint64_t r, uint64_t& at_r) {
+    const uint64_t n = Y.n;
+    unsigned c = 0;
+    at_r = r;
+    for (unsigned l = 0; l < Y.bits; ++l) {
+        const ulonglong2 cl = fm_cell(Y, 2 * Y.cells * l, at_r);
+        const uint64_t rk = fm_rank1(cl, at_r);
+        const unsigned bit = (unsigned)((cl.y >> (at_r & 63)) & 1ull);
+        c = (c << 1) | bit;
+        at_r = bit ? s_tab[FM_TAB_Z + l] + rk : at_r - rk;
+        at_r = at_r < n ? at_r : n;
+    }
+    return c;
+}
+
 // The functor of occ_tile_walk for the occurrence lists of an FM-index: slot o of interval x is rank r = lb[x] + (o - first); the walk
 // tests r's mark, and where it is clear reads the symbol at r and its rank in one descent and steps to LF(r).  pos[o] = val + steps, or
 // all ones where no mark came up within min(sample, n) steps (no intact index does that); sid[o] as in occ_expand_kernel.
@@ -265,16 +283,8 @@ struct FmWalk {
                 if (at < Y.marks) p = (T)((uint64_t)val[at] + steps);
                 break;
             }
-            unsigned c = 0;
-            uint64_t at_r = r;
-            for (unsigned l = 0; l < Y.bits; ++l) {
-                const ulonglong2 cl = fm_cell(Y, 2 * Y.cells * l, at_r);
-                const uint64_t rk = fm_rank1(cl, at_r);
-                const unsigned bit = (unsigned)((cl.y >> (at_r & 63)) & 1ull);
-                c = (c << 1) | bit;
-                at_r = bit ? s_tab[FM_TAB_Z + l] + rk : at_r - rk;
-                at_r = at_r < n ? at_r : n;
-            }
+            uint64_t at_r;
+            const unsigned c = fm_symbol_rank(Y, s_tab, r, at_r);
             if (c == 0 || c > Y.sigma) break;           // (STOP: the rank starts a string and is marked in an intact index)
             r = at_r + s_tab[FM_TAB_D + c];
         }
@@ -295,6 +305,129 @@ __global__ __launch_bounds__(256) void fm_occ_kernel(FmLayout Y, const uint64_t*
     for (uint64_t o0 = (uint64_t)blockIdx.x * OCC_TILE; o0 < total; o0 += (uint64_t)gridDim.x * OCC_TILE) {
         const uint64_t o1 = o0 + OCC_TILE < total ? o0 + OCC_TILE : total;
         occ_tile_walk(start, q, o0, o1, s_start, walk);
+    }
+}
+
+// ---- text samples and extraction (include/psacx.h: "FM-index", text samples) ----
+//
+// ts[k] = the rank of the suffix at position (k + 1) * rate - 1, k < blocks = n / rate; ts[blocks + j] = the rank of the suffix at the
+// last byte of string j.  From the sample at the right end of a block, or at its string's end where that comes first, the bytes to the
+// left come out under LF: the head symbol of the sampled rank from C, every further byte from the descent at the rank.  STOP stands at the
+// ranks of string starts, so no walk leaves its string, and no walk can be entered from the next one: hence the end samples.
+//
+// The calls hand the kernels a rate of at most n + 1 (every rate above n gives blocks = 0 and one block for all positions, as n + 1
+// does), so that (k + 1) * rate does not wrap; shift = log2(rate) where rate is a power of two, else 64.
+
+__device__ __forceinline__ uint64_t fm_block_of(uint64_t p, uint64_t rate, unsigned shift) { return shift < 64 ? p >> shift : p / rate; }
+
+struct FmDecode { uint8_t b[FM_SYMS]; };               // code -> byte, from the descriptor; b[0] = 0
+
+// One pass over the ranks: r goes to the slot of SA[r] where SA[r] + 1 is a multiple of rate, and to the end slot of its string where
+// SA[r] + 1 ends one (ends: the bitmap of the string ends; nullptr for one text, whose end is n).  An SA entry at or beyond n is skipped.
+// With 32-bit entries the division is one of 32 bits (rate <= n + 1 and SA[r] + 1 <= n, both below 2^32).
+template <typename T>
+__global__ __launch_bounds__(256) void fm_text_samples_kernel(uint64_t n, const T* __restrict__ SA, const uint32_t* __restrict__ ends,
+                                                              const uint64_t* __restrict__ off, uint64_t m, uint64_t rate, unsigned shift,
+                                                              uint64_t blocks, T* __restrict__ ts) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
+        const uint64_t p = (uint64_t)SA[r];
+        if (p >= n) continue;
+        const uint64_t e = p + 1;
+        const uint64_t k = shift < 64 ? e >> shift : sizeof(T) == 4 ? (uint64_t)((uint32_t)e / (uint32_t)rate) : e / rate;
+        if (k * rate == e && k - 1 < blocks) ts[k - 1] = (T)r;                                     // (k >= 1 here: e >= 1)
+        if (ends ? fm_bit(ends, e) : e == n) ts[blocks + (off ? occ_last_le(off, m, p) : 0)] = (T)r;
+    }
+}
+
+// start[j] = the length of query j clipped at the end of the string that holds pos[j] (0 for a pos at or beyond n), segs[j] = the
+// rate-aligned blocks its range meets; start[q] = segs[q] = 0.  off: valid offsets, or nullptr for one text.
+template <typename T>
+__global__ __launch_bounds__(256) void fm_extract_counts_kernel(uint64_t n, const uint64_t* __restrict__ off, uint64_t m, uint64_t rate, unsigned shift,
+                                                                const T* __restrict__ pos, const T* __restrict__ len, uint64_t q,
+                                                                uint64_t* __restrict__ start, uint64_t* __restrict__ segs) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= q; j += stride) {
+        uint64_t cl = 0, sg = 0;
+        if (j < q) {
+            const uint64_t a = (uint64_t)pos[j], l = (uint64_t)len[j];
+            if (a < n) {
+                uint64_t e = off ? off[occ_last_le(off, m, a) + 1] : n;
+                e = e < n ? e : n;
+                if (e > a) cl = l < e - a ? l : e - a;
+                if (cl) sg = fm_block_of(a + cl - 1, rate, shift) - fm_block_of(a, rate, shift) + 1;
+            }
+        }
+        start[j] = cl;
+        segs[j] = sg;
+    }
+}
+
+// The functor of occ_tile_walk for the extraction: slot o is segment o - first of query x, the part of [a, b) = [pos[x], pos[x] +
+// clipped length) inside block k = a / rate + (o - first).  The lane starts at the sample of position P = min((k + 1) * rate, e) - 1, e
+// the end of the string of a; the sample is clamped to n; the head symbol of that rank is the last c <= sigma with C[c] <= rank, by a
+// search of the table in LDS; then it steps P - lo < min(rate, n) times to the left, lo = max(a, k * rate), and stores the bytes whose
+// position lies below hi = min(b, (k + 1) * rate).  A sample of n, a head symbol 0, STOP, a code beyond sigma or a rank of n ends the
+// walk: the positions not reached get byte 0.  Slot and sample index stay inside by construction: k < blocks where (k + 1) * rate <= e
+// <= n, the string of a is below max(m, 1), and out[start[x] + (p - a)] with p < b lies below start[x + 1].
+template <typename T>
+struct FmExtract {
+    FmLayout Y;
+    const uint64_t* s_tab;
+    const uint8_t* s_dec;
+    const T* __restrict__ ts;
+    uint64_t blocks, rate;
+    unsigned shift;
+    const uint64_t* __restrict__ off;
+    uint64_t m;
+    const T* __restrict__ pos;
+    const uint64_t* __restrict__ start;
+    uint8_t* __restrict__ out;
+    __device__ __forceinline__ void operator()(uint64_t o, uint64_t x, uint64_t first) const {
+        const uint64_t n = Y.n, a = (uint64_t)pos[x], base = start[x], b = a + (start[x + 1] - base);
+        if (a >= n || b > n || b <= a) return;          // (not with the starts this call has scanned)
+        const uint64_t k = fm_block_of(a, rate, shift) + (o - first);
+        const uint64_t s = off ? occ_last_le(off, m, a) : 0;
+        uint64_t e = off ? off[s + 1] : n;
+        e = e < n ? e : n;
+        const uint64_t blo = k * rate, bhi = blo + rate;
+        const uint64_t lo = a > blo ? a : blo, hi = b < bhi ? b : bhi;
+        if (blo >= b || e < b) return;                  // (the same)
+        const bool inner = bhi <= e;
+        const uint64_t P = (inner ? bhi : e) - 1;
+        uint64_t r = (uint64_t)ts[inner ? k : blocks + s];
+        r = r < n ? r : n;
+        unsigned c = r < n ? (unsigned)occ_last_le(s_tab + FM_TAB_C, (uint64_t)Y.sigma + 1, r) : 0u;
+        bool live = c != 0;
+        for (uint64_t p = P;; --p) {
+            if (p < hi) out[base + (p - a)] = live ? s_dec[c] : (uint8_t)0;
+            if (p == lo) break;
+            if (live) {
+                uint64_t at_r;
+                c = fm_symbol_rank(Y, s_tab, r, at_r);
+                live = c != 0 && c <= Y.sigma;
+                if (live) { r = at_r + s_tab[FM_TAB_D + c]; live = r < n; }
+            }
+        }
+    }
+};
+
+// out[start_x + t] = S[pos_x + t] for every query x and t below its clipped length; tiles of segments as fm_occ_kernel has tiles of slots
+template <typename T>
+__global__ __launch_bounds__(256) void fm_extract_kernel(FmLayout Y, FmDecode dec, const T* __restrict__ ts, uint64_t blocks, uint64_t rate, unsigned shift,
+                                                         const uint64_t* __restrict__ off, uint64_t m, const T* __restrict__ pos, uint64_t q,
+                                                         const uint64_t* __restrict__ start, const uint64_t* __restrict__ segs, uint64_t nsegs,
+                                                         uint8_t* __restrict__ out) {
+    __shared__ uint64_t s_seg[OCC_CHUNK + 1];
+    __shared__ uint64_t s_tab[FM_TAB_WORDS];
+    __shared__ uint8_t s_dec[FM_SYMS];
+    for (uint64_t i = threadIdx.x; i < FM_TAB_WORDS; i += blockDim.x) s_tab[i] = Y.fm[Y.tab + i];
+    for (uint64_t i = threadIdx.x; i < FM_SYMS; i += blockDim.x) s_dec[i] = dec.b[i];
+    __syncthreads();
+    const FmExtract<T> walk{Y, s_tab, s_dec, ts, blocks, rate, shift, off, m, pos, start, out};
+    for (uint64_t o0 = (uint64_t)blockIdx.x * OCC_TILE; o0 < nsegs; o0 += (uint64_t)gridDim.x * OCC_TILE) {
+        const uint64_t o1 = o0 + OCC_TILE < nsegs ? o0 + OCC_TILE : nsegs;
+        occ_tile_walk(segs, q, o0, o1, s_seg, walk);
     }
 }
 

@@ -63,6 +63,12 @@ int fm_count_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info, 
 template <typename T>
 int fm_occurrences_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info, const uint64_t* d_off, uint64_t m, const T* d_lb, const T* d_ub,
                        uint64_t q, uint64_t limit, uint64_t* d_start, T* d_pos, T* d_sid, uint64_t cap, uint64_t* total);
+// fm.hip: psacx_fm_text_samples_dev_* (size query with d_ts == nullptr) and psacx_fm_extract_dev_* themselves (both wait)
+template <typename T>
+int fm_text_samples_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const uint64_t* d_off, uint64_t m, uint64_t rate, T* d_ts, uint64_t* entries);
+template <typename T>
+int fm_extract_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info, const T* d_ts, uint64_t rate, const uint64_t* d_off, uint64_t m,
+                   const T* d_pos, const T* d_len, uint64_t q, uint64_t* d_start, uint8_t* d_out, uint64_t cap, uint64_t* total);
 
 // psacx_u32.hip / psacx_u64.hip: pair_sort_keys_dev of construct.hpp: n >= 1 pairs (b1, b2) sorted in place on their low `bits` bits by the
 // rank-pair sort, whose buffers it lays out from the base of the ctx slab; waits; leaves the statistics and the profiling state of the

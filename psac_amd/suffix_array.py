@@ -288,14 +288,15 @@ class SuffixArray(object):
         keep = (docs >= min_docs) & ((docs <= max_docs) if max_docs else True)
         return lb[keep], ub[keep], ln[keep], docs[keep]
 
-    def fm_index(self, sample=32):
+    def fm_index(self, sample=32, text_rate=0):
         """The FMIndex of the text or string set of the last construct / construct_ss: fm_index() over its arrays.  The index owns its
-        memory in HBM alone and stays usable after this object, its text and its arrays are gone; sample=0 builds one that counts only."""
+        memory in HBM alone and stays usable after this object, its text and its arrays are gone; sample=0 builds one that counts only; text_rate > 0 adds the text samples, with which the index gives the
+        text back (FMIndex.extract, .text, .context)."""
         if getattr(self.ctx, "nranks", 1) != 1:
             raise ValueError("fm_index needs a single-rank context (the index is built on one GPU)")
         if getattr(self, "_text", None) is None or self._text.size != self.n or self.local_SA.size != self.n:
             raise ValueError("fm_index needs construct or construct_ss first")
-        return fm_index(self._text, self.local_SA, sample=sample, offsets=self._text_off, ctx=self.ctx)
+        return fm_index(self._text, self.local_SA, sample=sample, offsets=self._text_off, ctx=self.ctx, text_rate=text_rate)
 
     def mems(self, patterns, min_len, k=0, max_occ=0, super=False):
         """(qpos, tpos, len) of the maximal exact matches of the patterns against the text or string set of the last construct /
@@ -1030,6 +1031,36 @@ def fm_occurrences_device(ctx, d_fm, info, d_off, m, d_lb, d_ub, q, limit, d_sta
     return total.value
 
 
+def fm_text_samples_device(ctx, n, d_sa, d_off, m, rate, d_ts, index_bits):
+    """psacx_fm_text_samples_dev_*: the text samples of an FM-index from the suffix array at d_sa: d_ts[k] = the rank of the suffix at
+    position (k + 1) * rate - 1 for k < n // rate, and behind them the rank of the suffix at the last byte of every string (d_off: its
+    m + 1 offsets; None for one text).  d_ts=None is the size query.  Returns the number of entries, n // rate + max(m, 1)."""
+    fn = getattr(ctx._lib, "psacx_fm_text_samples_dev_u%d" % index_bits)
+    entries = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    ctx.check(fn(ctx.handle, int(n), opt(d_sa), opt(d_off), int(m), int(rate), opt(d_ts), C.byref(entries)))
+    return entries.value
+
+
+def fm_extract_device(ctx, d_fm, info, d_ts, rate, d_off, m, d_pos, d_len, q, d_start, d_out, cap, index_bits):
+    """psacx_fm_extract_dev_*: the bytes S[pos .. pos + len) of q queries, each clipped at the end of its string, from the index at
+    d_fm and the text samples at d_ts (fm_text_samples_device, with the same rate, d_off and m).  d_start receives the q + 1 prefix
+    sums of the clipped lengths, d_out the bytes; d_out=None is the size query.  Returns the total; raises PsacxError -2 where it
+    exceeds cap, with d_start valid, d_out untouched and the total in the error's attribute total."""
+    fn = getattr(ctx._lib, "psacx_fm_extract_dev_u%d" % index_bits)
+    total = C.c_uint64(0)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx._pre()
+    try:
+        ctx.check(fn(ctx.handle, opt(d_fm), C.byref(info), opt(d_ts), int(rate), opt(d_off), int(m), opt(d_pos), opt(d_len), int(q),
+                     opt(d_start), opt(d_out), int(cap), C.byref(total)))
+    except PsacxError as e:
+        e.total = total.value
+        raise
+    return total.value
+
+
 def fm_search(text, SA, patterns, sample=32, limit=0, offsets=None, positions=True, ctx=None):
     """psacx_fm_search_*: (lb, ub) of the patterns by backward search over an FM-index built for the call, and with positions=True
     (lb, ub, start, pos) -- or (lb, ub, start, pos, sid) with offsets -- where the occurrences of pattern j are pos[start[j]:start[j + 1]]
@@ -1067,15 +1098,18 @@ def fm_search(text, SA, patterns, sample=32, limit=0, offsets=None, positions=Tr
 
 class FMIndex(object):
     """An FM-index resident in HBM (SuffixArray.fm_index).  It owns the blob, its descriptor and, for a string set, the m + 1 string
-    offsets that name the string of a position; it needs neither the text nor the suffix array it was built from."""
+    offsets that name the string of a position; it needs neither the text nor the suffix array it was built from.  Built with
+    text_rate > 0 it owns the text samples too (nbytes counts them) and gives the bytes back: extract, text, context."""
 
-    def __init__(self, ctx, d_fm, info, index_bits, d_off=None, m=0):
+    def __init__(self, ctx, d_fm, info, index_bits, d_off=None, m=0, d_ts=None, text_rate=0, text_entries=0, offsets=None):
         self.ctx, self.d_fm, self.info, self.index_bits, self.d_off, self.m = ctx, d_fm, info, index_bits, d_off, m
         self.dtype = np.uint32 if index_bits == 32 else np.uint64
+        self.d_ts, self.text_rate, self.text_entries = d_ts, int(text_rate), int(text_entries)
+        self.offsets = None if offsets is None else np.array(offsets, dtype=np.uint64)          # (host copy: text() names the strings by it)
 
     @property
     def nbytes(self):
-        return int(self.info.words) * 8
+        return int(self.info.words) * 8 + self.text_entries * (self.index_bits // 8)
 
     def _with(self, arrays, body):
         held = []
@@ -1131,8 +1165,61 @@ class FMIndex(object):
         self._with([lb, ub, start], body)
         return (start, out["pos"], out["sid"]) if self.d_off else (start, out["pos"])
 
+    def extract(self, pos, length):
+        """(start, bytes): query i is the bytes S[pos[i] .. pos[i] + length[i]) clipped at the end of the string that holds pos[i]
+        (nothing for a pos at or beyond n); they are bytes[start[i]:start[i + 1]], a uint8 array.  length may be one number for all.
+        Needs an index built with text_rate > 0."""
+        if self.d_fm is None:
+            raise ValueError("the index has been freed")
+        if not self.d_ts:
+            raise ValueError("the index has no text samples (build it with text_rate > 0)")
+        p = np.ascontiguousarray(np.atleast_1d(pos), dtype=self.dtype)
+        ln = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(length), p.shape), dtype=self.dtype)
+        q = int(p.size)
+        start = np.zeros(q + 1, np.uint64)
+        got = {}
+
+        def body(d_pos, d_len, d_start):
+            args = (self.ctx, self.d_fm, self.info, self.d_ts, self.text_rate, self.d_off, self.m, d_pos, d_len, q, d_start)
+            total = fm_extract_device(*(args + (None, 0, self.index_bits)))
+            out = np.zeros(total, np.uint8)
+
+            def fill(d_out):
+                fm_extract_device(*(args + (d_out, total, self.index_bits)))
+                self.ctx.d2h(start, d_start)
+                if total:
+                    self.ctx.d2h(out, d_out)
+            self._with([out], fill)
+            got["out"] = out
+        self._with([p, ln, start], body)
+        return start, got["out"]
+
+    def text(self):
+        """The whole text back from the index, as bytes; for a string set the list of its strings."""
+        n = int(self.info.n)
+        if self.offsets is None:
+            return self.extract([0], [n])[1].tobytes()
+        start, out = self.extract(self.offsets[:-1], np.diff(self.offsets))
+        return [out[int(start[j]):int(start[j + 1])].tobytes() for j in range(self.m)]
+
+    def context(self, patterns, width, limit=0):
+        """locate(patterns, limit), then the window [pos - width, pos + len(pattern) + width) of every occurrence, clipped to its
+        string: (start, pos, wstart, bytes) -- (start, pos, sid, wstart, bytes) for a string set -- where the window of occurrence o is
+        bytes[wstart[o]:wstart[o + 1]]."""
+        if not self.d_ts:
+            raise ValueError("the index has no text samples (build it with text_rate > 0)")
+        res = self.locate(patterns, limit)
+        start, pos = res[0], res[1].astype(np.int64)
+        lens = np.repeat(np.array([len(bytes(P)) for P in patterns], np.int64), np.diff(start.astype(np.int64)))
+        lo = np.zeros(pos.size, np.int64)
+        if self.offsets is not None and pos.size:
+            lo = self.offsets.astype(np.int64)[res[2].astype(np.int64)]
+        a = np.maximum(lo, pos - int(width))
+        wstart, out = self.extract(a, pos + lens + int(width) - a)
+        return tuple(res) + (wstart, out)
+
     def free(self):
-        for name in ("d_fm", "d_off"):
+        for name in ("d_fm", "d_off", "d_ts"):
             p = getattr(self, name, None)
             if p and getattr(self.ctx, "handle", None):
                 self.ctx.free(p)
@@ -1145,9 +1232,10 @@ class FMIndex(object):
             pass
 
 
-def fm_index(text, SA, sample=32, offsets=None, ctx=None):
+def fm_index(text, SA, sample=32, offsets=None, ctx=None, text_rate=0):
     """The FMIndex of a text (or, with offsets, a string set) and its suffix array: text and SA are staged, the bitmap of the string
-    ends, the BWT and the index are built in HBM, and everything but the index is freed again."""
+    ends, the BWT and the index are built in HBM, and everything but the index is freed again.  text_rate > 0 builds the text samples
+    beside it (one rank per text_rate positions and one per string), which extract / text / context need."""
     t, sa = _text_bytes(text), np.ascontiguousarray(SA)
     if sa.dtype not in (np.uint32, np.uint64):
         raise TypeError("fm_index needs SA as uint32 or uint64")
@@ -1179,6 +1267,11 @@ def fm_index(text, SA, sample=32, offsets=None, ctx=None):
         info = fm_index_device(ctx, n, d_bwt, d_first, d_sa if sample else None, sample, None, bits)
         keep["fm"] = ctx.alloc(max(8, int(info.words) * 8))
         info = fm_index_device(ctx, n, d_bwt, d_first, d_sa if sample else None, sample, keep["fm"], bits)
+        entries = 0
+        if text_rate:
+            entries = fm_text_samples_device(ctx, n, None, keep.get("off"), m, text_rate, None, bits)
+            keep["ts"] = ctx.alloc(max(8, entries * (bits // 8)))
+            fm_text_samples_device(ctx, n, d_sa, keep.get("off"), m, text_rate, keep["ts"], bits)
     except Exception:
         for p in keep.values():
             ctx.free(p)
@@ -1186,7 +1279,7 @@ def fm_index(text, SA, sample=32, offsets=None, ctx=None):
     finally:
         for p in held:
             ctx.free(p)
-    return FMIndex(ctx, keep["fm"], info, bits, keep.get("off"), m)
+    return FMIndex(ctx, keep["fm"], info, bits, keep.get("off"), m, keep.get("ts"), text_rate, entries, so)
 
 
 MEMS_SUPER = _lib.PSACX_MEMS_SUPER
