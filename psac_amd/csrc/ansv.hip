@@ -47,9 +47,7 @@ int ansv_run(psacx_ctx* c, const T* in, uint64_t n, int lt, int rt, uint64_t non
         else { d_in = a.take<T>(n); d_l = a.take<uint64_t>(n); d_r = a.take<uint64_t>(n); }
         nsv_pyramid_layout<T>(a, d_in, n, P);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     if (!dev) PSACX_HIP(c, hipMemcpyAsync(d_in, in, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     ProfScope* ps = new ProfScope(c, TC_TOTAL);
     for (int L = 1; L < P.nlev; ++L) {
@@ -181,9 +179,7 @@ int suffix_tree_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const T* sa,
         uint64_t len = n;
         while (len > 64 && P.nlev < PYR_MAX) { len = (len + 63) / 64; P.lvl[P.nlev] = a.take<T>(len); P.len[P.nlev] = len; P.nlev++; }
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     PSACX_HIP(c, hipMemcpyAsync(d_lcp, lcp, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     PSACX_HIP(c, hipMemcpyAsync(d_sa, sa, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     PSACX_HIP(c, hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream));
@@ -219,9 +215,7 @@ int suffix_tree_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_
         d_ln = a.take<uint64_t>(n); d_rn = a.take<uint64_t>(n);
         nsv_pyramid_layout<T>(a, d_lcp, n, P);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     CodeTable tab;
     PSACX_TRY(tree_alphabet_dev(c, d_text, n, d_hist, tab, *sigma));
     if (!d_nodes) return PSACX_OK;                    // size query
@@ -275,9 +269,7 @@ int suffix_tree_gsa_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const u
         if (lcp0 != 0) lcp_copy = a.take<T>(n);
         nsv_pyramid_layout<T>(a, lcp_copy ? lcp_copy : d_lcp, n, P);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     CodeTable tab;
     PSACX_TRY(tree_alphabet_dev(c, d_text, n, d_hist, tab, *sigma));
     if (!d_nodes) return PSACX_OK;                    // size query

@@ -380,9 +380,7 @@ int check_suffix_tree_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, const T
         d = a.take<unsigned long long>(256 + 4);
         nsv_pyramid_layout<T>(a, lcp, n, P);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     CodeTable tab;
     uint32_t sigma = 0;
     PSACX_TRY(tree_alphabet_dev(c, text, n, d, tab, sigma));
@@ -426,9 +424,7 @@ int check_suffix_tree_gsa_dev(psacx_ctx* c, const uint8_t* text, uint64_t n, con
         bits = a.take<uint32_t>((n >> 5) + 1);
         nsv_pyramid_layout<T>(a, lcp, n, P);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     CodeTable tab;
     uint32_t sigma = 0;
     PSACX_TRY(tree_alphabet_dev(c, text, n, d, tab, sigma));

@@ -253,9 +253,7 @@ int op_split_by(psacx_ctx* c, const T* k1, const T* k2, const T* v, uint64_t n, 
     SortScratch sc;
     T* cls = nullptr;
     auto layout = [&](Arena& a) { cls = a.take<T>(n); sc.take(a, n, /*base_desc_only=*/true); };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     Splitters sp;
     sp.n = nsplit;
     for (uint32_t i = 0; i < nsplit; ++i) { sp.k1[i] = sk1[i]; sp.k2[i] = sk2[i]; sp.rank[i] = srank[i]; sp.idx[i] = sidx[i]; }
@@ -510,9 +508,7 @@ int build_block_pyramid(psacx_ctx* c, const T* block, uint64_t m, Pyramid<T>& P,
         unsigned long long* sc = a.take<unsigned long long>(8);
         if (scalar) *scalar = sc;
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     for (int L = 1; L < P.nlev; ++L) {
         hipLaunchKernelGGL((pyramid_level_kernel<T>), dim3(grid_for(c, P.len[L] * 64, 256, 8)), dim3(256), 0, c->stream, P.lvl[L - 1],
                            P.len[L - 1], P.lvl[L], P.len[L]);

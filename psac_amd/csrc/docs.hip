@@ -7,14 +7,6 @@
 
 namespace psacx {
 
-static int sort_first_call(psacx_ctx* c, uint32_t* a, uint32_t* b, uint64_t n, uint32_t bits) { return pair_sort_first_dev_u32(c, a, b, n, bits); }
-static int sort_first_call(psacx_ctx* c, uint64_t* a, uint64_t* b, uint64_t n, uint32_t bits) { return pair_sort_first_dev_u64(c, a, b, n, bits); }
-
-static int scan_call(psacx_ctx* c, uint32_t* a, uint64_t len) { return exclusive_scan_u32_dev(c, a, len); }
-static int scan_call(psacx_ctx* c, uint64_t* a, uint64_t len) { return exclusive_scan_u64_dev(c, a, len); }
-
-static uint32_t bits_of(uint64_t x) { uint32_t b = 1; while (b < 64 && (x >> b)) ++b; return b; }
-
 // psacx_doc_index_dev_*: the keys, their sort, prev and h from the sorted keys, and the scan of h in the caller's dup.
 // Scratch: the two key words, 2 n entries, are memory of the call's own, there before anything is written.  The ctx slab holds the
 // buffers of the rank-pair sort and then the block sums of the scan (both lay themselves out from its base; the sort waits).
@@ -46,7 +38,7 @@ int doc_index_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, c
     hipLaunchKernelGGL((doc_keys_kernel<T>), dim3(lane_grid), dim3(256), 0, c->stream, d_SA, n, d_off, m, k1, k2);
     PSACX_HIP(c, hipGetLastError());
     mark(1);
-    PSACX_TRY(sort_first_call(c, k1, k2, n, bits_of(m - 1)));
+    PSACX_TRY(pair_sort_first_dev_any(c, k1, k2, n, bits_of(m - 1)));
     mark(2);
     if (d_dup) PSACX_HIP(c, hipMemsetAsync(d_dup, 0, (n + 1) * sizeof(T), c->stream));
     hipLaunchKernelGGL((doc_prev_kernel<T>), dim3(lane_grid), dim3(256), 0, c->stream, (const T*)k1, (const T*)k2, n, d_prev, d_dup);
@@ -56,7 +48,7 @@ int doc_index_dev(psacx_ctx* c, uint64_t n, const uint64_t* d_off, uint64_t m, c
                            d_LCP, d_index, d_dup);
         PSACX_HIP(c, hipGetLastError());
         mark(3);
-        PSACX_TRY(scan_call(c, d_dup, n + 1));
+        PSACX_TRY(exclusive_scan_dev_any(c, d_dup, n + 1));
     } else mark(3);
     mark(4);
     s.step(hipStreamSynchronize(c->stream));
@@ -108,10 +100,8 @@ int doc_list_run(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_off,
     if (s.rc != PSACX_OK) return s.rc;
     hipLaunchKernelGGL((occ_counts_kernel<T>), dim3(grid_for(c, q + 1, 256, 8)), dim3(256), 0, c->stream, d_lb, d_ub, q, n, (uint64_t)0, d_cstart);
     PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_cstart, q + 1));
     uint64_t cand = 0;
-    PSACX_HIP(c, hipMemcpyAsync(&cand, d_cstart + q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PSACX_TRY(scan_total_u64_dev(c, d_cstart, q + 1, &cand));
     if (max_cand && cand > max_cand) return PSACX_ERANGE;
     if (cand == 0) {
         PSACX_HIP(c, hipMemsetAsync(d_start, 0, (q + 1) * sizeof(uint64_t), c->stream));
@@ -122,12 +112,12 @@ int doc_list_run(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_off,
     unsigned char* d_marks = nullptr;
     uint64_t* d_counts = nullptr;
     uint32_t* d_runs = nullptr;
-    auto cands = [&](Arena& a) {
+    s.place([&](Arena& a) {
         d_marks = a.take<unsigned char>(ntiles * OCC_TILE);
         d_counts = a.take<uint64_t>(ntiles + 1);
         d_runs = a.take<uint32_t>(ntiles * (OCC_TILE / DOC_RUN));
-    };
-    { Arena dry(nullptr); cands(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; cands(ar); }
+    });
+    if (s.rc != PSACX_OK) return s.rc;
     PSACX_HIP(c, hipMemsetAsync(d_marks + cand, 0, ntiles * OCC_TILE - cand, c->stream));
     const dim3 tile_grid(grid_for(c, ntiles * 256, 256, 8));
     hipLaunchKernelGGL((doc_mark_kernel<T>), tile_grid, dim3(256), 0, c->stream, d_prev, d_lb, (const uint64_t*)d_cstart, q, cand, d_marks);

@@ -234,6 +234,17 @@ inline int ensure_slab(psacx_ctx* c, size_t bytes) {
     return PSACX_OK;
 }
 
+// Scratch of a call in the ctx slab: layout(Arena&) takes its arrays; it runs once dry to size the slab and once on the slab itself.
+template <typename Layout>
+inline int slab_layout(psacx_ctx* c, Layout layout) {
+    Arena dry(nullptr);
+    layout(dry);
+    PSACX_TRY(ensure_slab(c, dry.off + 4096));
+    Arena ar(c->slab);
+    layout(ar);
+    return PSACX_OK;
+}
+
 inline int ensure_io(psacx_ctx* c, size_t bytes) {
     if (c->io_bytes >= bytes) return PSACX_OK;      // (kept between calls; it goes back to the device when a construction needs the room, construct_dev, or with psacx_trim)
     if (c->io) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->io); c->io = nullptr; c->io_bytes = 0; }

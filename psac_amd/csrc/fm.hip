@@ -9,13 +9,6 @@
 
 namespace psacx {
 
-static int bwt_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* e, const uint32_t* sa, uint8_t* b, uint32_t* f) {
-    return psacx_bwt_dev_u32(c, t, n, e, sa, b, f, nullptr);
-}
-static int bwt_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* e, const uint64_t* sa, uint8_t* b, uint32_t* f) {
-    return psacx_bwt_dev_u64(c, t, n, e, sa, b, f, nullptr);
-}
-
 // The layout a descriptor stands for, or PSACX_EINVAL where its bits / words do not follow from n, sigma, sample and marks, or a code
 // lies beyond sigma.
 template <typename T>
@@ -56,9 +49,7 @@ int fm_index_dev(psacx_ctx* c, uint64_t n, const uint8_t* d_bwt, const uint32_t*
         d_hist = a.take<unsigned long long>(512);
         d_cnt = a.take<uint64_t>(cells + 1);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     struct Marks {                                    // four events, made only under psacx_profile and destroyed on every path
         hipEvent_t e[4]; int made = 0;
         ~Marks() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(e[i]); }
@@ -209,9 +200,7 @@ int fm_occurrences_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* 
     if (!d_lb || !d_ub || !d_start) return PSACX_EINVAL;
     hipLaunchKernelGGL((occ_counts_kernel<T>), dim3(grid_for(c, q + 1, 256, 8)), dim3(256), 0, c->stream, d_lb, d_ub, q, Y.n, limit, d_start);
     PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_start, q + 1));
-    PSACX_HIP(c, hipMemcpyAsync(total, d_start + q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PSACX_TRY(scan_total_u64_dev(c, d_start, q + 1, total));
     if (!d_pos) return PSACX_OK;                      // size query
     if (*total > cap) return PSACX_ERANGE;
     if (*total == 0) return PSACX_OK;
@@ -248,9 +237,7 @@ int fm_text_samples_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const uint64_t*
             (void)a.take<unsigned char>(4096);
             d_ends = a.take<uint32_t>((n >> 5) + 1);
         };
-        { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-        Arena ar(c->slab);
-        layout(ar);
+        PSACX_TRY(slab_layout(c, layout));
         PSACX_TRY(string_offsets_valid_dev(c, d_off, m, n));
         PSACX_TRY(string_ends_bitmap_dev(c, d_off, m, n, d_ends));
     }
@@ -287,9 +274,7 @@ int fm_extract_dev(psacx_ctx* c, const uint64_t* d_fm, const psacx_fm_info* info
         (void)a.take<unsigned char>(std::max<uint64_t>(exclusive_scan_slab_bytes(q + 1), 4096));
         d_segs = a.take<uint64_t>(q + 1);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     if (d_off && Y.n) PSACX_TRY(string_offsets_valid_dev(c, d_off, m, Y.n));
     unsigned shift;
     const uint64_t blocks = Y.n / rate, use = fm_rate_of(rate, Y.n, shift);
@@ -331,9 +316,8 @@ int fm_search_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t
     if (sid && (!pos || !offsets)) return PSACX_EINVAL;
     if (n && (!text || !SA)) return PSACX_EINVAL;
     if (offsets && n && (m == 0 || m > n)) return PSACX_EINVAL;
-    if (poff[0] != 0) return PSACX_EINVAL;
-    for (uint64_t j = 0; j < q; ++j) if (poff[j + 1] < poff[j]) return PSACX_EINVAL;
-    if (poff[q] && !pat) return PSACX_EINVAL;
+    uint64_t S = 0;
+    PSACX_TRY(pattern_batch_valid(pat, poff, q, &S));
     PSACX_HIP(c, hipSetDevice(c->device));
     const uint64_t use = pos ? sample : 0;
     Staging s(c, "fm search");
@@ -343,17 +327,16 @@ int fm_search_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t
     uint32_t* d_first = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
     const uint64_t* d_off = nullptr;
     const uint32_t* d_ends = offsets && n ? s.string_ends(offsets, m, n, &d_off) : nullptr;
-    if (s.rc == PSACX_OK) s.rc = bwt_call(c, d_text, n, d_ends, d_SA, d_bwt, d_first);
+    if (s.rc == PSACX_OK) s.rc = bwt_dev<T>(c, d_text, n, d_ends, (const T*)d_SA, d_bwt, d_first, (uint64_t*)nullptr);
     psacx_fm_info info;
     if (s.rc == PSACX_OK) s.rc = fm_index_dev<T>(c, n, d_bwt, d_first, use ? d_SA : (const T*)nullptr, use, (uint64_t*)nullptr, &info);
     if (s.rc != PSACX_OK) return s.rc;
     uint64_t* d_fm = (uint64_t*)s.alloc(info.words * sizeof(uint64_t));
     if (s.rc == PSACX_OK) s.rc = fm_index_dev<T>(c, n, d_bwt, d_first, use ? d_SA : (const T*)nullptr, use, d_fm, &info);
-    uint8_t* d_pat = (uint8_t*)s.upload(pat, poff[q]);
-    uint64_t* d_poff = (uint64_t*)s.upload(poff, (q + 1) * sizeof(uint64_t));
+    const DeviceBatch b = s.upload_batch(pat, poff, q);
     T* d_lb = (T*)s.alloc(q * sizeof(T));
     T* d_ub = (T*)s.alloc(q * sizeof(T));
-    if (s.rc == PSACX_OK) s.rc = fm_count_dev<T>(c, d_fm, &info, d_pat, d_poff, q, d_lb, d_ub);
+    if (s.rc == PSACX_OK) s.rc = fm_count_dev<T>(c, d_fm, &info, b.pat, b.poff, q, d_lb, d_ub);
     s.download(lb, d_lb, q * sizeof(T));
     s.download(ub, d_ub, q * sizeof(T));
     if (!pos || s.rc != PSACX_OK) { s.step(hipStreamSynchronize(c->stream)); return s.rc; }

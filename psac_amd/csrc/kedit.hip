@@ -6,11 +6,6 @@
 
 namespace psacx {
 
-static int pair_sort_call(psacx_ctx* c, uint32_t* a, uint32_t* b, uint64_t n, uint32_t bits) { return pair_sort_keys_dev_u32(c, a, b, n, bits); }
-static int pair_sort_call(psacx_ctx* c, uint64_t* a, uint64_t* b, uint64_t n, uint32_t bits) { return pair_sort_keys_dev_u64(c, a, b, n, bits); }
-
-static uint32_t bits_of(uint64_t x) { uint32_t b = 1; while (b < 64 && (x >> b)) ++b; return b; }
-
 // the kernels of kedit.hpp by the bucket of e and by text / set
 #define KED_BY_BUCKET(e, CALL)                                                                                                      \
     do {                                                                                                                            \
@@ -42,7 +37,7 @@ static void launch_align(psacx_ctx* c, dim3 grid, uint32_t e, const uint8_t* d_t
 #undef KED_ALIGN
 }
 
-// psacx_kedit_dev_*: pieces, their search, the counts of their intervals and the scan as in kmismatch_dev; the masks of the candidates
+// psacx_kedit_dev_*: pieces, their search, the counts of their intervals and the scan by piece_candidates_dev; the masks of the candidates
 // and the scan of their counts; the raw pairs, their sort and the unique; the forward pass over the distinct pairs; with
 // PSACX_KEDIT_BEST the per-pattern minimum and a second compaction.
 // Scratch.  The ctx slab: the three words of the searches and the block sums of the scans at its base, and, between
@@ -66,39 +61,16 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
     if (!d_text || !d_SA || !d_poff) return PSACX_EINVAL;
     const uint32_t E1 = e + 1;
     if (q > (~0ull >> 8) / E1) return PSACX_ERANGE;
-    const uint64_t Q = q * E1;
     const unsigned stop = c->knobs.kedit_stop;
     const bool best = (flags & PSACX_KEDIT_BEST) != 0;
     PSACX_HIP(c, hipSetDevice(c->device));
 
-    if (!d_pat) {                                     // only a batch of empty patterns may come without a buffer
-        uint64_t S = 0;
-        PSACX_HIP(c, hipMemcpy(&S, d_poff + q, sizeof(S), hipMemcpyDeviceToHost));
-        if (S) return PSACX_EINVAL;
-    }
-
     Staging s(c, "kedit");
-    uint64_t *d_boff = nullptr, *d_cstart = nullptr;
-    T *d_lb = nullptr, *d_ub = nullptr;
-    auto pieces = [&](Arena& a) {
-        d_boff = a.take<uint64_t>(Q + 1);
-        d_cstart = a.take<uint64_t>(Q + 1);
-        d_lb = a.take<T>(Q);
-        d_ub = a.take<T>(Q);
-    };
-    { Arena dry(nullptr); pieces(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; pieces(ar); }
-    hipLaunchKernelGGL(kmm_pieces_kernel, dim3(grid_for(c, Q + 1, 256, 8)), dim3(256), 0, c->stream, d_poff, q, E1, d_boff);
-    PSACX_HIP(c, hipGetLastError());
-    // (the offsets are checked by the search, on the piece offsets, before anything is written: kmismatch.hip)
-    PSACX_TRY(locate_dev<T>(c, d_text, n, d_SA, d_table, k, code, d_pat ? d_pat : d_text, (const uint64_t*)d_boff, Q, d_lb, d_ub, d_ends));
-    hipLaunchKernelGGL((kmm_short_kernel<T>), dim3(grid_for(c, Q, 256, 8)), dim3(256), 0, c->stream, d_poff, q, E1, d_lb, d_ub);
-    hipLaunchKernelGGL((occ_counts_kernel<T>), dim3(grid_for(c, Q + 1, 256, 8)), dim3(256), 0, c->stream, (const T*)d_lb, (const T*)d_ub, Q, n, (uint64_t)0,
-                       d_cstart);
-    PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_cstart, Q + 1));
-    uint64_t total = 0;
-    PSACX_HIP(c, hipMemcpyAsync(&total, d_cstart + Q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PieceCandidates<T> pc;
+    PSACX_TRY(piece_candidates_dev<T>(c, s, d_text, n, d_ends, d_SA, d_table, k, code, d_pat, d_poff, q, E1, 0, pc));
+    uint64_t *const d_boff = pc.d_boff, *const d_cstart = pc.d_cstart;
+    T* const d_lb = pc.d_lb;
+    const uint64_t Q = pc.Q, total = pc.total;
     if (work) work[0] = total;
     if (max_cand && total > max_cand) return PSACX_ERANGE;
     if (total == 0 || stop == 1) return PSACX_OK;
@@ -106,20 +78,18 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
     // the masks of the candidates and the raw hits
     uint32_t* d_mask = nullptr;
     uint64_t* d_cnt = nullptr;
-    auto cands = [&](Arena& a) {
+    s.place([&](Arena& a) {
         d_mask = a.take<uint32_t>(total);
         d_cnt = a.take<uint64_t>(total + 1);
-    };
-    { Arena dry(nullptr); cands(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; cands(ar); }
+    });
+    if (s.rc != PSACX_OK) return s.rc;
     PSACX_HIP(c, hipMemsetAsync(d_cnt + total, 0, sizeof(uint64_t), c->stream));
     const uint64_t ctiles = (total + OCC_TILE - 1) / OCC_TILE;
     launch_verify<T>(c, dim3(grid_for(c, ctiles * 256, 256, 8)), e, d_text, n, d_ends, d_SA, d_pat, (const uint64_t*)d_boff, (const T*)d_lb,
                      (const uint64_t*)d_cstart, Q, E1, total, d_mask, d_cnt);
     PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_cnt, total + 1));
     uint64_t raw = 0;
-    PSACX_HIP(c, hipMemcpyAsync(&raw, d_cnt + total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PSACX_TRY(scan_total_u64_dev(c, d_cnt, total + 1, &raw));
     if (work) work[1] = raw;
     if (raw == 0 || stop == 2) return PSACX_OK;
 
@@ -128,17 +98,17 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
     T *d_k1 = nullptr, *d_k2 = nullptr;
     unsigned char* d_marks = nullptr;
     uint64_t* d_counts = nullptr;
-    auto raws = [&](Arena& a) {
+    s.place([&](Arena& a) {
         d_k1 = a.take<T>(raw);
         d_k2 = a.take<T>(raw);
         d_marks = a.take<unsigned char>(rtiles * OCC_TILE);
         d_counts = a.take<uint64_t>(rtiles + 1);
-    };
-    { Arena dry(nullptr); raws(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; raws(ar); }
+    });
+    if (s.rc != PSACX_OK) return s.rc;
     hipLaunchKernelGGL((ked_emit_kernel<T>), dim3(grid_for(c, total, 256, 8)), dim3(256), 0, c->stream, (const uint32_t*)d_mask, (const uint64_t*)d_cnt, total,
                        (const uint64_t*)d_boff, (const T*)d_lb, (const uint64_t*)d_cstart, Q, E1, d_SA, n, d_k1, d_k2);
     PSACX_HIP(c, hipGetLastError());
-    if (raw > 1) PSACX_TRY(pair_sort_call(c, d_k1, d_k2, raw, bits_of((q - 1) | (n - 1))));
+    if (raw > 1) PSACX_TRY(pair_sort_keys_dev_any(c, d_k1, d_k2, raw, bits_of((q - 1) | (n - 1))));
     hipLaunchKernelGGL((ked_unique_kernel<T>), dim3(grid_for(c, rtiles * OCC_TILE, 256, 8)), dim3(256), 0, c->stream, (const T*)d_k1, (const T*)d_k2, raw,
                        rtiles * OCC_TILE, d_marks);
     hipLaunchKernelGGL(select_count_kernel<OCC_TILE>, dim3(grid_for(c, rtiles * 256, 256, 8)), dim3(256), 0, c->stream, (const unsigned char*)d_marks, rtiles,
@@ -166,7 +136,7 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
     uint8_t* d_d0 = nullptr;
     uint32_t* d_best = nullptr;
     unsigned char* d_marks2 = nullptr;
-    auto uniq = [&](Arena& a) {
+    s.place([&](Arena& a) {
         d_q0 = a.take<uint64_t>(zu);
         d_t0 = a.take<T>(zu);
         d_l0 = a.take<T>(zu);
@@ -174,8 +144,8 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
         d_best = a.take<uint32_t>(q);
         d_marks2 = a.take<unsigned char>(utiles * OCC_TILE);
         d_counts2 = a.take<uint64_t>(utiles + 1);
-    };
-    { Arena dry(nullptr); uniq(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; uniq(ar); }
+    });
+    if (s.rc != PSACX_OK) return s.rc;
     PSACX_HIP(c, hipMemsetAsync(d_best, 0xFF, q * sizeof(uint32_t), c->stream));
     s.step(select_emit(c, d_marks, OCC_TILE, rtiles, d_counts, KedPairEmit<T>{d_k1, d_k2, d_q0, d_t0}));
     launch_align<T>(c, dim3(grid_for(c, zu, 256, 8)), e, d_text, n, d_ends, d_pat, d_poff, q, (const uint64_t*)d_q0, (const T*)d_t0, zu, d_l0, d_d0, d_best);
@@ -193,14 +163,6 @@ int kedit_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
     return s.rc;
 }
 
-// the table of locate.hip by index width
-static int table_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint32_t* table, uint16_t* code, uint32_t* sigma, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, table, code, sigma, e) : psacx_lookup_table_dev_u32(c, t, n, nullptr, k, table, code, sigma, e);
-}
-static int table_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint64_t* table, uint16_t* code, uint32_t* sigma, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u64(c, t, n, ends, k, table, code, sigma, e) : psacx_lookup_table_dev_u64(c, t, n, nullptr, k, table, code, sigma, e);
-}
-
 // The host-pointer form: text, SA and patterns are staged (staging.hpp); the bitmap of the string ends and, when k > 0, the table
 // are built beside them; the count query sizes the lists and the quadruples come back.  Everything allocated is freed on every
 // path.  qid == nullptr: the count query.
@@ -215,27 +177,19 @@ int kedit_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* of
     if ((qid == nullptr) != (tpos == nullptr) || (qid == nullptr) != (len == nullptr) || (qid == nullptr) != (dist == nullptr)) return PSACX_EINVAL;
     if (q == 0 || n == 0) return PSACX_OK;
     if (!text || !SA || !poff || (offsets && (m == 0 || m > n))) return PSACX_EINVAL;
-    if (poff[0] != 0) return PSACX_EINVAL;
-    for (uint64_t i = 0; i < q; ++i) if (poff[i + 1] < poff[i]) return PSACX_EINVAL;
-    const uint64_t S = poff[q];
+    uint64_t S = 0;
+    PSACX_TRY(pattern_batch_valid(pat, poff, q, &S));
     if (S == 0) return PSACX_OK;
-    if (!pat) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     Staging s(c, "kedit");
     const uint8_t* d_text = (const uint8_t*)s.upload(text, n);
     const T* d_SA = (const T*)s.upload(SA, n * sizeof(T));
-    const uint8_t* d_pat = (const uint8_t*)s.upload(pat, S);
-    const uint64_t* d_poff = (const uint64_t*)s.upload(poff, (q + 1) * sizeof(uint64_t));
+    const DeviceBatch b = s.upload_batch(pat, poff, q);
+    const uint8_t* d_pat = b.pat;
+    const uint64_t* d_poff = b.poff;
     const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
     uint16_t code[256];
-    T* d_table = nullptr;
-    if (s.rc == PSACX_OK && k) {                      // the size of the table, then the table
-        uint32_t sigma = 0;
-        uint64_t entries = 0;
-        s.rc = table_call(c, d_text, n, d_ends, k, (T*)nullptr, code, &sigma, &entries);
-        if (s.rc == PSACX_OK) d_table = (T*)s.alloc(entries * sizeof(T));
-        if (s.rc == PSACX_OK) s.rc = table_call(c, d_text, n, d_ends, k, d_table, code, &sigma, &entries);
-    }
+    const T* d_table = staged_lookup_table<T>(s, d_text, n, d_ends, k, code);
     const uint16_t* cd = k ? code : nullptr;
     if (s.rc == PSACX_OK)
         s.rc = kedit_dev<T>(c, d_text, n, d_ends, d_SA, d_table, k, cd, d_pat, d_poff, q, e, max_cand, flags, (uint64_t*)nullptr, (T*)nullptr, (T*)nullptr,

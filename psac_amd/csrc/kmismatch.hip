@@ -6,8 +6,45 @@
 
 namespace psacx {
 
-// psacx_kmismatch_dev_*: the piece offsets, the locate call over them (which checks the offsets), the counts of the intervals and their scan,
-// the marks of the candidates, the counts of the mark tiles, their scan and the triples.
+// The front end of kmismatch_dev and kedit_dev (query_calls.hpp): the piece offsets, the locate call over them, the counts of the
+// intervals and their scan.
+template <typename T>
+int piece_candidates_dev(psacx_ctx* c, Staging& s, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table,
+                         uint32_t k, const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t E1, size_t extra,
+                         PieceCandidates<T>& pc) {
+    if (!d_pat) {                                     // only a batch of empty patterns may come without a buffer
+        uint64_t S = 0;
+        PSACX_HIP(c, hipMemcpy(&S, d_poff + q, sizeof(S), hipMemcpyDeviceToHost));
+        if (S) return PSACX_EINVAL;
+    }
+    const uint64_t Q = q * E1;
+    pc.Q = Q;
+    s.place([&](Arena& a) {
+        pc.d_boff = a.take<uint64_t>(Q + 1);
+        pc.d_cstart = a.take<uint64_t>(Q + 1);
+        pc.d_extra = extra ? a.take<unsigned char>(extra) : nullptr;
+        pc.d_lb = a.take<T>(Q);
+        pc.d_ub = a.take<T>(Q);
+    });
+    if (s.rc != PSACX_OK) return s.rc;
+    hipLaunchKernelGGL(kmm_pieces_kernel, dim3(grid_for(c, Q + 1, 256, 8)), dim3(256), 0, c->stream, d_poff, q, E1, pc.d_boff);
+    PSACX_HIP(c, hipGetLastError());
+    // (the offsets are checked by the search, on the piece offsets: boff[j (e + 1)] = poff[j], so a poff that does not start at 0 or
+    // descends gives piece offsets that do neither, and the search returns PSACX_EINVAL before it writes)
+    PSACX_TRY(locate_dev<T>(c, d_text, n, d_SA, d_table, k, code, d_pat ? d_pat : d_text, (const uint64_t*)pc.d_boff, Q, pc.d_lb, pc.d_ub, d_ends));
+    hipLaunchKernelGGL((kmm_short_kernel<T>), dim3(grid_for(c, Q, 256, 8)), dim3(256), 0, c->stream, d_poff, q, E1, pc.d_lb, pc.d_ub);
+    hipLaunchKernelGGL((occ_counts_kernel<T>), dim3(grid_for(c, Q + 1, 256, 8)), dim3(256), 0, c->stream, (const T*)pc.d_lb, (const T*)pc.d_ub, Q, n, (uint64_t)0,
+                       pc.d_cstart);
+    PSACX_HIP(c, hipGetLastError());
+    return scan_total_u64_dev(c, pc.d_cstart, Q + 1, &pc.total);
+}
+
+template int piece_candidates_dev<uint32_t>(psacx_ctx*, Staging&, const uint8_t*, uint64_t, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t,
+                                            const uint16_t*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, size_t, PieceCandidates<uint32_t>&);
+template int piece_candidates_dev<uint64_t>(psacx_ctx*, Staging&, const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, const uint64_t*, uint32_t,
+                                            const uint16_t*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, size_t, PieceCandidates<uint64_t>&);
+
+// psacx_kmismatch_dev_*: the front end above, the marks of the candidates, the counts of the mark tiles, their scan and the triples.
 // Scratch.  The ctx slab holds the three words of the searches and the block sums of the scans only (both at its base, one after the
 // other).  Two blocks of memory of the call's own: one sized by the pieces -- piece offsets, candidate starts, the word of the tested
 // candidates and the piece intervals -- and, once the number of candidates is known and has passed max_cand, one sized by the
@@ -27,41 +64,15 @@ int kmismatch_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_
     if (!d_text || !d_SA || !d_poff) return PSACX_EINVAL;
     const uint32_t E1 = e + 1;
     if (q > (~0ull >> 8) / E1) return PSACX_ERANGE;
-    const uint64_t Q = q * E1;
     PSACX_HIP(c, hipSetDevice(c->device));
 
-    if (!d_pat) {                                     // only a batch of empty patterns may come without a buffer
-        uint64_t S = 0;
-        PSACX_HIP(c, hipMemcpy(&S, d_poff + q, sizeof(S), hipMemcpyDeviceToHost));
-        if (S) return PSACX_EINVAL;
-    }
-
     Staging s(c, "kmismatch");
-    uint64_t *d_boff = nullptr, *d_cstart = nullptr;
-    unsigned long long* d_tested = nullptr;
-    T *d_lb = nullptr, *d_ub = nullptr;
-    auto pieces = [&](Arena& a) {
-        d_boff = a.take<uint64_t>(Q + 1);
-        d_cstart = a.take<uint64_t>(Q + 1);
-        d_tested = a.take<unsigned long long>(1);
-        d_lb = a.take<T>(Q);
-        d_ub = a.take<T>(Q);
-    };
-    { Arena dry(nullptr); pieces(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; pieces(ar); }
-    PSACX_HIP(c, hipMemsetAsync(d_tested, 0, sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(kmm_pieces_kernel, dim3(grid_for(c, Q + 1, 256, 8)), dim3(256), 0, c->stream, d_poff, q, E1, d_boff);
-    PSACX_HIP(c, hipGetLastError());
-    // (the offsets are checked by the search, on the piece offsets: boff[j (e + 1)] = poff[j], so a poff that does not start at 0 or
-    // descends gives piece offsets that do neither, and the search returns PSACX_EINVAL before it writes)
-    PSACX_TRY(locate_dev<T>(c, d_text, n, d_SA, d_table, k, code, d_pat ? d_pat : d_text, (const uint64_t*)d_boff, Q, d_lb, d_ub, d_ends));
-    hipLaunchKernelGGL((kmm_short_kernel<T>), dim3(grid_for(c, Q, 256, 8)), dim3(256), 0, c->stream, d_poff, q, E1, d_lb, d_ub);
-    hipLaunchKernelGGL((occ_counts_kernel<T>), dim3(grid_for(c, Q + 1, 256, 8)), dim3(256), 0, c->stream, (const T*)d_lb, (const T*)d_ub, Q, n, (uint64_t)0,
-                       d_cstart);
-    PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_u64_dev(c, d_cstart, Q + 1));
-    uint64_t total = 0;
-    PSACX_HIP(c, hipMemcpyAsync(&total, d_cstart + Q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PieceCandidates<T> pc;
+    PSACX_TRY(piece_candidates_dev<T>(c, s, d_text, n, d_ends, d_SA, d_table, k, code, d_pat, d_poff, q, E1, sizeof(unsigned long long), pc));
+    uint64_t *const d_boff = pc.d_boff, *const d_cstart = pc.d_cstart;
+    unsigned long long* const d_tested = reinterpret_cast<unsigned long long*>(pc.d_extra);      // the word of the tested candidates
+    T* const d_lb = pc.d_lb;
+    const uint64_t Q = pc.Q, total = pc.total;
     if (work) work[0] = total;
     if (max_cand && total > max_cand) return PSACX_ERANGE;
     if (total == 0 || c->knobs.kmismatch_stop == 1) return PSACX_OK;
@@ -69,11 +80,12 @@ int kmismatch_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_
     const uint64_t ntiles = (total + OCC_TILE - 1) / OCC_TILE;
     unsigned char* d_marks = nullptr;
     uint64_t* d_counts = nullptr;
-    auto cands = [&](Arena& a) {
+    s.place([&](Arena& a) {
         d_marks = a.take<unsigned char>(ntiles * OCC_TILE);
         d_counts = a.take<uint64_t>(ntiles + 1);
-    };
-    { Arena dry(nullptr); cands(dry); Arena ar((char*)s.alloc(dry.off)); if (s.rc != PSACX_OK) return s.rc; cands(ar); }
+    });
+    if (s.rc != PSACX_OK) return s.rc;
+    PSACX_HIP(c, hipMemsetAsync(d_tested, 0, sizeof(unsigned long long), c->stream));
     PSACX_HIP(c, hipMemsetAsync(d_marks + total, 0, ntiles * OCC_TILE - total, c->stream));
     {
         const dim3 grid(grid_for(c, ntiles * 256, 256, 8));
@@ -105,14 +117,6 @@ int kmismatch_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_
     return s.rc;
 }
 
-// the table of the other file by index width
-static int table_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint32_t* table, uint16_t* code, uint32_t* sigma, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, table, code, sigma, e) : psacx_lookup_table_dev_u32(c, t, n, nullptr, k, table, code, sigma, e);
-}
-static int table_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint64_t* table, uint16_t* code, uint32_t* sigma, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u64(c, t, n, ends, k, table, code, sigma, e) : psacx_lookup_table_dev_u64(c, t, n, nullptr, k, table, code, sigma, e);
-}
-
 // The host-pointer form: text, SA and patterns are staged (staging.hpp); the bitmap of the string ends and, when k > 0, the table
 // are built beside them; the count query sizes the lists and the triples come back.  Everything allocated is freed on every path.
 // qid == nullptr: the count query.
@@ -127,27 +131,19 @@ int kmismatch_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t
     if ((qid == nullptr) != (tpos == nullptr) || (qid == nullptr) != (dist == nullptr)) return PSACX_EINVAL;
     if (q == 0 || n == 0) return PSACX_OK;
     if (!text || !SA || !poff || (offsets && (m == 0 || m > n))) return PSACX_EINVAL;
-    if (poff[0] != 0) return PSACX_EINVAL;
-    for (uint64_t i = 0; i < q; ++i) if (poff[i + 1] < poff[i]) return PSACX_EINVAL;
-    const uint64_t S = poff[q];
+    uint64_t S = 0;
+    PSACX_TRY(pattern_batch_valid(pat, poff, q, &S));
     if (S == 0) return PSACX_OK;
-    if (!pat) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     Staging s(c, "kmismatch");
     const uint8_t* d_text = (const uint8_t*)s.upload(text, n);
     const T* d_SA = (const T*)s.upload(SA, n * sizeof(T));
-    const uint8_t* d_pat = (const uint8_t*)s.upload(pat, S);
-    const uint64_t* d_poff = (const uint64_t*)s.upload(poff, (q + 1) * sizeof(uint64_t));
+    const DeviceBatch b = s.upload_batch(pat, poff, q);
+    const uint8_t* d_pat = b.pat;
+    const uint64_t* d_poff = b.poff;
     const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
     uint16_t code[256];
-    T* d_table = nullptr;
-    if (s.rc == PSACX_OK && k) {                      // the size of the table, then the table
-        uint32_t sigma = 0;
-        uint64_t entries = 0;
-        s.rc = table_call(c, d_text, n, d_ends, k, (T*)nullptr, code, &sigma, &entries);
-        if (s.rc == PSACX_OK) d_table = (T*)s.alloc(entries * sizeof(T));
-        if (s.rc == PSACX_OK) s.rc = table_call(c, d_text, n, d_ends, k, d_table, code, &sigma, &entries);
-    }
+    const T* d_table = staged_lookup_table<T>(s, d_text, n, d_ends, k, code);
     const uint16_t* cd = k ? code : nullptr;
     if (s.rc == PSACX_OK)
         s.rc = kmismatch_dev<T>(c, d_text, n, d_ends, d_SA, d_table, k, cd, d_pat, d_poff, q, e, max_cand, (uint64_t*)nullptr, (T*)nullptr,

@@ -77,6 +77,23 @@ int lookup_table_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* /
     return PSACX_OK;
 }
 
+// the table of a host-pointer form (staging.hpp)
+template <typename T>
+T* staged_lookup_table(Staging& s, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, uint32_t k, uint16_t code[256]) {
+    if (s.rc != PSACX_OK || !k) return nullptr;
+    CodeTable tab;
+    uint32_t sigma = 0;
+    uint64_t keys = 0;
+    s.rc = table_alphabet(s.c, d_text, n, k, tab, sigma, keys);
+    T* d_table = (T*)s.alloc((keys + 1) * sizeof(T));
+    if (s.rc == PSACX_OK) s.rc = lookup_table_fill<T>(s.c, d_text, n, k, sigma + 1, keys, tab, d_table, d_ends);
+    if (s.rc == PSACX_OK) std::memcpy(code, tab.c, sizeof(tab.c));
+    return d_table;
+}
+
+template uint32_t* staged_lookup_table<uint32_t>(Staging&, const uint8_t*, uint64_t, const uint32_t*, uint32_t, uint16_t*);
+template uint64_t* staged_lookup_table<uint64_t>(Staging&, const uint8_t*, uint64_t, const uint32_t*, uint32_t, uint16_t*);
+
 // What a search takes of its table: (d_table, k, code[]) are all there or all absent (k == 0), and code[] gives tab and
 // B = sigma + 1 with B^k inside LOCATE_MAX_KEYS; PSACX_EINVAL otherwise.
 struct SearchTable { CodeTable tab; uint32_t B = 1; };
@@ -176,6 +193,11 @@ int match_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d
     });
 }
 
+template int match_dev<uint32_t>(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, bool, const uint32_t*, const uint32_t*, uint32_t, const uint16_t*,
+                                 const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint64_t, uint32_t*, uint32_t*, uint32_t*);
+template int match_dev<uint64_t>(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, bool, const uint64_t*, const uint64_t*, uint32_t, const uint16_t*,
+                                 const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*);
+
 // The host-pointer forms of the two: everything is staged in device memory of its own for the time of the call, the table is built
 // when k > 0, and the result arrays come back: lb and ub of q entries, or with longest (psacx_match_*) len, lb and ub of q
 // entries, of poff[q] in the suffix mode.  offsets != nullptr: the text is the string set of those m + 1 offsets (psacx_*_gsa_*);
@@ -188,35 +210,26 @@ int search_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* o
     if (q == 0) return PSACX_OK;
     if (!text || !SA || !poff || n == 0) return PSACX_EINVAL;
     if (offsets && (m == 0 || m > n)) return PSACX_EINVAL;
-    if (poff[0] != 0) return PSACX_EINVAL;
-    for (uint64_t i = 0; i < q; ++i) if (poff[i + 1] < poff[i]) return PSACX_EINVAL;
-    if (poff[q] && !pat) return PSACX_EINVAL;
-    const uint64_t entries = (flags & PSACX_MATCH_SUFFIXES) ? poff[q] : q;
+    uint64_t S = 0;
+    PSACX_TRY(pattern_batch_valid(pat, poff, q, &S));
+    const uint64_t entries = (flags & PSACX_MATCH_SUFFIXES) ? S : q;
     if (entries && ((longest && !len) || !lb || !ub)) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     Staging s(c, longest ? "match" : "locate");
     const uint8_t* d_text = (const uint8_t*)s.upload(text, n);
     const T* d_SA = (const T*)s.upload(SA, n * sizeof(T));
-    const uint8_t* d_pat = (const uint8_t*)s.upload(pat, poff[q]);
-    const uint64_t* d_poff = (const uint64_t*)s.upload(poff, (q + 1) * sizeof(uint64_t));
+    const DeviceBatch b = s.upload_batch(pat, poff, q);
     T* d_len = longest ? (T*)s.alloc(entries * sizeof(T)) : nullptr;
     T* d_lb = (T*)s.alloc(entries * sizeof(T));
     T* d_ub = (T*)s.alloc(entries * sizeof(T));
     const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
-    CodeTable tab;
-    T* d_table = nullptr;
-    if (s.rc == PSACX_OK && k) {                      // one histogram for the alphabet, then the table sized by it
-        uint32_t sigma = 0;
-        uint64_t keys = 0;
-        s.rc = table_alphabet(c, d_text, n, k, tab, sigma, keys);
-        d_table = (T*)s.alloc((keys + 1) * sizeof(T));
-        if (s.rc == PSACX_OK) s.rc = lookup_table_fill<T>(c, d_text, n, k, sigma + 1, keys, tab, d_table, d_ends);
-    }
-    const uint16_t* code = k ? tab.c : nullptr;
+    uint16_t codes[256];
+    const T* d_table = staged_lookup_table<T>(s, d_text, n, d_ends, k, codes);
+    const uint16_t* code = k ? codes : nullptr;
     if (s.rc == PSACX_OK)
-        s.rc = longest ? match_dev<T>(c, d_text, n, d_ends, offsets != nullptr, d_SA, d_table, k, code, d_pat, d_poff, q, flags, max_len, entries, d_len,
+        s.rc = longest ? match_dev<T>(c, d_text, n, d_ends, offsets != nullptr, d_SA, d_table, k, code, b.pat, b.poff, q, flags, max_len, entries, d_len,
                                       d_lb, d_ub)
-                       : locate_dev<T>(c, d_text, n, d_SA, d_table, k, code, d_pat, d_poff, q, d_lb, d_ub, d_ends);
+                       : locate_dev<T>(c, d_text, n, d_SA, d_table, k, code, b.pat, b.poff, q, d_lb, d_ub, d_ends);
     s.download(len, d_len, entries * sizeof(T));
     s.download(lb, d_lb, entries * sizeof(T));
     s.download(ub, d_ub, entries * sizeof(T));
@@ -253,9 +266,7 @@ int occurrences_dev(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_o
     PSACX_HIP(c, hipSetDevice(c->device));
     hipLaunchKernelGGL((occ_counts_kernel<T>), dim3(grid_for(c, q + 1, 256, 8)), dim3(256), 0, c->stream, d_lb, d_ub, q, n, limit, d_start);
     PSACX_HIP(c, hipGetLastError());
-    PSACX_TRY(exclusive_scan_dev<uint64_t>(c, d_start, q + 1));
-    PSACX_HIP(c, hipMemcpyAsync(total, d_start + q, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    PSACX_TRY(scan_total_u64_dev(c, d_start, q + 1, total));
     if (!d_pos) return PSACX_OK;                      // size query
     if (*total > cap) return PSACX_ERANGE;
     if (*total == 0) return PSACX_OK;
@@ -270,6 +281,12 @@ int occurrences_dev(psacx_ctx* c, const T* d_SA, uint64_t n, const uint64_t* d_o
 // the scan for callers outside this file (query_calls.hpp)
 int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len) { return exclusive_scan_dev<uint64_t>(c, d_a, len); }
 int exclusive_scan_u32_dev(psacx_ctx* c, uint32_t* d_a, uint64_t len) { return exclusive_scan_dev<uint32_t>(c, d_a, len); }
+int scan_total_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len, uint64_t* total) {
+    PSACX_TRY(exclusive_scan_dev<uint64_t>(c, d_a, len));
+    PSACX_HIP(c, hipMemcpyAsync(total, d_a + len - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    PSACX_HIP(c, hipStreamSynchronize(c->stream));
+    return PSACX_OK;
+}
 uint64_t exclusive_scan_slab_bytes(uint64_t len) {
     return (len + 256 * LOCATE_SCAN_ITEMS - 1) / (256 * LOCATE_SCAN_ITEMS) * sizeof(unsigned long long) + 4096;
 }

@@ -64,9 +64,7 @@ int lz77_dev(psacx_ctx* c, uint64_t n, const T* d_lpf, const T* d_src, T* d_star
         d_marks = a.take<unsigned char>(ntiles * geo.B);
         d_gexit = a.take<T>(n);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     PSACX_HIP(c, hipMemsetAsync(d_counts, 0, (ntiles + 1) * sizeof(uint64_t), c->stream));
     PSACX_HIP(c, hipMemsetAsync(d_gentry, 0xFF, ngroups * sizeof(uint64_t), c->stream));
     PSACX_HIP(c, hipMemsetAsync(d_marks, 0, ntiles * geo.B, c->stream));

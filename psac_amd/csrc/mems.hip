@@ -53,9 +53,7 @@ int mems_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const T* d_LCP, const T* d
         if (super) d_kept = a.take<unsigned long long>(1);
         else d_ccnt = a.take<uint64_t>(S + 1);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
 
     if (super) {
         PSACX_HIP(c, hipMemsetAsync(d_kept, 0, sizeof(unsigned long long), c->stream));
@@ -123,30 +121,6 @@ int mems_dev(psacx_ctx* c, uint64_t n, const T* d_SA, const T* d_LCP, const T* d
     return s.rc;
 }
 
-// the calls of the other files by index width (their templates are instantiated behind the C ABI)
-static int table_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint32_t* table, uint16_t* code, uint32_t* sigma, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u32(c, t, n, ends, k, table, code, sigma, e) : psacx_lookup_table_dev_u32(c, t, n, nullptr, k, table, code, sigma, e);
-}
-static int table_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, uint32_t k, uint64_t* table, uint16_t* code, uint32_t* sigma, uint64_t* e) {
-    return ends ? psacx_lookup_table_gsa_dev_u64(c, t, n, ends, k, table, code, sigma, e) : psacx_lookup_table_dev_u64(c, t, n, nullptr, k, table, code, sigma, e);
-}
-static int match_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, const uint32_t* table, uint32_t k,
-                      const uint16_t* code, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t S, uint32_t* len, uint32_t* lb, uint32_t* ub) {
-    return ends ? psacx_match_gsa_dev_u32(c, t, n, ends, sa, table, k, code, pat, poff, q, PSACX_MATCH_SUFFIXES, 0, S, len, lb, ub)
-                : psacx_match_dev_u32(c, t, n, sa, table, k, code, pat, poff, q, PSACX_MATCH_SUFFIXES, 0, S, len, lb, ub);
-}
-static int match_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, const uint64_t* table, uint32_t k,
-                      const uint16_t* code, const uint8_t* pat, const uint64_t* poff, uint64_t q, uint64_t S, uint64_t* len, uint64_t* lb, uint64_t* ub) {
-    return ends ? psacx_match_gsa_dev_u64(c, t, n, ends, sa, table, k, code, pat, poff, q, PSACX_MATCH_SUFFIXES, 0, S, len, lb, ub)
-                : psacx_match_dev_u64(c, t, n, sa, table, k, code, pat, poff, q, PSACX_MATCH_SUFFIXES, 0, S, len, lb, ub);
-}
-static int bwt_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint32_t* sa, uint8_t* bwt, uint32_t* first) {
-    return psacx_bwt_dev_u32(c, t, n, ends, sa, bwt, first, nullptr);
-}
-static int bwt_call(psacx_ctx* c, const uint8_t* t, uint64_t n, const uint32_t* ends, const uint64_t* sa, uint8_t* bwt, uint32_t* first) {
-    return psacx_bwt_dev_u64(c, t, n, ends, sa, bwt, first, nullptr);
-}
-
 // The host-pointer form: text, SA, LCP and patterns are staged (staging.hpp); the bitmap of the string ends, the table when k > 0, the
 // statistics, the index and the BWT are built beside them; the count query sizes the lists and the triples come back.  Everything
 // allocated is freed on every path.  qpos == nullptr: the count query.
@@ -161,11 +135,9 @@ int mems_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* off
     if ((qpos == nullptr) != (tpos == nullptr) || (qpos == nullptr) != (len == nullptr)) return PSACX_EINVAL;
     if (q == 0 || n == 0) return PSACX_OK;
     if (!text || !SA || !LCP || !poff || (offsets && (m == 0 || m > n))) return PSACX_EINVAL;
-    if (poff[0] != 0) return PSACX_EINVAL;
-    for (uint64_t i = 0; i < q; ++i) if (poff[i + 1] < poff[i]) return PSACX_EINVAL;
-    const uint64_t S = poff[q];
+    uint64_t S = 0;
+    PSACX_TRY(pattern_batch_valid(pat, poff, q, &S));
     if (S == 0) return PSACX_OK;
-    if (!pat) return PSACX_EINVAL;
     PSACX_HIP(c, hipSetDevice(c->device));
     RmqLayout Y;
     rmq_layout(n, Y);
@@ -173,8 +145,9 @@ int mems_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* off
     const uint8_t* d_text = (const uint8_t*)s.upload(text, n);
     const T* d_SA = (const T*)s.upload(SA, n * sizeof(T));
     const T* d_LCP = (const T*)s.upload(LCP, n * sizeof(T));
-    const uint8_t* d_pat = (const uint8_t*)s.upload(pat, S);
-    const uint64_t* d_poff = (const uint64_t*)s.upload(poff, (q + 1) * sizeof(uint64_t));
+    const DeviceBatch b = s.upload_batch(pat, poff, q);
+    const uint8_t* d_pat = b.pat;
+    const uint64_t* d_poff = b.poff;
     const uint32_t* d_ends = offsets ? s.string_ends(offsets, m, n) : nullptr;
     T* d_mlen = (T*)s.alloc(S * sizeof(T));
     T* d_mlb = (T*)s.alloc(S * sizeof(T));
@@ -183,18 +156,13 @@ int mems_host(psacx_ctx* c, const uint8_t* text, uint64_t n, const uint64_t* off
     uint8_t* d_bwt = (uint8_t*)s.alloc(n);
     uint32_t* d_first = (uint32_t*)s.alloc(((n >> 5) + 1) * sizeof(uint32_t));
     uint16_t code[256];
-    T* d_table = nullptr;
-    if (s.rc == PSACX_OK && k) {                      // the size of the table, then the table
-        uint32_t sigma = 0;
-        uint64_t entries = 0;
-        s.rc = table_call(c, d_text, n, d_ends, k, (T*)nullptr, code, &sigma, &entries);
-        if (s.rc == PSACX_OK) d_table = (T*)s.alloc(entries * sizeof(T));
-        if (s.rc == PSACX_OK) s.rc = table_call(c, d_text, n, d_ends, k, d_table, code, &sigma, &entries);
-    }
-    if (s.rc == PSACX_OK) s.rc = match_call(c, d_text, n, d_ends, d_SA, d_table, k, k ? code : nullptr, d_pat, d_poff, q, S, d_mlen, d_mlb, d_mub);
+    const T* d_table = staged_lookup_table<T>(s, d_text, n, d_ends, k, code);
+    if (s.rc == PSACX_OK)
+        s.rc = match_dev<T>(c, d_text, n, d_ends, d_ends != nullptr, d_SA, d_table, k, k ? code : nullptr, d_pat, d_poff, q, PSACX_MATCH_SUFFIXES, 0, S, d_mlen,
+                            d_mlb, d_mub);
     uint64_t entries = 0;
     if (s.rc == PSACX_OK) s.rc = rmq_index_dev<T>(c, d_LCP, n, d_index, &entries);
-    if (s.rc == PSACX_OK) s.rc = bwt_call(c, d_text, n, d_ends, d_SA, d_bwt, d_first);
+    if (s.rc == PSACX_OK) s.rc = bwt_dev<T>(c, d_text, n, d_ends, d_SA, d_bwt, d_first, (uint64_t*)nullptr);
     if (s.rc == PSACX_OK)
         s.rc = mems_dev<T>(c, n, d_SA, d_LCP, d_index, d_bwt, d_first, d_pat, d_poff, q, d_mlen, d_mlb, d_mub, min_len, max_occ, flags, (uint64_t*)nullptr,
                            (T*)nullptr, (T*)nullptr, 0, z, (uint64_t*)nullptr);

@@ -1094,9 +1094,7 @@ struct MultiRun {
         SortScratch sc;
         T* cls = nullptr;
         auto layout = [&](Arena& a) { cls = a.take<T>(cnt); sc.take(a, cnt, /*base_desc_only=*/true); };
-        { Arena dry(nullptr); layout(dry); MG_OP(g, c, ensure_slab(c, dry.off + 4096)); }
-        Arena ar(c->slab);
-        layout(ar);
+        MG_OP(g, c, slab_layout(c, layout));
         MG_OP(g, c, psacx_op_owners(c, gidx, cnt, n, (uint32_t)P, cls));
         SortBufs<T> in{const_cast<T*>(gidx), nullptr, const_cast<T*>(payload)}, o{out.k2.p, nullptr, out.v.p};
         unsigned long long* starts = reinterpret_cast<unsigned long long*>(c->pinned + PIN_HIST);

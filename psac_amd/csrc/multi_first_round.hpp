@@ -196,9 +196,7 @@ int MultiRun<T>::sort_first_two_word(std::vector<Rec<T>>& rec, const std::vector
             if (!cn) return PSACX_OK;
             SortScratch sc;
             auto layout = [&](Arena& ar) { sc.d_base = ar.take<unsigned long long>((size_t)RADIX); sc.desc_bytes = sort_desc_bytes(cn); sc.d_desc = ar.take<char>(sc.desc_bytes); };
-            { Arena dry(nullptr); layout(dry); MG_OP(g, c, ensure_slab(c, dry.off + 4096)); }
-            Arena ar(c->slab);
-            layout(ar);
+            MG_OP(g, c, slab_layout(c, layout));
             uint64_t sq, snq, vq;
             payload_of(i, 0, &sq, &snq, &vq);
             MG_HIP(g, hipSetDevice(c->device));

@@ -1,6 +1,9 @@
 // query_calls.hpp -- what the query layer calls across its .hip files (locate.hip, rmq.hip, lz.hip, repeats.hip, mems.hip, kmismatch.hip, kedit.hip, docs.hip, fm.hip, and check.hip and
 // ansv.hip where they serve it), declared once.  Every file that defines one of these includes this header too, so a signature
-// that moves in one place alone does not compile.
+// that moves in one place alone does not compile.  A template that another file calls is declared here and instantiated for both index
+// widths where it is defined; the calls that exist per width only (the sorts of psacx_u32.hip / psacx_u64.hip, the two scans) have
+// overloads by entry type here, so that no caller re-enters the C ABI or keeps width shims of its own.  What the host-pointer forms
+// share beyond that is in staging.hpp.
 #pragma once
 #include "engine.hpp"
 
@@ -18,12 +21,25 @@ int string_ends_bitmap_dev(psacx_ctx* c, const uint64_t* d_off, uint64_t m, uint
 int exclusive_scan_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len);
 int exclusive_scan_u32_dev(psacx_ctx* c, uint32_t* d_a, uint64_t len);           // (32-bit entries whose sum stays below 2^32: docs.hip)
 uint64_t exclusive_scan_slab_bytes(uint64_t len);
+// the scan of d_a[0 .. len), len >= 1, and its last entry -- the sum of all but the last -- in *total: one copy, one wait
+int scan_total_u64_dev(psacx_ctx* c, uint64_t* d_a, uint64_t len, uint64_t* total);
 
 // locate.hip: psacx_locate_dev_* itself, and with d_ends psacx_locate_gsa_dev_* (uses the first words of the ctx slab; waits), instantiated
 // there for both widths
 template <typename T>
 int locate_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const T* d_SA, const T* d_table, uint32_t k, const uint16_t* code,
                const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, T* d_lb, T* d_ub, const uint32_t* d_ends = nullptr);
+// locate.hip: psacx_match_dev_* itself, and with set psacx_match_gsa_dev_*, which insists on d_ends (waits), instantiated there for both
+// widths
+template <typename T>
+int match_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, bool set, const T* d_SA, const T* d_table, uint32_t k,
+              const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t flags, uint64_t max_len, uint64_t out_entries,
+              T* d_len, T* d_lb, T* d_ub);
+
+// repeats.hip: psacx_bwt_dev_* itself (uses the first word of the ctx slab; waits), instantiated there for both widths
+template <typename T>
+int bwt_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, uint8_t* d_bwt, uint32_t* d_first,
+            uint64_t* primary);
 
 // ansv.hip: all nearest smaller values of an array in HBM into two arrays of n 64-bit entries (pyramid in the ctx slab; waits)
 int ansv_dev_u32(psacx_ctx* c, const uint32_t* in, uint64_t n, int lt, int rt, uint64_t nonsv, uint64_t* l, uint64_t* r);
@@ -45,6 +61,19 @@ template <typename T>
 int kmismatch_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table, uint32_t k,
                   const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t e, uint64_t max_cand, uint64_t* d_qid,
                   T* d_tpos, uint8_t* d_dist, uint64_t cap, uint64_t* z, uint64_t* work);
+
+// kmismatch.hip: the front end kmismatch_dev and kedit_dev share, after their own argument checks.  A batch without d_pat must be all
+// empty (PSACX_EINVAL; one blocking copy of poff[q]).  One block of s holds the Q + 1 piece offsets, the Q + 1 candidate starts, `extra`
+// bytes for the caller and the Q piece intervals, Q = q E1; the pieces are cut, searched by locate_dev (which refuses malformed
+// offsets before anything is written), the pieces of patterns shorter than E1 are emptied, and the interval counts are scanned:
+// total candidates.  Waits.  Instantiated there for both widths.
+struct Staging;
+template <typename T>
+struct PieceCandidates { uint64_t *d_boff, *d_cstart; unsigned char* d_extra; T *d_lb, *d_ub; uint64_t Q, total; };
+template <typename T>
+int piece_candidates_dev(psacx_ctx* c, Staging& s, const uint8_t* d_text, uint64_t n, const uint32_t* d_ends, const T* d_SA, const T* d_table,
+                         uint32_t k, const uint16_t* code, const uint8_t* d_pat, const uint64_t* d_poff, uint64_t q, uint32_t E1, size_t extra,
+                         PieceCandidates<T>& pc);
 
 // kedit.hip: psacx_kedit_dev_* itself (kernels in kedit.hpp; waits), instantiated there for both widths
 template <typename T>
@@ -79,6 +108,17 @@ int pair_sort_keys_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n,
 // the ranks by their string by it)
 int pair_sort_first_dev_u32(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits);
 int pair_sort_first_dev_u64(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits);
+
+// the sorts and the scans above by the width of their entries, for the templates of the query layer
+inline int pair_sort_keys_dev_any(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits) { return pair_sort_keys_dev_u32(c, b1, b2, n, bits); }
+inline int pair_sort_keys_dev_any(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits) { return pair_sort_keys_dev_u64(c, b1, b2, n, bits); }
+inline int pair_sort_first_dev_any(psacx_ctx* c, uint32_t* b1, uint32_t* b2, uint64_t n, uint32_t bits) { return pair_sort_first_dev_u32(c, b1, b2, n, bits); }
+inline int pair_sort_first_dev_any(psacx_ctx* c, uint64_t* b1, uint64_t* b2, uint64_t n, uint32_t bits) { return pair_sort_first_dev_u64(c, b1, b2, n, bits); }
+inline int exclusive_scan_dev_any(psacx_ctx* c, uint32_t* d_a, uint64_t len) { return exclusive_scan_u32_dev(c, d_a, len); }
+inline int exclusive_scan_dev_any(psacx_ctx* c, uint64_t* d_a, uint64_t len) { return exclusive_scan_u64_dev(c, d_a, len); }
+
+// the bits of x, at least 1: the key width of a sort whose largest key is x
+inline uint32_t bits_of(uint64_t x) { uint32_t b = 1; while (b < 64 && (x >> b)) ++b; return b; }
 
 constexpr uint64_t RMQ_MAX_N = 1ull << 48;             // 64^PYR_MAX: the top level of the range-minimum index is one group
 

@@ -35,6 +35,9 @@ int bwt_dev(psacx_ctx* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_e
     return PSACX_OK;
 }
 
+template int bwt_dev<uint32_t>(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, const uint32_t*, uint8_t*, uint32_t*, uint64_t*);
+template int bwt_dev<uint64_t>(psacx_ctx*, const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint8_t*, uint32_t*, uint64_t*);
+
 // psacx_repeats_dev_*: the directories its kind needs, one launch over the ranks, the counts of the select bytes, their scan, and the
 // three lists (repeats.hpp).  Scratch in the ctx slab: the block sums of the scans first (exclusive_scan_dev puts them at the slab's
 // base), then bitmaps, directories, select bytes and tile counts.  The candidate intervals of a call that writes lists take 2 n
@@ -67,9 +70,7 @@ int repeats_dev(psacx_ctx* c, uint64_t n, const T* d_LCP, const T* d_index, cons
         d_sel = a.take<unsigned char>(ntiles * REP_TILE);
         d_counts = a.take<uint64_t>(ntiles + 1);
     };
-    { Arena dry(nullptr); layout(dry); PSACX_TRY(ensure_slab(c, dry.off + 4096)); }
-    Arena ar(c->slab);
-    layout(ar);
+    PSACX_TRY(slab_layout(c, layout));
     Staging s(c, "repeats");
     T *d_clb = nullptr, *d_cub = nullptr;
     if (d_lb) {
